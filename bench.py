@@ -12,6 +12,11 @@ resident in HBM).  For N>1 every rank runs its own 32 images (weak scaling) and 
 detections are all-gathered (RCCL) inside the timed step.  Rank 0 prints ONE JSON line.
 `--gpus N` with fewer than N visible GPUs, or a WORLD_SIZE that disagrees with N, exits non-zero: a run never reports
 fewer ranks than it was asked for.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can measure - the API-level
+detect() / detect_stream() rates, the sustained window, the fp32 mode, the solo-kernel table (roofline.dominant_kernel),
+socket power and the CPU baseline - runs only with `--full` (the `--no-*` options still switch single parts of it off).
+`--dump-outputs DIR` writes the detections of the last timed step as DIR/*.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -239,6 +244,23 @@ def solo_kernel_table(plan0, repeat=5):
     return sorted(groups.values(), key=lambda g: -g["ms"])
 
 
+def dump_outputs(out_dir, dets, counts):
+    """What a detect() caller receives for the last timed step, as .npy files in ``out_dir``:
+      * detections.npy - float32 [sum of counts, 7], the kept rows of every image back to back in image order (the
+        list[Tensor[n, 7] | None] of detect() concatenated; images without detections contribute no rows);
+      * detections_per_image.npy - float64 [images], how many rows of detections.npy belong to each image.
+    ``dets`` [images, cap, 7] / ``counts`` [images] are the step's output buffers (rows beyond a count are unspecified, so they
+    are not written).  The inputs are seeded, so two runs with the same arguments can be compared file by file."""
+    import numpy as np
+    d = dets.detach().cpu().numpy().astype(np.float32, copy=False)
+    c = counts.detach().cpu().numpy().astype(np.int64)
+    n = np.minimum(c, d.shape[1])
+    packed = np.concatenate([d[b, :k] for b, k in enumerate(n)], axis=0) if len(n) else np.zeros((0, 7), np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "detections.npy"), np.ascontiguousarray(packed, dtype=np.float32))
+    np.save(os.path.join(out_dir, "detections_per_image.npy"), n.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -263,9 +285,17 @@ def main():
     ap.add_argument("--no-sustained", action="store_true", help="skip the >= 2.5 s sustained-rate window after the timed region")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: rehearse the N-rank launcher and the all-gather over gloo, print a line with value null")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: API-level detect() / detect_stream() rates, the "
+                         "sustained window, the fp32 mode, the solo-kernel table, socket power and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's detections as DIR/detections.npy (float32 [n, 7]) and "
+                         "DIR/detections_per_image.npy (float64 [images])")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if "RANK" not in os.environ and (args.gpus > 1 or args.dry_run):
         sys.exit(launch_ranks(args, sys.argv[1:]))               # BEFORE any GPU call in this process
@@ -369,7 +399,7 @@ def main():
     # count D2H copy and the list[Tensor | None] split inside the timed region, host-synchronous); sharded runs time
     # detect_sharded (forward + NMS + all-gather + split on every rank)
     api_ips = stream_ips = None
-    if not args.no_api:
+    if args.full and not args.no_api:
         from pytorch_yolo_amd.distributed import detect_sharded
         k_api = max(3, min(args.steps, 20))
         with torch.no_grad():
@@ -399,6 +429,9 @@ def main():
             assert n_out == bs * n_stream
 
     with torch.no_grad():
+        for i in range(n_streams):        # set-up, untimed: the first launch of each pipeline loads code objects and creates streams
+            step(i, timed=False)
+        sync_all()
         for i in range(args.warmup):
             step(i)
         sync_all()
@@ -417,10 +450,12 @@ def main():
     conv_ms = [span_ms / args.steps]
     list_ms = [ev[i][0][0].elapsed_time(ev[i][0][1]) for i in range(args.warmup, total_steps)]      # one list, start to end
     n_dets = counts.cpu().tolist()
+    if args.dump_outputs and rank == 0:          # before anything below reuses the step buffers
+        dump_outputs(args.dump_outputs, dets, counts)
 
     # the same steps over a window of >= 2.5 s (the timed region of `--steps 20` is 0.1 s on a chip whose clock follows a power cap)
     sustained_ips = None
-    if world == 1 and not args.no_sustained:
+    if args.full and world == 1 and not args.no_sustained:
         n_sus = max(args.steps, int(2.5 / (dt / args.steps)) + 1)
         with torch.no_grad():
             sync_all()
@@ -433,7 +468,7 @@ def main():
     # the reference-precision mode (model.precision = "fp32": float32 activations and weights on the f32 MFMA, the mode whose NMS
     # kept-index sets equal the reference's end to end): detect() through the API, a few calls
     fp32_ips = None
-    if world == 1 and not args.no_api and args.workload in ("spp", "tiny"):
+    if args.full and world == 1 and not args.no_api and args.workload in ("spp", "tiny"):
         m32 = wl["cls"](**wl["kw"]).eval()
         m32.load_state_dict(synth_state_dict(m32.state_dict(), 1234, n_class=80))
         m32 = m32.to(dev)
@@ -541,7 +576,7 @@ def main():
                                "floor_ms": round(max(abytes / 6.3e12, flops_step / 1.25e15) * 1e3, 4),
                                "time_over_floor": round(conv_ms_avg / (max(abytes / 6.3e12, flops_step / 1.25e15) * 1e3), 2),
                                "mfma_tflops": round(achieved, 2), "mfma_frac": round(achieved / PEAK_BF16_TFLOPS, 4)}
-        if world == 1:
+        if args.full and world == 1:
             # the dominant kernel family by itself, live: every launch of one sub-batch list timed alone with HIP events
             with torch.no_grad():
                 tab = solo_kernel_table((plan._full[0] if whole else plan.subs[0]) if hasattr(plan, "subs") else plan)
@@ -551,13 +586,13 @@ def main():
                 "label": top["label"], "launches_per_list": top["launches"], "avg_ms_solo": round(top["ms"] / top["launches"], 4),
                 "flops_per_launch": top["flops"] / top["launches"], "achieved": round(tf, 1), "frac": round(tf / PEAK_BF16_TFLOPS, 4),
                 "share_of_list_time": round(top["ms"] / sum(g["ms"] for g in tab), 3)}
-        if world == 1 and not args.no_api:
+        if args.full and world == 1 and not args.no_api:
             with torch.no_grad():
                 pw = power_sample(lambda i: step(args.warmup + i % args.steps, timed=False))
             sync_all()
             if pw is not None:
                 out["roofline"]["power"] = pw
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.workload)
         print(json.dumps(out), flush=True)
     if sharded:

@@ -16,6 +16,58 @@ def load_golden(name):
     return np.load(os.path.join(GOLDEN, name + ".npz"))
 
 
+GOLDEN_THREADS = 8      # torch.set_num_threads() of tests/golden/make_golden.py: the CPU convs sum in a thread-count-dependent order
+
+
+def arith_fingerprint() -> str:
+    """SHA-256 of the bits of seeded fp32 conv / batch-norm / activation / decode ops on this CPU at GOLDEN_THREADS threads: the
+    torch CPU arithmetic the oracle runs on, and no oracle code."""
+    import hashlib
+    import torch.nn.functional as F
+    before = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    g = torch.Generator().manual_seed(20261016)
+    h = hashlib.sha256()
+    try:
+        with torch.no_grad():
+            for n, cin, cout, hw, k, s in ((1, 3, 32, 64, 3, 1), (2, 32, 64, 40, 3, 2), (1, 64, 128, 20, 3, 1), (2, 128, 64, 26, 1, 1),
+                                           (1, 256, 512, 13, 3, 1), (1, 512, 255, 10, 1, 1), (4, 64, 64, 16, 3, 1)):
+                x = torch.rand(n, cin, hw, hw, generator=g) - 0.5
+                w = (torch.rand(cout, cin, k, k, generator=g) - 0.5) / (cin * k * k) ** 0.5
+                y = F.conv2d(x, w, torch.rand(cout, generator=g) - 0.5, stride=s, padding=k // 2)
+                y = F.batch_norm(y, torch.rand(cout, generator=g), torch.rand(cout, generator=g) + 0.5, torch.rand(cout, generator=g) + 0.5,
+                                 torch.rand(cout, generator=g), eps=1e-5)
+                h.update(y.numpy().tobytes())
+                h.update(F.leaky_relu(y, 0.1).numpy().tobytes())
+            v = torch.linspace(-30.0, 30.0, 100003)
+            for t in (torch.sigmoid(v), torch.exp(v), F.interpolate(v.view(1, 1, 1, -1), scale_factor=2, mode="nearest"),
+                      F.max_pool2d(v[:100000].view(1, 1, 100, 1000), 5, 1, 2)):
+                h.update(t.numpy().tobytes())
+            io = (torch.rand(2, 3, 13, 13, 85, generator=g) - 0.5) * 20.0      # strided column slices, as in the YOLO decode
+            io[..., 0:2] = torch.sigmoid(io[..., 0:2])
+            io[..., 2:4] = torch.exp(io[..., 2:4]) * torch.rand(1, 3, 1, 1, 2, generator=g)
+            io[..., 4:] = torch.sigmoid(io[..., 4:])
+            io[..., :4] *= 32.0
+            h.update(io.numpy().tobytes())
+    finally:
+        torch.set_num_threads(before)
+    return h.hexdigest()
+
+
+_GOLDEN_ARITH = []
+
+
+def golden_arithmetic() -> bool:
+    """True when this CPU computes like the host that recorded the goldens (tests/golden/host_arithmetic.json): the oracle tests then
+    require bit-equality with them.  Elsewhere the reference itself would give other bits, and they use bounds measured for that."""
+    if not _GOLDEN_ARITH:
+        import json
+        with open(os.path.join(GOLDEN, "host_arithmetic.json")) as f:
+            want = json.load(f)["fingerprint"]
+        _GOLDEN_ARITH.append(arith_fingerprint() == want)
+    return _GOLDEN_ARITH[0]
+
+
 def build_case(case):
     """(product model in eval mode with seeded weights, state_dict, input x) for a MODEL/FULL case tuple."""
     family, kw, bs, h, w, wseed, xseed = case

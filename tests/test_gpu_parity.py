@@ -3006,13 +3006,14 @@ def test_detect_stream_yields_every_batch_in_order():
 @pytest.mark.parametrize("extra", [(), ("--pipeline", "halves", "--no-api"), ("--streams", "1", "--no-api")])
 def test_bench_line_contract(extra):
     """bench.py as the driver runs it (a child process, one JSON line on stdout): the contract keys, the roofline object and the
-    echo of --steps / --warmup, on the small workload in both pipeline modes."""
+    echo of --steps / --warmup, on the small workload in both pipeline modes; with --full, which adds the API / sustained / fp32
+    figures checked at the end."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "6", "--warmup", "2",
-                        "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -3035,3 +3036,33 @@ def test_bench_line_contract(extra):
     if not extra:
         assert d["config"]["detect_api_images_per_s"] > 0 and d["config"]["detect_stream_api_images_per_s"] > 0
         assert 0 < d["config"]["fp32_mode_images_per_s"] < d["value"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain bench.py run (no --full) times its steps and nothing else, and --dump-outputs writes the last timed step's
+    detections: the same files, bit for bit, from two runs with the same arguments, and the counts the result line reports."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "5", "--warmup", "2",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0
+        for k_ in ("detect_api_images_per_s", "detect_stream_api_images_per_s", "sustained_images_per_s", "fp32_mode_images_per_s"):
+            assert k_ not in d["config"], k_
+        assert "cpu_baseline" not in d and "dominant_kernel" not in d["roofline"] and "power" not in d["roofline"]
+        dets, per_image = np.load(out / "detections.npy"), np.load(out / "detections_per_image.npy")
+        assert dets.dtype == np.float32 and dets.ndim == 2 and dets.shape[1] == 7
+        assert per_image.dtype == np.float64 and per_image.shape == (d["config"]["images_per_gpu"],)
+        assert per_image.sum() == dets.shape[0] > 0
+        assert abs(per_image.mean() - d["config"]["mean_detections_per_image"]) <= 0.051      # (the line rounds to 0.1)
+        assert np.isfinite(dets).all()
+        runs.append((dets, per_image))
+    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])

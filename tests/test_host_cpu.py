@@ -421,8 +421,16 @@ def test_unsupported_widths_fail_loudly():
 
 def test_package_asks_for_enough_hardware_queues():
     """pytorch_yolo_amd/__init__.py: GPU_MAX_HW_QUEUES defaults to 8 (two pipelines + joined-call streams + all-gather side
-    stream + RCCL's own do not fit HIP's default 4 queues: two sub-batch pipelines on one queue serialise)."""
-    assert int(os.environ["GPU_MAX_HW_QUEUES"]) >= 8
+    stream + RCCL's own do not fit HIP's default 4 queues: two sub-batch pipelines on one queue serialise), and a value the caller
+    exported is left alone.  Checked in fresh interpreters: this process's environment is whatever started the test run."""
+    import subprocess
+    import sys
+    code = "import os, pytorch_yolo_amd; print(os.environ['GPU_MAX_HW_QUEUES'])"
+    base = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+    for env, check in ((base, lambda q: q >= 8), (dict(base, GPU_MAX_HW_QUEUES="12"), lambda q: q == 12)):
+        r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert check(int(r.stdout.split()[-1])), r.stdout
 
 
 def test_no_cpu_fallback():

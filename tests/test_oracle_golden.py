@@ -5,9 +5,36 @@ import pytest
 import torch
 
 import _cases as C
-from helpers import build_case, build_rule_case, build_separable_case, load_golden, oracle_forward, strict_share
+from helpers import GOLDEN_THREADS, build_case, build_rule_case, build_separable_case, golden_arithmetic, load_golden, oracle_forward, strict_share
 from oracle import blocks as ob
 from oracle import nms as onms
+
+# On a CPU whose fp32 arithmetic differs from the recording host's (helpers.golden_arithmetic() False), the reference itself gives
+# other bits, and the oracle is held to these bounds instead of bit-equality.  Measured at GOLDEN_THREADS threads on an AMD EPYC
+# 9575F against goldens recorded on an Intel Xeon: io / p within 9.0e-6 relative (lite_nc80) and 3.7e-4 absolute (tiny_kd2_nc80
+# boxes), io column sums within 9.7e-10 relative.  The bounds leave a margin of about 5x.
+XHOST_RTOL, XHOST_ATOL, XHOST_COLSUM_RTOL = 5e-5, 1e-5, 5e-9
+
+
+def assert_golden(got, want, what=""):
+    """Bit-equal on the recording host's arithmetic, within the measured cross-CPU bound elsewhere."""
+    if golden_arithmetic():
+        assert np.array_equal(got, want), what or "differs from the golden"
+    else:
+        np.testing.assert_allclose(got, want, rtol=XHOST_RTOL, atol=XHOST_ATOL, err_msg=what)
+
+
+def assert_colsum(io, g):
+    np.testing.assert_allclose(io.numpy().astype(np.float64).sum(1), g["io_colsum"], rtol=1e-9 if golden_arithmetic() else XHOST_COLSUM_RTOL)
+
+
+@pytest.fixture(autouse=True, scope="module")
+def _golden_thread_count():
+    """Run the oracle at the thread count the goldens were recorded with, so that bit-equality does not depend on the host's cores."""
+    before = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    yield
+    torch.set_num_threads(before)
 
 
 def test_kat_maxpool21(golden_dir):
@@ -47,9 +74,9 @@ def test_model_small_bit_exact(name):
     model, sd, x = build_case(case)
     io, p = oracle_forward(case, sd, x)
     g = load_golden("model_" + name)
-    assert np.array_equal(io.numpy(), g["io"])
+    assert_golden(io.numpy(), g["io"], "io")
     for k, t in enumerate(p):
-        assert np.array_equal(t.numpy(), g[f"p{k}"])
+        assert_golden(t.numpy(), g[f"p{k}"], f"p{k}")
 
 
 @pytest.mark.parametrize("name", ["tiny_small", "spp_small"])
@@ -71,12 +98,12 @@ def test_model_full_size_samples(name):
     io, p = oracle_forward(case, sd, x)
     g = load_golden("full_" + name)
     assert list(io.shape) == g["io_shape"].tolist()
-    assert np.array_equal(io.numpy()[:, g["rows"]], g["io_rows"])
-    np.testing.assert_allclose(io.numpy().astype(np.float64).sum(1), g["io_colsum"], rtol=1e-9)
+    assert_golden(io.numpy()[:, g["rows"]], g["io_rows"], "sampled io rows")
+    assert_colsum(io, g)
     for k, t in enumerate(p):
         assert list(t.shape) == g[f"p{k}_shape"].tolist()
     dets, kept = onms.non_max_suppression(io.numpy().copy(), **C.NMS_FULL)
-    _check_nms(dets, kept, g, prefix="nms_")
+    _check_nms(dets, kept, g, prefix="nms_", exact=golden_arithmetic())
 
 
 def test_separable_full_size_case():
@@ -92,10 +119,10 @@ def test_separable_full_size_case():
     with torch.no_grad():
         io, p = om.spp_forward(sd, x, C.SPP_ANCHORS, 80)
     assert list(io.shape) == g["io_shape"].tolist()
-    assert np.array_equal(io.numpy()[:, g["rows"]], g["io_rows"])
-    np.testing.assert_allclose(io.numpy().astype(np.float64).sum(1), g["io_colsum"], rtol=1e-9)
+    assert_golden(io.numpy()[:, g["rows"]], g["io_rows"], "sampled io rows")
+    assert_colsum(io, g)
     dets, kept = onms.non_max_suppression(io.numpy().copy(), sep["conf_thres"], sep["nms_thres"])
-    _check_nms(dets, kept, g, prefix="nms_")
+    _check_nms(dets, kept, g, prefix="nms_", exact=golden_arithmetic())
     assert int(g["nms_count_0"]) == 22 and float(g["nms_dets_0"][:, 4].min()) > 0.8 and int(g["n_between_04_06"]) == 0
     conf = g["nms_dets_0"][:, 4]
     assert len(np.unique(conf)) == len(conf)                                   # no ties: the reference's argsort order is defined
@@ -108,11 +135,20 @@ def test_separable_full_size_case():
     new_w, new_b = C.calibrate_separable_heads([sd0[k].numpy() for k in wk], [sd0[k].numpy() for k in bk], [t[0].numpy() for t in p0], 80,
                                                sep["per_anchor"], sep["span"], sep["gamma_obj"], sep["cls_gain"])
     for k in range(3):
-        assert np.array_equal(new_w[k], g[f"head_bn_weight_{k}"]) and np.array_equal(new_b[k], g[f"head_bn_bias_{k}"])
-    # the rounding model (fp32 oracle re-run under the product's bf16 rounding points) carries these detections strictly
+        assert_golden(new_w[k], g[f"head_bn_weight_{k}"], f"head {k} BN weight")
+        assert_golden(new_b[k], g[f"head_bn_bias_{k}"], f"head {k} BN bias")
+    # the rounding model (fp32 oracle re-run under the product's bf16 rounding points) carries these detections strictly; held against
+    # this host's own fp32 detections (on the recording arithmetic bit-equal to the golden ones, checked above)
     io_b, _ = run_policy(om.spp_forward, sd, x, C.SPP_ANCHORS, 80, policy="bf16")
     db, _ = onms.non_max_suppression(io_b.numpy().copy(), sep["conf_thres"], sep["nms_thres"])
-    assert strict_share(g["nms_dets_0"], db[0]) == 1.0 and strict_share(db[0], g["nms_dets_0"]) == 1.0
+    fwd, back = strict_share(dets[0], db[0]), strict_share(db[0], dets[0])
+    if golden_arithmetic():
+        assert fwd == 1.0 and back == 1.0, (fwd, back)
+    else:
+        # the seed was selected for this on the recording arithmetic; other fp32 sums tip a value across a bf16 rounding boundary, and
+        # one merge pile can resolve differently (AMD EPYC 9575F, 8 threads: one of the 22 fp32 detections unpaired, its bf16 pile split
+        # into two boxes, 21 pairs): at most one such pile
+        assert round((1 - fwd) * len(dets[0])) <= 1 and round((1 - back) * len(db[0])) <= 2, (fwd, back)
 
 
 def test_rule_selected_cases_are_what_the_rule_selects():
@@ -141,20 +177,24 @@ def test_rule_selected_cases_are_what_the_rule_selects():
             continue
         qualifying.append(seed)
         g = load_golden(f"full_spp_640_rule_{seed}")
-        assert np.array_equal(io.numpy()[:, g["rows"]], g["io_rows"]), "oracle differs from the reference on a rule case"
+        assert_golden(io.numpy()[:, g["rows"]], g["io_rows"], "oracle differs from the reference on a rule case")
         for k, h in enumerate(C.SEPARABLE_HEADS):
-            assert np.array_equal(sd[h + ".sequence.batch_norm.weight"].numpy(), g[f"head_bn_weight_{k}"])
-            assert np.array_equal(sd[h + ".sequence.batch_norm.bias"].numpy(), g[f"head_bn_bias_{k}"])
+            assert_golden(sd[h + ".sequence.batch_norm.weight"].numpy(), g[f"head_bn_weight_{k}"], f"head {k} BN weight")
+            assert_golden(sd[h + ".sequence.batch_norm.bias"].numpy(), g[f"head_bn_bias_{k}"], f"head {k} BN bias")
         live = [v for v in gaps if v is not None]
-        assert min(live) >= rule["min_gap_drifts"] * rule["drift"] and np.allclose([-1.0 if v is None else v for v in gaps], g["cut_gaps"])
+        assert min(live) >= rule["min_gap_drifts"] * rule["drift"]
+        np.testing.assert_allclose([-1.0 if v is None else v for v in gaps], g["cut_gaps"], rtol=1e-5 if golden_arithmetic() else XHOST_RTOL,
+                                   atol=1e-8)
         dets, kept = onms.non_max_suppression(io.numpy().copy(), rule["conf_thres"], rule["nms_thres"])
-        _check_nms(dets, kept, g, "nms_")
+        _check_nms(dets, kept, g, "nms_", exact=golden_arithmetic())
         conf = g["nms_dets_0"][:, 4]
         assert len(conf) >= rule["min_detections"] and len(np.unique(conf)) == len(conf) and conf.min() > rule["conf_thres"] + rule["conf_band"]
     assert tuple(qualifying) == tuple(C.RULE_SEEDS)
 
 
-def _check_nms(dets, kept, g, prefix=""):
+def _check_nms(dets, kept, g, prefix="", exact=True):
+    """``exact=False``: detections of an oracle forward on a CPU that does not compute like the recording one (golden_arithmetic()):
+    the same kept indices, classes and merged-box bound, confidences within XHOST_RTOL."""
     for b, (d, k) in enumerate(zip(dets, kept)):
         n = int(g[f"{prefix}count_{b}"])
         if n == 0:
@@ -163,7 +203,11 @@ def _check_nms(dets, kept, g, prefix=""):
         ref = g[f"{prefix}dets_{b}"]
         assert d.shape == ref.shape
         assert np.array_equal(k, g[f"{prefix}kept_{b}"]), "kept-index set differs from the reference"
-        assert np.array_equal(d[:, 4:], ref[:, 4:]), "conf / class_conf / class must be bit-equal"
+        if exact:
+            assert np.array_equal(d[:, 4:], ref[:, 4:]), "conf / class_conf / class must be bit-equal"
+        else:
+            assert np.array_equal(d[:, 6], ref[:, 6]), "class differs from the reference"
+            np.testing.assert_allclose(d[:, 4:6], ref[:, 4:6], rtol=XHOST_RTOL, atol=XHOST_ATOL)
         # merged boxes: torch's reduction order vs sequential fp32 -> a few ulp
         np.testing.assert_allclose(d[:, :4], ref[:, :4], rtol=2e-6, atol=2e-4)
 

@@ -7,10 +7,10 @@ export PYTHONPATH=$GRAFT_REPO_ROOT
 O=gpurun_out
 PART=${1:-all}
 if [ "$PART" != "pmc" ]; then
-  timeout -k 10 400 python bench.py > $O/r5p_bench_spp.json 2> $O/r5p_bench_spp.err; echo "bench spp rc $?"
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/r5p_bench_spp_driver.json 2> $O/r5p_bench_spp_driver.err; echo "bench spp (driver flags) rc $?"
+  timeout -k 10 400 python bench.py --full > $O/r5p_bench_spp.json 2> $O/r5p_bench_spp.err; echo "bench spp rc $?"
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/r5p_bench_spp_driver.json 2> $O/r5p_bench_spp_driver.err; echo "bench spp (driver flags) rc $?"
   for WL in tiny mobile efficient; do
-    timeout -k 10 300 python bench.py --workload $WL --no-cpu-baseline > $O/r5p_bench_$WL.json 2> $O/r5p_bench_$WL.err; echo "bench $WL rc $?"
+    timeout -k 10 300 python bench.py --full --workload $WL --no-cpu-baseline > $O/r5p_bench_$WL.json 2> $O/r5p_bench_$WL.err; echo "bench $WL rc $?"
   done
   python tools/layer_profile.py --workload spp --bs 32 --compact > $O/r5p_layers_spp.txt 2>&1
   python tools/layer_profile.py --workload tiny --compact > $O/r5p_layers_tiny.txt 2>&1

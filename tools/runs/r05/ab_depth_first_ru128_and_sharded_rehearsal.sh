@@ -20,7 +20,7 @@ for r in 1 2; do
   YOLO_RESUNIT_DEBUG=2048 run "round $r ru128 on 20x8 tiles" >> $O/r5b_ab.txt
 done
 cat $O/r5b_ab.txt
-YOLO_BENCH_SHARDED_AT_1=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --no-cpu-baseline > $O/r5b_bench_sharded1.json 2> $O/r5b_bench_sharded1.err; echo "sharded rc $?"
+YOLO_BENCH_SHARDED_AT_1=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --no-cpu-baseline > $O/r5b_bench_sharded1.json 2> $O/r5b_bench_sharded1.err; echo "sharded rc $?"
 python - <<'PY'
 import json
 j = json.loads(open("gpurun_out/r5b_bench_sharded1.json").read().strip().splitlines()[-1])

@@ -8,10 +8,10 @@ timeout -k 10 900 python -m pytest tests/ -x -q -m gpu > $O/r5z_gpu_suite.log 2>
 [ $rc -ne 0 ] && exit 1
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
 for WL in tiny mobile; do
-  timeout -k 10 300 python bench.py --workload $WL --no-cpu-baseline > $O/r5z_bench_$WL.json 2> $O/r5z_bench_$WL.err; echo "bench $WL rc $?"
+  timeout -k 10 300 python bench.py --full --workload $WL --no-cpu-baseline > $O/r5z_bench_$WL.json 2> $O/r5z_bench_$WL.err; echo "bench $WL rc $?"
   python tools/layer_profile.py --workload $WL --compact > $O/r5z_layers_$WL.txt 2>&1
 done
-timeout -k 10 400 python bench.py > $O/r5z_bench_spp.json 2> $O/r5z_bench_spp.err; echo "bench spp rc $?"
+timeout -k 10 400 python bench.py --full > $O/r5z_bench_spp.json 2> $O/r5z_bench_spp.err; echo "bench spp rc $?"
 python - <<'PY'
 import json
 for f in ("tiny", "mobile", "spp"):

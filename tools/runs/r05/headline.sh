@@ -4,8 +4,8 @@ cd $GRAFT_REPO_ROOT
 export PYTHONPATH=$GRAFT_REPO_ROOT
 O=gpurun_out
 for i in 1 2; do
-  timeout -k 10 400 python bench.py > $O/r5q_bench_spp_$i.json 2> $O/r5q_bench_spp_$i.err; echo "bench spp $i rc $?"
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/r5q_bench_spp_driver_$i.json 2> $O/r5q_bench_spp_driver_$i.err; echo "bench spp (driver flags) $i rc $?"
+  timeout -k 10 400 python bench.py --full > $O/r5q_bench_spp_$i.json 2> $O/r5q_bench_spp_$i.err; echo "bench spp $i rc $?"
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/r5q_bench_spp_driver_$i.json 2> $O/r5q_bench_spp_driver_$i.err; echo "bench spp (driver flags) $i rc $?"
 done
 python - <<'PY'
 import json

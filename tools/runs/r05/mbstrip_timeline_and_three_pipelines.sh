@@ -11,7 +11,7 @@ done
 unset YOLO_HIP_LIB
 for WL in tiny mobile; do
   for S in 2 3; do
-    timeout -k 10 300 python bench.py --workload $WL --streams $S --no-cpu-baseline --no-api > $O/r5r_bench_${WL}_s$S.json 2> $O/r5r_bench_${WL}_s$S.err; echo "bench $WL streams $S rc $?"
+    timeout -k 10 300 python bench.py --full --workload $WL --streams $S --no-cpu-baseline --no-api > $O/r5r_bench_${WL}_s$S.json 2> $O/r5r_bench_${WL}_s$S.err; echo "bench $WL streams $S rc $?"
   done
 done
 python - <<'PY'
