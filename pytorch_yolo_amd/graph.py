@@ -1,0 +1,180 @@
+"""The symbolic layer graph a model records once per (batch, H, W): ``Recorder`` and the ``Sym`` / ``Node`` / ``Buf`` records.
+
+A model's ``_trace`` method reads like the reference's ``_forward_encoder``; every call appends one ``Node``.  ``Node.attrs`` holds
+what the recorder wrote (weights, stride, activation, padding, name, pool geometry) and nothing else: what the planner decides
+lives in its own records (planner.Launch), where a tensor lives in ``Sym.buf`` / ``Sym.c_offset``."""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import List, Optional
+
+import torch
+
+from . import kernels as K
+
+
+@dataclass(eq=False)
+class Sym:
+    """A logical NHWC activation."""
+    n: int
+    h: int
+    w: int
+    c: int
+    producer: Optional["Node"] = None
+    slot: int = 0                      # 0 main output, 1 pre-add output
+    f32: bool = False
+    # placement (filled by the planner)
+    buf: Optional["Buf"] = None
+    c_offset: int = 0
+    consumers: List["Node"] = field(default_factory=list)
+
+
+@dataclass(eq=False)
+class Buf:
+    n: int
+    h: int
+    w: int
+    c_total: int
+    f32: bool = False
+    tensor: Optional[torch.Tensor] = None
+
+
+@dataclass(eq=False)
+class Node:
+    kind: str                          # input | conv | dwconv | pool | spp | up | cat | head
+    srcs: List[Sym]
+    outs: List[Sym]
+    attrs: dict
+
+
+class Recorder:
+    def __init__(self, n, c_in, h, w):
+        self.nodes: List[Node] = []
+        self.c_in = c_in
+        x = Sym(n, h, w, K.roundup(c_in, 8))
+        self.input = x
+        self._add("input", [], [x])
+        self.heads = []
+
+    def _add(self, kind, srcs, outs, **attrs):
+        node = Node(kind, list(srcs), list(outs), attrs)
+        for o in outs:
+            o.producer = node
+        for s in srcs:
+            s.consumers.append(node)
+        self.nodes.append(node)
+        return node
+
+    # weight = (w_oihw f32, bias f32) already BN-folded; act in {'leaky','relu6','none'}
+    @staticmethod
+    def tf_same(size: int, k: int, stride: int):
+        """TensorFlow "same" padding as efficientnet_pytorch 0.2.0's Conv2dSamePadding computes it: output ceil(size / stride),
+        total pad max((out - 1) stride + k - size, 0), the odd one BELOW / RIGHT.  Returns (out, leading pad)."""
+        out = -(-size // stride)
+        return out, max((out - 1) * stride + k - size, 0) // 2
+
+    def conv(self, x: Sym, weight, stride=1, act="leaky", residual: Sym = None, want_preadd=False, f32_out=False, pad=None,
+             name=None, tf_same=False):
+        w, _ = weight
+        cout, cin_w, k, _ = w.shape
+        if cin_w > x.c:
+            raise RuntimeError(f"conv expects {cin_w} input channels, tensor has {x.c}")
+        same = (k - 1) // 2
+        pad = same if pad is None else pad
+        ho, wo = (x.h + 2 * pad - k) // stride + 1, (x.w + 2 * pad - k) // stride + 1
+        if tf_same:
+            (ho, pad), (wo, pad_w) = self.tf_same(x.h, k, stride), self.tf_same(x.w, k, stride)
+            if pad != pad_w:
+                raise RuntimeError("tf_same conv: the two axes need different leading pads (one odd, one even size): not supported")
+        if not f32_out and cout % 8:
+            raise RuntimeError(f"internal conv width {cout} is not a multiple of 8 (unsupported kernels_divider)")
+        y = Sym(x.n, ho, wo, cout, f32=f32_out)
+        outs = [y]
+        if want_preadd:
+            outs.append(Sym(x.n, ho, wo, cout, slot=1))
+        srcs = [x] + ([residual] if residual is not None else [])
+        self._add("conv", srcs, outs, weight=weight, stride=stride, act=act, has_res=residual is not None, name=name)
+        if pad != same:
+            self.nodes[-1].attrs["pad"] = pad            # (SqueezeNet's unpadded first conv; no fused form takes it)
+        return (y, outs[1]) if want_preadd else y
+
+    def dwconv(self, x: Sym, weight, stride=1, act="relu6", tf_same=False):
+        """Depthwise k x k conv.  Default: 3x3 / pad 1 (MobileNetV2).  ``tf_same``: k = 3 or 5 with TensorFlow "same" padding
+        (EfficientNet-B0's MBConvBlock._depthwise_conv) - the general kernel, which also takes the swish activation."""
+        w, _ = weight                                   # [c,1,k,k]
+        k = w.shape[2]
+        if not tf_same:
+            if k != 3:
+                raise RuntimeError("dwconv: only 3x3 with torch-style pad 1; pass tf_same=True for k = 5")
+            ho, wo = (x.h - 1) // stride + 1, (x.w - 1) // stride + 1
+            y = Sym(x.n, ho, wo, x.c)
+            self._add("dwconv", [x], [y], weight=weight, stride=stride, act=act)
+            return y
+        (ho, pad), (wo, pad_w) = self.tf_same(x.h, k, stride), self.tf_same(x.w, k, stride)
+        if pad != pad_w:
+            raise RuntimeError("tf_same dwconv: the two axes need different leading pads: not supported")
+        y = Sym(x.n, ho, wo, x.c)
+        self._add("dwconv", [x], [y], weight=weight, stride=stride, act=act, ksize=k, pad=pad)
+        return y
+
+    def se(self, x: Sym, w1, b1, w2, b2):
+        """Squeeze-and-excitation: y = x * sigmoid(W2 swish(W1 mean_hw(x) + b1) + b2) (efficientnet_pytorch MBConvBlock).
+        w1: [sq, c] (or [sq, c, 1, 1]), w2: [c, sq]."""
+        y = Sym(x.n, x.h, x.w, x.c)
+        self._add("se", [x], [y], w1=w1, b1=b1, w2=w2, b2=b2)
+        return y
+
+    def maxpool(self, x: Sym, size, stride, pad=None, ceil_mode=False):
+        # reference MaxPool: (2,1) -> pad 1, dilation 2 (models/yolo_base.py:60-66)
+        if size == 2 and stride == 1:
+            pad, dil = 1, 2
+        else:
+            pad, dil = ((size - 1) // 2 if pad is None else pad), 1
+
+        def out(n):                                       # torch.nn.MaxPool2d output size incl. ceil_mode
+            span = n + 2 * pad - dil * (size - 1) - 1
+            o = (-(-span // stride) if ceil_mode else span // stride) + 1
+            return o - 1 if ceil_mode and (o - 1) * stride >= n + pad else o
+        ho, wo = out(x.h), out(x.w)
+        y = Sym(x.n, ho, wo, x.c)
+        self._add("pool", [x], [y], size=size, stride=stride, pad=pad, dil=dil)
+        return y
+
+    def spp_concat(self, x: Sym):
+        y = Sym(x.n, x.h, x.w, 4 * x.c)
+        self._add("spp", [x], [y])
+        return y
+
+    def upsample2(self, x: Sym):
+        y = Sym(x.n, 2 * x.h, 2 * x.w, x.c)
+        self._add("up", [x], [y])
+        return y
+
+    def concat(self, xs: List[Sym]):
+        y = Sym(xs[0].n, xs[0].h, xs[0].w, sum(x.c for x in xs))
+        self._add("cat", xs, [y])
+        return y
+
+    def slice(self, x: Sym, offset: int, c: int):
+        """Channel view [offset, offset + c) of ``x`` (8-channel aligned): no launch, the consumers read the view."""
+        if offset % 8 or c % 8 or offset + c > x.c:
+            raise RuntimeError("slice: views are 8-channel aligned")
+        y = Sym(x.n, x.h, x.w, c)
+        self._add("slice", [x], [y], offset=offset)
+        return y
+
+    def shuffle2(self, a: Sym, b: Sym, half: int):
+        """ShuffleNetV2's ``channel_shuffle(cat(a, b), groups=2)`` for two tensors of ``half`` logical channels each,
+        every one held in a slot of a.c == b.c >= half physical channels (zero beyond ``half``): logical channel j of the
+        result is (a, b)[j % 2][j // 2]; the result keeps the two-slot layout (logical [0, half) in slot 0, [half, 2 half)
+        in slot 1)."""
+        if a.c != b.c or half > a.c or (a.h, a.w) != (b.h, b.w):
+            raise RuntimeError("shuffle2: mismatched halves")
+        y = Sym(a.n, a.h, a.w, 2 * a.c)
+        self._add("shuffle", [a, b], [y], half=half)
+        return y
+
+    def head(self, x: Sym, yolo_layer):
+        self.heads.append((x, yolo_layer))
+        self._add("head", [x], [])
+

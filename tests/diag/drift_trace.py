@@ -63,19 +63,19 @@ def main():
         one = C.cast(C.byref(plan.op_array, i * C.sizeof(YoloOp)), C.POINTER(YoloOp))
         K.run_ops(one, 1)
         torch.cuda.synchronize()
-        nd = plan.op_nodes[i]
+        launch = plan.op_launches[i]
+        nd = launch.node
         name = nd.attrs.get("name") if nd.kind == "conv" else None
         if name is None:
             lines.append(f"| {i} | ({nd.kind}) | - | | | |")
             continue
-        kind = ("stem" if "stem_pre" in nd.attrs else "resunit" if "fuse_pre" in nd.attrs else "head+decode" if nd.attrs.get("head_fused")
-                else "conv")
+        kind = "head+decode" if launch.kind == "head" else launch.kind
         key = name
         if nd.attrs["has_res"]:                                    # the launch stores x + conv: compare with the Add's output
             m = re.match(r"(down\d+)\.seq(\d+)\.1$", name)
             key = f"{m.group(1)}.add{m.group(2)}"
         r32, r16 = t32[key], t16[key]
-        if nd.attrs.get("head_fused"):
+        if launch.kind == "head":
             hd = plan.heads[head_i]
             got = ps[plan.heads.index(next(h for h in plan.heads if h["op"] == i))].cpu()       # [bs,na,ny,nx,no] raw logits
             bs, na, ny, nx, no = got.shape
@@ -83,11 +83,10 @@ def main():
             r32, r16 = conv(r32), conv(r16)
             head_i += 1
         else:
-            dst = nd.attrs.get("pool_into") or nd.attrs.get("up_into") or nd.outs[0]
-            got = _sym_to_nchw(dst).cpu()
-            if nd.attrs.get("up_into") is not None:
+            got = _sym_to_nchw(launch.dst).cpu()
+            if launch.up:
                 r32, r16 = (F.interpolate(t, scale_factor=2, mode="nearest") for t in (r32, r16))
-            elif nd.attrs.get("pool_into") is not None:
+            elif launch.pooled:
                 r32, r16 = (F.max_pool2d(t, 2, 2) for t in (r32, r16))
         lines.append(f"| {i} | {key} | {kind} | {rel_rms(got, r32):.5f} | {rel_rms(got, r16):.5f} | {rel_rms(r16, r32):.5f} |")
     torch.cuda.synchronize()

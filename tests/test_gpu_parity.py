@@ -2034,8 +2034,7 @@ def test_benched_list_diverges_only_where_the_summation_order_does():
                 K.set_launch_cus(old)
         outs = []
         for plan in (pa, pb):
-            nd = plan.op_nodes[i]
-            sy = (nd.attrs.get("up_into") or nd.attrs.get("pool_into") or nd.outs[0]) if nd.kind == "conv" else nd.outs[0]
+            sy = plan.op_launches[i].dst
             outs.append(sy.buf.tensor[:16, ..., sy.c_offset:sy.c_offset + sy.c])
         a, b = outs
         if names[0] == names[1] and not diverged:
@@ -2057,7 +2056,7 @@ def test_benched_list_diverges_only_where_the_summation_order_does():
 
 @pytest.mark.parametrize("spec", ["0-5:2", "0-2:4,2-5:2"])
 def test_depth_first_sub_batch_lists_are_bit_equal(spec, monkeypatch):
-    """engine.Plan._depth_first (YOLO_DEPTH_FIRST): the first launches of the YOLOv3-SPP list run as S passes over image sub-batches
+    """diag._depth_first (YOLO_DEPTH_FIRST): the first launches of the YOLOv3-SPP list run as S passes over image sub-batches
     (stem -> 64-channel unit -> stride-2 conv -> the two 128-channel units, reference models/yolov3_spp.py:98-125) so that a
     producer's output is still in the Infinity Cache when its consumer reads it.  Same kernels, same tiles (a tile never crosses an
     image): every output - decoded rows and raw head tensors - must be BIT-EQUAL to the plain list's, twice in a row.  (16 images:

@@ -195,8 +195,34 @@ def test_planner_tiny_and_mobile():
     assert sum(1 for o in _ops(plan) if o.kind == OP_CONV and o.residual) == 0           # the identity shortcuts are inside the fused blocks
 
 
+def test_every_node_belongs_to_one_launch_and_attrs_stay_the_recorders():
+    """The planner's bookkeeping: over the plans of the SPP, tiny and mobile families every recorded node is the ``node`` of
+    exactly one launch, a member of exactly one launch's ``pre`` (swallowed by a fused launch), or of a kind that never launches;
+    the launch records are typed (planner.Launch), and building a plan leaves every ``Node.attrs`` key set as the recorder wrote it."""
+    from pytorch_yolo_amd.planner import NO_LAUNCH, RULES, Launch
+    assert NO_LAUNCH == ("input", "up", "cat", "slice", "head") and len(set(RULES)) == len(RULES) == 8
+    for model, hw, bs in ((YOLOv3SPP(anchors=C.SPP_ANCHORS).eval(), 640, 8), (YOLOv3Tiny().eval(), 416, 1), (YOLOv3TinyMobile().eval(), 416, 1)):
+        for precision in ("bf16", "fp32") if not isinstance(model, YOLOv3TinyMobile) else ("bf16",):
+            rec = engine.Recorder(bs, 3, hw, hw)
+            model._trace(rec, rec.input)
+            keys = [sorted(nd.attrs) for nd in rec.nodes]
+            plan = engine.Plan(rec, torch.device("cpu"), model.n_class, hw, precision)
+            assert [sorted(nd.attrs) for nd in rec.nodes] == keys, "a planner pass wrote to Node.attrs"
+            assert all(isinstance(L, Launch) for L in plan.launches) and len({id(L) for L in plan.launches}) == len(plan.launches)
+            leads, swallowed = [L.node for L in plan.launches], [m for L in plan.launches for m in L.pre]
+            for nd in rec.nodes:
+                n_lead, n_pre = sum(1 for m in leads if m is nd), sum(1 for m in swallowed if m is nd)
+                assert (n_lead, n_pre) in ((1, 0), (0, 1)) or (n_lead == n_pre == 0 and nd.kind in NO_LAUNCH), \
+                    f"{nd.kind} node: node of {n_lead} launches, swallowed by {n_pre}"
+            # every op knows its launch, and through it the tensor it writes (None: a head's rows of io)
+            assert len(plan.op_launches) == plan.n_ops and plan.op_nodes == [L.node for L in plan.op_launches]
+            assert all((L.dst is None) == (L.kind == "head") and (L.dst is None or L.dst.buf is not None) for L in plan.op_launches)
+            if precision == "fp32":
+                assert all(L.kind in ("conv", "pool", "spp") and not (L.pooled or L.reads_nchw) for L in plan.launches)
+
+
 def test_depth_first_sub_batches_of_the_first_stages(monkeypatch):
-    """YOLO_DEPTH_FIRST="a-b:S,...": launches [a, b) of the list become S passes over image sub-batches (engine.Plan._depth_first) -
+    """YOLO_DEPTH_FIRST="a-b:S,...": launches [a, b) of the list become S passes over image sub-batches (diag._depth_first) -
     same ops, batch size n / S, every batch-major pointer moved by the sub-batch's first image; everything behind keeps its order,
     the head ops' indices follow, and the input pointer is patched into every sub-launch that reads the caller's batch."""
     model = YOLOv3SPP(anchors=C.SPP_ANCHORS).eval()
@@ -237,7 +263,7 @@ def test_every_launch_stays_inside_the_plans_allocations(family, bs, hw, precisi
     range each pointer may be dereferenced over BY THE C ABI'S CONTRACT (include/yolo_hip.h: a view is [n, h, w, c_total] elements
     from its base, a packed weight matrix is cout_pad x kpad, a bias is cout_pad floats) must lie inside ONE allocation the plan
     owns (an activation buffer or a packed weight it keeps alive), reads and writes alike; buffers that share storage
-    (engine.Plan._alloc) must have identical extents.  Catches planner errors: a view wider than its buffer, a shared buffer of
+    (planner.alloc) must have identical extents.  Catches planner errors: a view wider than its buffer, a shared buffer of
     another size, a weight packed for fewer input channels than the conv reads, a pooled / upsampled output sized for the wrong map.
     (The kernels' own indexing is audited dynamically on the GPU: test_launch_lists_stay_inside_their_buffers.)"""
     from pytorch_yolo_amd._lib import OP_CONV_F32, OP_MAXPOOL_F32
@@ -442,7 +468,7 @@ def test_no_cpu_fallback():
         non_max_suppression(torch.rand(1, 10, 8))
     import pytorch_yolo_amd
     src = "".join(open(os.path.join(os.path.dirname(pytorch_yolo_amd.__file__), f)).read()
-                  for f in ("engine.py", "kernels.py", "_lib.py", "distributed.py"))
+                  for f in ("engine.py", "graph.py", "planner.py", "emit.py", "diag.py", "kernels.py", "_lib.py", "distributed.py"))
     assert "oracle" not in src, "the product must never import the oracle"
 
 

@@ -21,12 +21,6 @@ from pytorch_yolo_amd._lib import OP_CONV, OP_HEAD_DECODE, OP_RESUNIT, YoloOp
 from pytorch_yolo_amd.utils.synthetic import synth_images
 
 
-def out_sym(nd):
-    if nd.kind == "conv":
-        return nd.attrs.get("up_into") or nd.attrs.get("pool_into") or nd.outs[0]
-    return nd.outs[0]
-
-
 def main():
     dev = torch.device("cuda", 0)
     model, sd, _ = build_case(CS.FULL_CASES["spp_640"])
@@ -57,7 +51,7 @@ def main():
             k = [h["op"] for h in pa.heads].index(i)
             a, b = psa[k].double(), psb[k][:16].double()
         else:
-            sa, sb = out_sym(pa.op_nodes[i]), out_sym(pb.op_nodes[i])
+            sa, sb = pa.op_launches[i].dst, pb.op_launches[i].dst
             a = sa.buf.tensor[..., sa.c_offset:sa.c_offset + sa.c].double()
             b = sb.buf.tensor[:16, ..., sb.c_offset:sb.c_offset + sb.c].double()
         d = (a - b)
