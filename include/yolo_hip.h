@@ -49,7 +49,7 @@ YOLO_API const char* yolo_last_error(void);
 YOLO_API int yolo_abi_version(void);
 /* Tuning / A-B hook (process-wide, not part of the numerics contract): overrides what the environment variables
  * YOLO_CONV_VARIANT (knob 0), YOLO_CONV_DEBUG (knob 1), YOLO_CONV_PP (knob 2), YOLO_RESUNIT_DEBUG (knob 3) and YOLO_MBCONV_DEBUG (knob 4) set at load time.
- * Returns the old value. */
+ * Returns the old value.  pytorch_yolo_amd/csrc/tuning.h names every bit of every knob. */
 YOLO_API int yolo_set_tuning(int knob, int value);
 
 /* ---- input packing: the `imgs.to(device)` + first-layer layout step (utils/utils.py:374) -----

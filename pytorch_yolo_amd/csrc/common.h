@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include "../../include/yolo_hip.h"
+#include "tuning.h"
 
 typedef __bf16 bf16_t;
 typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const ConvArgs a
       const int piece = i * 4 + wave, kc = piece >> 3, pb = piece & 7;
       const int px = p0 + pb * 16 + drow;
       const uint32_t vo = px < a.M ? (uint32_t)(p0 + pb * 16) * x_pitch + lane_src : kOobOffset;
-      if (!(a.debug & 1)) lds_dma16s(rx, smem + piece * 1024, vo, (uint32_t)kc * 64u);
+      if (!(a.debug & kCdNoPixelDma)) lds_dma16s(rx, smem + piece * 1024, vo, (uint32_t)kc * 64u);
     }
     wait_vmcnt<0>();
     __syncthreads();
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const ConvArgs a
     for (int f = 0; f < NF; ++f)
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[f][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (!(a.debug & 4))
+    if (!(a.debug & kCdNoMfma))
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc)
 #pragma unroll
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(const ConvArgs a
         for (int f = 0; f < NF; ++f) acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wreg[f][kc], xf, acc[f][j], 0, 0, 0);
       }
     __syncthreads();                                  // every wave is done with the pixel tile: stage the result over it
-    if (a.debug & 8) continue;                        // (timing-only ablations: bit 1 no DMA, 4 no MFMA, 8 no staging / stores)
+    if (a.debug & kCdNoEpilogue) continue;                        // (timing-only ablations, as in the other conv kernels)
     auto stage = [&](auto act) {
 #pragma unroll
       for (int f = 0; f < NF; ++f)
@@ -281,8 +281,8 @@ int yolo_conv::launch_stream1x1(const ConvArgs& a, int force, hipStream_t s) {
   // 0.0412 -> 0.0322).  With apply_act's former branch chain in the staging loop the same kernel LOST to the tiled one
   // (0.0255 vs 0.0207): four waves per workgroup have nobody to hide a serial epilogue behind.
   if (!force && a.M < 40000) return 1;
-  // round 5: the pipelined form for the 128-cout layers (YOLO_CONV_DEBUG bit 33554432: the first form, for A/Bs)
-  if (!(a.debug & 33554432)) {
+  // round 5: the pipelined form for the 128-cout layers (kCdStreamFirstForm: the first form, for A/Bs)
+  if (!(a.debug & kCdStreamFirstForm)) {
     if (d.cout == 128 && d.cin == 256) return launch_stream2<128, 256, 80>(a, s);
     if (d.cout == 128 && d.cin == 128) return launch_stream2<128, 128, 80>(a, s);
     if (d.cout == 128 && d.cin == 384) return launch_stream2<128, 384, 48>(a, s);

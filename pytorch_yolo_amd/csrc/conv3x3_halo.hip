@@ -88,13 +88,13 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv3x3_halo_kernel(co
     char* const base = s_halo + hb * HALO_B + wave * 1024;
 #pragma unroll
     for (int it = 0; it < HPT; ++it)
-      if (it >= lo && it < hi && !(a.debug & 1)) lds_dma16s(rx, base + it * (NW * 1024), h_off[it], (uint32_t)c * (CK * 2u));
+      if (it >= lo && it < hi && !(a.debug & kCdNoPixelDma)) lds_dma16s(rx, base + it * (NW * 1024), h_off[it], (uint32_t)c * (CK * 2u));
   };
   auto issue_w = [&](int wb, int c, int tap) {
     char* const base = s_w + wb * WBUF_B + wave * 1024;
 #pragma unroll
     for (int it = 0; it < WIT; ++it)
-      if (!(a.debug & 2)) lds_dma16s(rw, base + it * (NW * 1024), w_off[it], (uint32_t)((tap * d.cin + c * CK) * 2));
+      if (!(a.debug & kCdNoWeightDma)) lds_dma16s(rw, base + it * (NW * 1024), w_off[it], (uint32_t)((tap * d.cin + c * CK) * 2));
   };
 
   // ---- fragment row bases: tile pixel q = wm*TM + j*32 + r32 -> halo row of tap (0,0)
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv3x3_halo_kernel(co
             for (int j = 0; j < NI16; ++j)
               acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], xf[j], acc16[i][j], 0, 0, 0);
         }
-      } else if (!(a.debug & 4)) {
+      } else if (!(a.debug & kCdNoMfma)) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           const int g = ks * 2 + khalf;
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void conv3x3_halo_kernel(co
     }
   }
 
-  if (a.debug & 8) {
+  if (a.debug & kCdNoEpilogue) {
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -417,11 +417,11 @@ int yolo_conv::launch_halo3x3(const ConvArgs& a, hipStream_t s) {
     const bool one = d.cin == 64;
     // 128 couts per block with ONE halo buffer = 73 KB of LDS, i.e. two blocks per CU: they drift apart, so one
     // block's epilogue (a third of a layer's time on the 80x80 maps) runs under the other's MFMA loop.  Measured
-    // -12..-14 % per layer against 256 couts per block (146 KB, one block per CU); YOLO_CONV_DEBUG bit 1024 selects
+    // -12..-14 % per layer against 256 couts per block (146 KB, one block per CU); kCdHalo256Couts selects
     // the old form.  (128 couts with two halo buffers, 114 KB, is the worst of the three.)
-    if (d.cout % 256 == 0 && (a.debug & 1024)) return one ? launch<16, 16, 256, 4, 2, 64, 1>(a, s) : launch<16, 16, 256, 4, 2, 64, 2>(a, s);
-    // v_mfma_f32_16x16x32_bf16 form (the chip holds a higher clock on it): -6 % per layer; bit 65536 selects 32x32x16
-    if (d.cout % 128 == 0 && !(a.debug & 65536)) return launch<16, 16, 128, 4, 2, 64, 1, true>(a, s);
+    if (d.cout % 256 == 0 && (a.debug & kCdHalo256Couts)) return one ? launch<16, 16, 256, 4, 2, 64, 1>(a, s) : launch<16, 16, 256, 4, 2, 64, 2>(a, s);
+    // v_mfma_f32_16x16x32_bf16 form (the chip holds a higher clock on it): -6 % per layer; kCdHaloMfma32x32 selects 32x32x16
+    if (d.cout % 128 == 0 && !(a.debug & kCdHaloMfma32x32)) return launch<16, 16, 128, 4, 2, 64, 1, true>(a, s);
     if (d.cout % 128 == 0) return launch<16, 16, 128, 4, 2, 64, 1>(a, s);
     return one ? launch<16, 16, 64, 4, 1, 64, 1>(a, s) : launch<16, 16, 64, 4, 1, 64, 2>(a, s);
   }

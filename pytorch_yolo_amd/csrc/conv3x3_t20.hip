@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_t20v2_kernel(const ConvArgs a)
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("s_nop 15\n\ts_nop 15");              // the last asm MFMAs' D registers: 12 wait states before any other reader
 #endif
-  if (a.debug & 8) return;
+  if (a.debug & kCdNoEpilogue) return;
 
   // ---- epilogue (the final barrier of the loop has passed: the halo buffers are free; the weight prefetches of the two
   // steps beyond the end land in registers nobody reads)
@@ -494,7 +494,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_t20_kernel(const ConvArgs a)
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("s_nop 15\n\ts_nop 15");              // the last asm MFMAs' D registers: 12 wait states before any other reader
 #endif
-  if (a.debug & 8) return;
+  if (a.debug & kCdNoEpilogue) return;
   wait_vmcnt<0>();                                     // (the dummy plane behind the last chunk is still landing in buffer 0)
   __builtin_amdgcn_s_barrier();
   t20v2_epilogue<RD, LEAKY>(a, smem, acc, wave, lane, b, y0, x0, n0);
@@ -506,9 +506,9 @@ int launch_t20s2(const ConvArgs& a, hipStream_t s) {
   const long grid = (long)a.d.n * ((a.d.ho + kT20 - 1) / kT20) * ((a.d.wo + kT20 - 1) / kT20) * b.n_tiles;
   if (grid > 0x7fffffffL) return yolo_set_error(YOLO_E_UNSUPPORTED, "conv grid too large");
   if (pick_only("t20s2<400px x 128 couts, 4 waves, parity planes> grid %ld", grid)) return 0;
-  // (chunk pairs where the layer has an even number of 32-channel chunks: every stride-2 layer of YOLOv3-SPP; YOLO_CONV_DEBUG bit
-  // 16777216 keeps the chunk-by-chunk order for A/Bs)
-  const bool pair = (a.d.cin / 32) % 2 == 0 && !(a.debug & 16777216);
+  // (chunk pairs where the layer has an even number of 32-channel chunks: every stride-2 layer of YOLOv3-SPP; kCdT20NoChunkPairs
+  // keeps the chunk-by-chunk order for A/Bs)
+  const bool pair = (a.d.cin / 32) % 2 == 0 && !(a.debug & kCdT20NoChunkPairs);
   if (pair) {
     if (a.d.act == YOLO_ACT_LEAKY01) hipLaunchKernelGGL((conv3x3s2_t20_kernel<3, 3, 2, true, true>), dim3((unsigned)grid), dim3(256), 0, s, b);
     else hipLaunchKernelGGL((conv3x3s2_t20_kernel<3, 3, 2, false, true>), dim3((unsigned)grid), dim3(256), 0, s, b);

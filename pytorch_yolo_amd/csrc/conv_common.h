@@ -22,51 +22,62 @@ constexpr uint32_t kOobOffset = 0xF0000000u;  // > any buffer we accept (host ch
 
 // YOLOLayer decode fused into a head conv's epilogue (conv_igemm.hip, DECODE instances)
 struct HeadDecodeArgs {
-  float* io;            // [bs, io_rows_total, no]
-  float* p;             // [bs, na, ny, nx, no] or null
-  int na, no, io_rows_total, io_row_offset;
-  float stride;
-  float anchor_w[4], anchor_h[4];   // anchors_px / stride (yolo_layer.py:109)
+  float* io = nullptr;  // [bs, io_rows_total, no]
+  float* p = nullptr;   // [bs, na, ny, nx, no] or null
+  int na = 0, no = 0, io_rows_total = 0, io_row_offset = 0;
+  float stride = 0.f;
+  float anchor_w[4] = {}, anchor_h[4] = {};   // anchors_px / stride (yolo_layer.py:109)
   // filter mode (yolo_head_decode_filter_fwd; io == nullptr): the epilogue runs the NMS row filter on its own decoded rows and
   // leaves a key per row + the survivors' records in the compact NMS workspace (nms_common.h) instead of storing io
-  float* rec;                        // [bs][io_rows_total][8]: x, y, w, h, class score of a surviving row, at its io row
-  unsigned long long* row_keys;      // [bs][io_rows_total]: the row's sort key if it survives, ~0 otherwise
-  float conf_thres, min_wh;
+  float* rec = nullptr;                   // [bs][io_rows_total][8]: x, y, w, h, class score of a surviving row, at its io row
+  unsigned long long* row_keys = nullptr; // [bs][io_rows_total]: the row's sort key if it survives, ~0 otherwise
+  float conf_thres = 0.f, min_wh = 0.f;
 };
 
 struct ConvArgs {
-  const bf16_t* x;
-  const bf16_t* w;
-  const float* bias;
-  const bf16_t* res;
-  void* y;
-  bf16_t* aux;
-  YoloConvDesc d;
-  int M;        // n*ho*wo
-  int n_tiles;  // cout tiles
-  int steps;    // kpad / 32
-  uint32_t x_bytes, w_bytes;
+  const bf16_t* x = nullptr;
+  const bf16_t* w = nullptr;
+  const float* bias = nullptr;
+  const bf16_t* res = nullptr;
+  void* y = nullptr;
+  bf16_t* aux = nullptr;
+  YoloConvDesc d = {};
+  int M = 0;        // n*ho*wo
+  int n_tiles = 0;  // cout tiles
+  int steps = 0;    // kpad / 32
+  uint32_t x_bytes = 0, w_bytes = 0;
   HeadDecodeArgs hd;   // DECODE instances only
   // split-K launches (conv_igemm_bf16_kernel<..., SPLITK>): grid.y = splits, `steps` = K steps PER split; every split
   // writes its fp32 partial tile to ws[split][M][cout], the last one to arrive at a tile (cnt[tile], self-resetting)
   // adds the partials in split order and runs the normal epilogue
-  int splits;
-  float* ws;
-  int* cnt;
-  int debug;    // YOLO_CONV_DEBUG / yolo_set_tuning(1, .), timing ablations and A/B rules only (results are wrong with bits 1..8 set).
-                // Ablation bits every conv kernel understands:   1 no pixel DMA   2 no weight DMA   4 no MFMA   8 no epilogue
-                // Rule bits of the dispatcher (conv_igemm.hip):  16 no LDS-staged epilogue   32 no halo kernel   128 no 128x256 tiles
-                //   256 no loader waves   512 8-wave 256x256 tiles   2048 32x32x16 MFMA in the gather kernel   8192 4-wave 128x128 / head
-                //   tiles   16384 two-stage ring for the loader-wave tiles   32768 64x64 tiles for every tiny-grid 1x1 layer
-                //   4194304 two-stage 64x64 tiles;   halo kernel: 1024 blocks of 256 couts   65536 32x32x16 MFMA
-                // Kernel FAMILIES are selected by the other knob, YOLO_CONV_PP / yolo_set_tuning(2, .): 8 no halo kernel, 16 / 64 the
-                //   20x20-tile kernels always / never, 1024 / 2048 the streaming 1x1 never / always.  YOLO_RESUNIT_DEBUG (fused units):
-                //   8 no epilogue, 32 generic 16x16 kernel for C = 64, 64 / 128 the 20-pixel-wide tile kernels always / never,
-                //   512 one workgroup per CU, 1024 dump tile 0's intermediate (tools/dbg/ruw_tdump.py).
+  int splits = 1;
+  float* ws = nullptr;
+  int* cnt = nullptr;
+  int debug = 0;   // the launcher's tuning word (tuning.h): Tuning::conv_debug for the conv kernels, Tuning::resunit for the fused units
 #ifdef YOLO_STAMPS
-  unsigned long long* stamps;   // diagnostic build only (tools/block_timeline.py): 4 words per workgroup
+  unsigned long long* stamps = nullptr;   // diagnostic build only (tools/block_timeline.py): 4 words per workgroup
 #endif
 };
+
+// Bytes behind the x view and the packed weights of a layer (the kernels address them with 32-bit offsets: callers check < kOobOffset)
+inline size_t conv_x_bytes(const YoloConvDesc& d) { return (size_t)d.n * d.h * d.w * d.in_c_total * 2; }
+inline size_t conv_w_bytes(const YoloConvDesc& d) { return (size_t)d.cout_pad * d.kpad * 2; }
+
+// The arguments every conv launcher starts from; whatever else a kernel family needs (n_tiles, debug, hd, split-K) the caller sets.
+inline ConvArgs make_conv_args(const void* x, const void* w, const float* bias, const void* res, void* y, void* aux, const YoloConvDesc& d) {
+  ConvArgs a;
+  a.x = (const bf16_t*)x;
+  a.w = (const bf16_t*)w;
+  a.bias = bias;
+  a.res = (const bf16_t*)res;
+  a.y = y;
+  a.aux = (bf16_t*)aux;
+  a.d = d;
+  a.M = d.n * d.ho * d.wo;
+  a.x_bytes = (uint32_t)conv_x_bytes(d);
+  a.w_bytes = (uint32_t)conv_w_bytes(d);
+  return a;
+}
 
 // Diagnostic build (-DYOLO_STAMPS, never the shipped library): the first lane of every workgroup records when it
 // started and ended (s_memrealtime, 100 MHz), how many shader cycles that took (s_memtime) and where it ran
@@ -332,7 +343,6 @@ __device__ __forceinline__ int xcd_swizzle(int bid, int nblk) {
 // kernel instance they would launch there and return 0 WITHOUT launching (no GPU needed).
 bool resunit_t20_applies(int c, int n, int h, int w);   // conv_resunit_t20.hip: the shipped rule of the 20-pixel-wide tile kernels
 int launch_resunit_t20(const ConvArgs& c, const bf16_t* w1, const float* b1, int kpad1, uint32_t w1_bytes, bool force, hipStream_t s);
-int& resunit_debug();              // conv_resunit.hip: YOLO_RESUNIT_DEBUG / yolo_set_tuning(3, .)
 int launch_cus();                  // compute units the coming launches may use (256, or a CU-masked stream's share)
 char* pick_buffer();
 bool pick_only(const char* fmt, ...);   // true (and the name recorded) in pick mode

@@ -178,12 +178,12 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16
       for (int it = 0; it < PIT; ++it) {
         if (it < lo || it >= hi) continue;
         const uint32_t voff = (px_mask[it] & bit) ? (uint32_t)px_base[it] + tap_off : kOobOffset;
-        if (!(a.debug & 1)) lds_dma16(rx, xb + it * (NL * 1024), voff);
+        if (!(a.debug & kCdNoPixelDma)) lds_dma16(rx, xb + it * (NL * 1024), voff);
       }
 #pragma unroll
       for (int it = 0; it < WIT; ++it) {
         if (PIT + it < lo || PIT + it >= hi) continue;
-        if (!(a.debug & 2)) lds_dma16s(rw, wb + it * (NL * 1024), w_off[it], (uint32_t)step * (BK * 2u));
+        if (!(a.debug & kCdNoWeightDma)) lds_dma16s(rw, wb + it * (NL * 1024), w_off[it], (uint32_t)step * (BK * 2u));
       }
     } else {
       const bool tap_ok = tap < ntaps;
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16
 #pragma unroll
       for (int kk = 0; kk < BK / 32; ++kk) {
         if (more) issue(nb, s + NS - 1, kk * LPS / (BK / 32), (kk + 1) * LPS / (BK / 32));
-        if (!(a.debug & 4)) {
+        if (!(a.debug & kCdNoMfma)) {
           const char* const wk = wbuf + (kk ? (wo ^ 64) : wo);
           const char* const xk = xbuf + (kk ? (xo ^ 64) : xo);
           bf16x8 xf[NI16];
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       if (more) issue(nb, s + NS - 1, ks * LPS / KS, (ks + 1) * LPS / KS);
-      if (!(a.debug & 4)) {
+      if (!(a.debug & kCdNoMfma)) {
         const int g = ks * 2 + khalf;
         bf16x8 wf[MI], xf[NI];
 #pragma unroll
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16
     if (++buf == NS) buf = 0;
   }
 
-  if (a.debug & 8) {
+  if (a.debug & kCdNoEpilogue) {
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -575,88 +575,210 @@ bool pick_only(const char* fmt, ...) {
 }
 }  // namespace yolo_conv
 
-int& yolo_conv_mb_debug();   // conv_mbconv.hip: YOLO_MBCONV_DEBUG / yolo_set_tuning(4, .)
+static int env_int(const char* name, int unset) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : unset;
+}
+Tuning& tuning() {   // the environment at first use, yolo_set_tuning afterwards
+  static Tuning t{env_int("YOLO_CONV_VARIANT", -1), env_int("YOLO_CONV_DEBUG", 0), env_int("YOLO_CONV_PP", 0),
+                  env_int("YOLO_RESUNIT_DEBUG", 0), env_int("YOLO_MBCONV_DEBUG", 0)};
+  return t;
+}
+
+extern "C" int yolo_set_tuning(int knob, int value) {
+  static constexpr int Tuning::* kKnobs[] = {&Tuning::variant, &Tuning::conv_debug, &Tuning::families, &Tuning::resunit, &Tuning::mbconv};
+  YOLO_REQUIRE(knob >= 0 && knob < 5, "set_tuning: unknown knob %d", knob);
+  int& slot = tuning().*kKnobs[knob];
+  const int old = slot;
+  slot = value;
+  return old;
+}
 
 namespace {
-int conv_variant_override = -1;
-int conv_debug_flags = 0;   // tuning hook (YOLO_CONV_VARIANT), see yolo_conv2d_launch
-int conv_pp_mask = 0;       // YOLO_CONV_PP / yolo_set_tuning(2, .): kernel-family selection for tests and A/B runs - 8 no halo kernel,
-                            // 16 the 20x20-tile kernels on every layer they can compute, 64 ... on none, 1024 no streaming 1x1, 2048 ... on every layer it can compute
 
-// split-K request of the current yolo_conv2d_splitk_fwd call (consumed by conv2d_launch_ex)
+// Every instance of conv_igemm_bf16_kernel in the library: X(id, BM, BN, WAVES_M, WAVES_N, BK, NS, FAST, LDS_EPI, MFMA16, DECODE, NP,
+// SPLITK).  Names: tile (pixels x couts), then what departs from 4 waves / BK 64 / 2 stages / 16x16x32 MFMA / fast gather / LDS-staged
+// epilogue: _Nw waves, _bk32, _Nst stages, _loaders (+4 loader waves), _m32 (32x32x16 MFMA), _generic (gather for any cin % 8 == 0),
+// _direct (stores from the accumulator registers: f32 output, couts or views the 16-byte epilogue cannot address).
+#define YOLO_IGEMM_INSTANCES(X)                                                         \
+  X(k64x256_8w_decode, 64, 256, 1, 8, 64, 2, true, false, false, true, 0, false)        \
+  X(k64x256_bk32_decode, 64, 256, 1, 4, 32, 2, true, false, false, true, 0, false)      \
+  X(k64x256_bk32_generic_decode, 64, 256, 1, 4, 32, 2, false, false, false, true, 0, false) \
+  X(k256x32_m32, 256, 32, 4, 1, 32, 2, true, true, false, false, 0, false)              \
+  X(k256x32_m32_direct, 256, 32, 4, 1, 32, 2, true, false, false, false, 0, false)      \
+  X(k256x32_m32_generic, 256, 32, 4, 1, 32, 2, false, true, false, false, 0, false)     \
+  X(k256x32_m32_generic_direct, 256, 32, 4, 1, 32, 2, false, false, false, false, 0, false) \
+  X(k256x64_m32, 256, 64, 4, 1, 32, 2, true, true, false, false, 0, false)              \
+  X(k256x64_m32_direct, 256, 64, 4, 1, 32, 2, true, false, false, false, 0, false)      \
+  X(k256x64_m32_generic, 256, 64, 4, 1, 32, 2, false, true, false, false, 0, false)     \
+  X(k256x64_m32_generic_direct, 256, 64, 4, 1, 32, 2, false, false, false, false, 0, false) \
+  X(k128x128_bk32_3st_m32, 128, 128, 2, 2, 32, 3, true, true, false, false, 0, false)   \
+  X(k128x128_bk32_3st_m32_direct, 128, 128, 2, 2, 32, 3, true, false, false, false, 0, false) \
+  X(k128x128_bk32_3st_m32_generic, 128, 128, 2, 2, 32, 3, false, true, false, false, 0, false) \
+  X(k128x128_bk32_3st_m32_generic_direct, 128, 128, 2, 2, 32, 3, false, false, false, false, 0, false) \
+  X(k128x128_m32, 128, 128, 2, 2, 64, 2, true, true, false, false, 0, false)            \
+  X(k128x128_m32_direct, 128, 128, 2, 2, 64, 2, true, false, false, false, 0, false)    \
+  X(k128x128_bk32_m32, 128, 128, 2, 2, 32, 2, true, true, false, false, 0, false)       \
+  X(k128x128_bk32_m32_direct, 128, 128, 2, 2, 32, 2, true, false, false, false, 0, false) \
+  X(k128x64_m32, 128, 64, 2, 2, 64, 2, true, true, false, false, 0, false)              \
+  X(k128x64_m32_direct, 128, 64, 2, 2, 64, 2, true, false, false, false, 0, false)      \
+  X(k64x128_m32, 64, 128, 2, 2, 64, 2, true, true, false, false, 0, false)              \
+  X(k64x128_m32_direct, 64, 128, 2, 2, 64, 2, true, false, false, false, 0, false)      \
+  X(k64x64_m32, 64, 64, 2, 2, 64, 2, true, true, false, false, 0, false)                \
+  X(k64x64_m32_direct, 64, 64, 2, 2, 64, 2, true, false, false, false, 0, false)        \
+  X(k256x128_8w_m32, 256, 128, 4, 2, 64, 2, true, true, false, false, 0, false)         \
+  X(k256x128_8w_m32_direct, 256, 128, 4, 2, 64, 2, true, false, false, false, 0, false) \
+  X(k256x128_8w_bk32_m32, 256, 128, 4, 2, 32, 2, true, true, false, false, 0, false)    \
+  X(k256x128_8w_bk32_m32_direct, 256, 128, 4, 2, 32, 2, true, false, false, false, 0, false) \
+  X(k256x256_8w_m32, 256, 256, 4, 2, 64, 2, true, true, false, false, 0, false)         \
+  X(k256x256_8w_m32_direct, 256, 256, 4, 2, 64, 2, true, false, false, false, 0, false) \
+  X(k64x64_4st, 64, 64, 2, 2, 64, 4, true, true, true, false, 0, false)                 \
+  X(k64x64_4st_splitk, 64, 64, 2, 2, 64, 4, true, true, true, false, 0, true)           \
+  X(k64x64, 64, 64, 2, 2, 64, 2, true, true, true, false, 0, false)                     \
+  X(k128x128, 128, 128, 2, 2, 64, 2, true, true, true, false, 0, false)                 \
+  X(k128x128_8w, 128, 128, 2, 4, 64, 2, true, true, true, false, 0, false)              \
+  X(k128x128_8w_3st, 128, 128, 2, 4, 64, 3, true, true, true, false, 0, false)          \
+  X(k128x256_8w, 128, 256, 2, 4, 64, 2, true, true, true, false, 0, false)              \
+  X(k128x256_16w_3st, 128, 256, 2, 8, 64, 3, true, true, true, false, 0, false)         \
+  X(k128x256_loaders, 128, 256, 2, 4, 64, 2, true, true, true, false, 4, false)         \
+  X(k128x256_loaders_3st, 128, 256, 2, 4, 64, 3, true, true, true, false, 4, false)     \
+  X(k128x256_loaders_3st_splitk, 128, 256, 2, 4, 64, 3, true, true, true, false, 4, true) \
+  X(k256x128_8w, 256, 128, 4, 2, 64, 2, true, true, true, false, 0, false)              \
+  X(k256x128_8w_bk32, 256, 128, 4, 2, 32, 2, true, true, true, false, 0, false)         \
+  X(k256x256_8w, 256, 256, 4, 2, 64, 2, true, true, true, false, 0, false)              \
+  X(k256x256_16w, 256, 256, 4, 4, 64, 2, true, true, true, false, 0, false)
+
+enum class IgemmId {
+#define X(id, ...) id,
+  YOLO_IGEMM_INSTANCES(X)
+#undef X
+};
+
+int launch_igemm(IgemmId id, const ConvArgs& a, hipStream_t s) {
+  switch (id) {
+#define X(id, ...) \
+  case IgemmId::id: return launch_cfg<__VA_ARGS__>(a, s);
+    YOLO_IGEMM_INSTANCES(X)
+#undef X
+  }
+  return yolo_set_error(YOLO_E_UNSUPPORTED, "conv: unknown kernel instance %d", (int)id);
+}
+
+thread_local int g_launch_cus = 256;   // compute units the coming launches may use (a CU-masked stream: yolo_set_launch_cus)
+
+// Output, residual and pre-add views that the LDS-staged epilogue (16-byte accesses, whole 32-cout slabs) can address
+bool lds_epilogue_views(const YoloConvDesc& d, bool has_res, bool has_aux) {
+  return d.out_dtype == YOLO_DT_BF16 && d.cout % 32 == 0 && d.out_c_offset % 8 == 0 && d.out_c_total % 8 == 0 &&
+         (!has_res || (d.res_c_offset % 8 == 0 && d.res_c_total % 8 == 0)) && (!has_aux || (d.aux_c_offset % 8 == 0 && d.aux_c_total % 8 == 0));
+}
+
+// Shape rules that choose_igemm and the split-K planner (yolo_conv2d_splitk_plan) share; M = n * ho * wo.
+// few pixels, few output channels, long K (MobileNetV2-tiny head: 3x3 1280 -> 64 on 13x13): 256-row tiles leave most
+// CUs idle, 64x64 tiles quadruple the workgroup count
+bool few_pixels_64_couts(const YoloConvDesc& d, long M, int n_cu) { return d.cout == 64 && d.cin % 64 == 0 && (M + 255) / 256 < n_cu / 2; }
+// 256x256 (8 waves, one block per CU) halves the operand traffic per FLOP but needs enough tiles to fill
+// the 256 CUs; otherwise 128x128 (4 waves, two blocks per CU).  Measured on MI355X, see DESIGN.md.
+bool fills_256x256(const YoloConvDesc& d, long M, int n_cu) { return d.cout % 256 == 0 && ((M + 255) / 256) * (d.cout / 256) >= n_cu * 5 / 8; }
+// 128x256 tiles (8 waves) when they cover the layer in one round of the 256 CUs: 25 % less operand traffic per
+// FLOP than 128x128 (-7 % on the 20x20 3x3 and the 40x40 1x1 layers)
+bool one_round_128x256(const YoloConvDesc& d, long M, int n_cu) { return d.cout % 256 == 0 && ((M + 127) / 128) * (d.cout / 256) <= n_cu; }
+
+// Which instance of the gather kernel a layer gets.  No side effects: the answer depends on the arguments alone.
+// head: the YOLOLayer decode runs as the epilogue.  splits > 1: a split-K launch was asked for (yolo_conv2d_splitk_fwd).
+// n_cu: compute units the launch may use.
+IgemmId choose_igemm(const YoloConvDesc& d, bool has_res, bool has_aux, bool head, int splits, int n_cu, const Tuning& t) {
+  using I = IgemmId;
+  const int dbg = t.conv_debug;
+  if (head) {   // head conv with the YOLOLayer decode as its epilogue: one 64-pixel x 256-cout tile per block
+    // 8 waves (2 blocks per CU -> 4 per SIMD) when cin allows 64-deep stages; kCdFourWaves selects the 4-wave forms
+    if (d.cin % 64 == 0 && !(dbg & kCdFourWaves)) return I::k64x256_8w_decode;
+    return d.cin % 32 == 0 ? I::k64x256_bk32_decode : I::k64x256_bk32_generic_decode;
+  }
+  const long M = (long)d.n * d.ho * d.wo;
+  const bool one_tap = d.ksize == 1 && d.cin % 8 == 0 && !(dbg & kCdOneTapGeneric);      // (kCdOneTapGeneric: the generic path for them, A/B)
+  const bool fast64 = d.cin % 64 == 0, fast32 = d.cin % 32 == 0 || one_tap;
+  const bool epi = lds_epilogue_views(d, has_res, has_aux) && !(dbg & kCdNoLdsEpilogue);
+#define EPI(id) (epi ? I::id : I::id##_direct)
+  if (d.cout <= 32) return fast32 ? EPI(k256x32_m32) : EPI(k256x32_m32_generic);
+  // few_pixels_64_couts ... and with one small workgroup per CU nothing hides the LDS-DMA latency of a two-stage ring: four stages
+  if (few_pixels_64_couts(d, M, n_cu) && epi && t.variant < 0 && !(dbg & kCdMfma32x32)) {
+    if (splits > 1) return I::k64x64_4st_splitk;
+    return dbg & kCd64x64TwoStages ? I::k64x64 : I::k64x64_4st;
+  }
+  if (d.cout <= 64) return fast32 ? EPI(k256x64_m32) : EPI(k256x64_m32_generic);
+  if (!fast64) return fast32 ? EPI(k128x128_bk32_3st_m32) : EPI(k128x128_bk32_3st_m32_generic);
+  int pick = t.variant;
+  if (t.variant < 0) {
+    pick = fills_256x256(d, M, n_cu) ? 5 : 0;
+    // ... unless 128x128 tiles (two workgroups per CU) fill their last round much better: on 128 CUs the stride-2 128 -> 256 layer
+    // is 400 tiles of 256x256 = 3.1 rounds (0.78) against 6.25 rounds of 128x128 (0.89): -8 %
+    // (measured on a 128-CU share only; on the whole chip the same round counts at 32 images favour the 256x256 tiles by 5 %)
+    if (pick == 5 && d.ksize == 3 && n_cu <= 128) {
+      const long tiles256 = ((M + 255) / 256) * (d.cout / 256), t128 = ((M + 127) / 128) * (d.cout / 128);
+      const double e256 = (double)tiles256 / (double)(((tiles256 + n_cu - 1) / n_cu) * n_cu);
+      const double e128 = (double)t128 / (double)(((t128 + 2 * n_cu - 1) / (2 * n_cu)) * 2 * n_cu);
+      if (e128 > 1.1 * e256) pick = 0;
+    }
+    // short-K 1x1 layers on big maps are latency/HBM-bound: 256x128 tiles with 32-deep stages keep
+    // 16 waves per CU resident (two 8-wave blocks), which hides the per-tile prologue/epilogue
+    if (d.ksize == 1 && d.cin <= 512 && M >= 40000) pick = 9;
+    if (pick == 0 && one_round_128x256(d, M, n_cu) && !(dbg & kCdNo128x256)) pick = 12;
+    // tiny grids (1x1 layers on the 20x20 maps): 64x64 tiles quadruple the block count so the chip fills
+    if (d.ksize == 1 && ((M + 127) / 128) * ((d.cout + 127) / 128) < n_cu) pick = 11;
+  }
+  // 16x16x32 MFMA mainloop (same LDS traffic and cycles per FLOP as 32x32x16; the chip holds a higher clock on
+  // it: +2..3 % measured on every shape).  kCdMfma32x32 falls back to 32x32x16.
+  if (epi && !(dbg & kCdMfma32x32)) {
+    switch (pick) {
+      case 5:
+        // 16 waves (64x64 each) instead of 8 (64x128): four waves per SIMD hide the LDS-DMA issue stalls of one another
+        // (-7..8 % per layer; loader waves would spill here: 128 accumulators + 3 waves per SIMD).  kCd256x256EightWaves: old form.
+        return dbg & kCd256x256EightWaves ? I::k256x256_8w : I::k256x256_16w;
+      case 3: return I::k256x128_8w;
+      case 13: return I::k256x256_16w;
+      case 12:
+        // 3x3 layers: four extra loader waves issue all LDS-DMA, the eight MFMA waves only read LDS and multiply
+        // (-7 % on the 20x20 layers; neutral on 1x1, so those keep the symmetric form).  kCdNoLoaderWaves disables it.
+        // ... and a THREE-stage ring: a K step of this tile is ~0.9 us of MFMA, less than an HBM round trip, and in the
+        // model the weights of these layers (9.4 MB each) come from HBM: 0.094 -> 0.075 ms per layer inside the network
+        // (nothing in a back-to-back micro-benchmark, where they sit in the Infinity Cache).  kCdLoadersTwoStages: two stages.
+        if (d.ksize == 3 && splits > 1) return I::k128x256_loaders_3st_splitk;
+        if (d.ksize == 3 && !(dbg & kCdNoLoaderWaves)) return dbg & kCdLoadersTwoStages ? I::k128x256_loaders : I::k128x256_loaders_3st;
+        if (d.ksize == 1) return I::k128x256_16w_3st;   // 16 waves (-7..12 % on the 40x40 1x1 layers), 3 stages
+        return I::k128x256_8w;
+      case 9: return I::k256x128_8w_bk32;   // (a third stage costs a resident block: slower)
+      case 11:
+        // inside the network (weights from HBM) an 8-wave 128x128 tile with a three-stage ring edges out the 64x64
+        // tiles that win a back-to-back micro-benchmark; layers with fewer than 64 such tiles keep the small ones
+        if (((M + 127) / 128) * ((d.cout + 127) / 128) >= 64 && !(dbg & kCdTinyGrid64x64)) return I::k128x128_8w_3st;
+        return I::k64x64;
+      default:
+        return dbg & kCdFourWaves ? I::k128x128 : I::k128x128_8w;   // 8 waves of 64x32: -13 % on the stride-2 64->128 layer
+    }
+  }
+  switch (pick) {
+    case 3: return EPI(k256x128_8w_m32);
+    case 7: return EPI(k128x128_bk32_m32);
+    case 8: return EPI(k128x64_m32);
+    case 10: return EPI(k64x128_m32);
+    case 11: return EPI(k64x64_m32);
+    case 9: return EPI(k256x128_8w_bk32_m32);
+    case 5: return EPI(k256x256_8w_m32);
+    default: return EPI(k128x128_m32);
+  }
+#undef EPI
+}
+
+// split-K request of a yolo_conv2d_splitk_fwd call
 struct SplitK {
   int splits = 1;
   float* ws = nullptr;
   int* cnt = nullptr;
 };
-thread_local SplitK g_splitk;
-thread_local int g_launch_cus = 256;   // compute units the coming launches may use (a CU-masked stream: yolo_set_launch_cus)
 
-// The two shapes split-K serves (few pixels, long K, so few tiles that most CUs idle): tiles and K steps of the tile
-// configuration the dispatch below picks, or 0 tiles when the layer is not one of them.
-void splitk_shape(const YoloConvDesc& d, bool has_res_or_aux_views_ok, long* tiles, int* steps) {
-  *tiles = 0;
-  *steps = 0;
-  const long M = (long)d.n * d.ho * d.wo;
-  const bool epi = d.out_dtype == YOLO_DT_BF16 && d.cout % 32 == 0 && d.out_c_offset % 8 == 0 && d.out_c_total % 8 == 0 && has_res_or_aux_views_ok;
-  if (!epi || d.cin % 64 != 0 || d.upsample2x || (long)d.h * d.w >= 80 * 80) return;
-  if (d.cout == 64 && (M + 255) / 256 < 128) {                       // 64x64 tiles, BK 64
-    *tiles = (M + 63) / 64;
-    *steps = d.ksize * d.ksize * d.cin / 64;
-  } else if (d.ksize == 3 && d.stride == 1 && d.cout % 256 == 0 && ((M + 255) / 256) * (d.cout / 256) < 160 &&
-             ((M + 127) / 128) * (d.cout / 256) <= 256) {            // 128x256 loader-wave tiles, BK 64
-    *tiles = ((M + 127) / 128) * (d.cout / 256);
-    *steps = 9 * d.cin / 64;
-  }
-}
-
-}  // namespace
-
-static int conv2d_launch_ex(const void* x, const void* w, const float* bias, const void* res, void* y, void* y_aux,
-                            const YoloConvDesc* dp, const HeadDecodeArgs* hd, hipStream_t s);
-
-static bool read_conv_env() {
-  static const bool done = [] {
-    if (const char* e = getenv("YOLO_CONV_VARIANT")) conv_variant_override = atoi(e);
-    if (const char* e = getenv("YOLO_CONV_DEBUG")) conv_debug_flags = atoi(e);
-    if (const char* e = getenv("YOLO_CONV_PP")) conv_pp_mask = atoi(e);
-    return true;
-  }();
-  return done;
-}
-
-namespace yolo_conv {
-int launch_cus() { return g_launch_cus; }
-}  // namespace yolo_conv
-
-// The tile rules below size grids against the compute units a launch can use: 256, or what the CU mask of the stream leaves
-// (engine.StreamedPlan gives each sub-batch pipeline half of every XCD).  Thread-local; returns the previous value.
-extern "C" int yolo_set_launch_cus(int n_cu) {
-  YOLO_REQUIRE(n_cu >= 8 && n_cu <= 1024, "set_launch_cus: %d out of range", n_cu);
-  const int old = g_launch_cus;
-  g_launch_cus = n_cu;
-  return old;
-}
-
-extern "C" int yolo_set_tuning(int knob, int value) {
-  read_conv_env();
-  int* const slot = knob == 0 ? &conv_variant_override : knob == 1 ? &conv_debug_flags : knob == 2 ? &conv_pp_mask : knob == 3 ? &resunit_debug()
-                    : knob == 4 ? &yolo_conv_mb_debug() : nullptr;
-  YOLO_REQUIRE(slot, "set_tuning: unknown knob %d", knob);
-  const int old = *slot;
-  *slot = value;
-  return old;
-}
-
-int yolo_conv2d_launch(const void* x, const void* w, const float* bias, const void* res, void* y, void* y_aux,
-                       const YoloConvDesc* dp, hipStream_t s) {
-  return conv2d_launch_ex(x, w, bias, res, y, y_aux, dp, nullptr, s);
-}
-
-static int conv2d_launch_ex(const void* x, const void* w, const float* bias, const void* res, void* y, void* y_aux,
-                            const YoloConvDesc* dp, const HeadDecodeArgs* hd, hipStream_t s) {
+int conv2d_launch_ex(const void* x, const void* w, const float* bias, const void* res, void* y, void* y_aux, const YoloConvDesc* dp,
+                     const HeadDecodeArgs* hd, const SplitK& sk, hipStream_t s) {
   YOLO_REQUIRE(x && w && bias && (y || hd) && dp, "conv: null pointer");
-  read_conv_env();
   const YoloConvDesc& d = *dp;
   YOLO_REQUIRE(d.ksize == 1 || d.ksize == 3, "conv: ksize %d unsupported (1 or 3)", d.ksize);
   YOLO_REQUIRE(d.stride == 1 || d.stride == 2, "conv: stride %d unsupported", d.stride);
@@ -676,143 +798,84 @@ static int conv2d_launch_ex(const void* x, const void* w, const float* bias, con
   const bool std_out = d.ho == ho_std && d.wo == wo_std;
   if (res) YOLO_REQUIRE(d.res_c_total % 4 == 0 && d.res_c_offset % 4 == 0 && !d.upsample2x, "conv: bad residual view");
   if (y_aux) YOLO_REQUIRE(d.aux_c_total % 4 == 0 && d.aux_c_offset % 4 == 0, "conv: bad aux view");
-  const size_t x_bytes = (size_t)d.n * d.h * d.w * d.in_c_total * 2;
-  const size_t w_bytes = (size_t)d.cout_pad * d.kpad * 2;
-  YOLO_REQUIRE(x_bytes < kOobOffset && w_bytes < kOobOffset, "conv: tensor larger than 3.75 GiB not supported");
+  YOLO_REQUIRE(conv_x_bytes(d) < kOobOffset && conv_w_bytes(d) < kOobOffset, "conv: tensor larger than 3.75 GiB not supported");
   const long M = (long)d.n * d.ho * d.wo;
   YOLO_REQUIRE(M > 0 && M < 0x7fffffffL / 4, "conv: M out of range");
 
-  ConvArgs a;
-  a.x = (const bf16_t*)x;
-  a.w = (const bf16_t*)w;
-  a.bias = bias;
-  a.res = (const bf16_t*)res;
-  a.y = y;
-  a.aux = (bf16_t*)y_aux;
-  a.d = d;
-  a.M = (int)M;
-  a.n_tiles = 0;
-  a.steps = 0;
-  a.x_bytes = (uint32_t)x_bytes;
-  a.w_bytes = (uint32_t)w_bytes;
-  a.debug = conv_debug_flags;
-  a.splits = g_splitk.splits;
-  a.ws = g_splitk.ws;
-  a.cnt = g_splitk.cnt;
+  const Tuning& t = tuning();
+  ConvArgs a = make_conv_args(x, w, bias, res, y, y_aux, d);
+  a.debug = t.conv_debug;
+  a.splits = sk.splits;
+  a.ws = sk.ws;
+  a.cnt = sk.cnt;
   YOLO_SET_STAMPS(a);
-  if (hd) {   // head conv with the YOLOLayer decode as its epilogue: one 64-pixel x 256-cout tile per block
-    a.hd = *hd;
-    // 8 waves (2 blocks per CU -> 4 per SIMD) when cin allows 64-deep stages; bit 8192 selects the 4-wave forms
-    if (d.cin % 64 == 0 && !(conv_debug_flags & 8192)) return launch_cfg<64, 256, 1, 8, 64, 2, true, false, false, true>(a, s);
-    return d.cin % 32 == 0 ? launch_cfg<64, 256, 1, 4, 32, 2, true, false, false, true>(a, s)
-                           : launch_cfg<64, 256, 1, 4, 32, 2, false, false, false, true>(a, s);
-  }
-  const int variant = conv_variant_override >= 0 ? conv_variant_override : 0;
-  const bool one_tap = d.ksize == 1 && d.cin % 8 == 0 && !(conv_debug_flags & 268435456);      // (bit 268435456: the generic path for them, A/B)
-  const bool fast64 = d.cin % 64 == 0, fast32 = d.cin % 32 == 0 || one_tap;
-  const bool epi = d.out_dtype == YOLO_DT_BF16 && d.cout % 32 == 0 && d.out_c_offset % 8 == 0 && d.out_c_total % 8 == 0 &&
-                   (!res || (d.res_c_offset % 8 == 0 && d.res_c_total % 8 == 0)) &&
-                   (!y_aux || (d.aux_c_offset % 8 == 0 && d.aux_c_total % 8 == 0)) && !(conv_debug_flags & 16);
+  if (hd) a.hd = *hd;
+  // the other kernel families, each on the layers it takes (1 = not this one); never with a forced variant, a head or, the first
+  // two, a split-K request
+  const bool others = !hd && t.variant < 0 && std_out && lds_epilogue_views(d, res != nullptr, y_aux != nullptr) && !(t.conv_debug & kCdNoLdsEpilogue);
   // 3x3 layers whose maps 20x20 tiles cover and fill the chip with (conv3x3_t20.hip: stride 1 and, round 3, stride 2).
-  // YOLO_CONV_PP bit 16: every layer the kernels can compute, bit 64: never.
-  if (epi && std_out && conv_variant_override < 0 && !(conv_pp_mask & 64) && a.splits <= 1) {
-    const int rc = launch_t20_3x3(a, conv_pp_mask & 16 ? 1 : 0, s);
+  // kFamT20Always: every layer the kernels can compute, kFamT20Never: never.
+  if (others && !(t.families & kFamT20Never) && a.splits <= 1) {
+    const int rc = launch_t20_3x3(a, t.families & kFamT20Always ? 1 : 0, s);
     if (rc != 1) return rc;
   }
-  // short-K 1x1 layers on the large maps: weight-stationary streaming kernel (conv1x1_stream.hip).  YOLO_CONV_PP bit 1024: never,
-  // bit 2048: every layer it can compute.
-  if (epi && std_out && d.ksize == 1 && conv_variant_override < 0 && !(conv_pp_mask & 1024) && a.splits <= 1) {
-    const int rc = launch_stream1x1(a, conv_pp_mask & 2048 ? 1 : 0, s);
+  // short-K 1x1 layers on the large maps: weight-stationary streaming kernel (conv1x1_stream.hip).  kFamStreamNever: never,
+  // kFamStreamAlways: every layer it can compute.
+  if (others && d.ksize == 1 && !(t.families & kFamStreamNever) && a.splits <= 1) {
+    const int rc = launch_stream1x1(a, t.families & kFamStreamAlways ? 1 : 0, s);
     if (rc != 1) return rc;
   }
-  if (epi && std_out && !(conv_debug_flags & 32) && conv_variant_override < 0 && !(conv_pp_mask & 8)) {   // large 3x3/s1 maps: halo-staged kernel
-    a.n_tiles = 0;
+  if (others && !(t.conv_debug & kCdNoHalo) && !(t.families & kFamNoHalo)) {   // large 3x3/s1 maps: halo-staged kernel
     const int rc = launch_halo3x3(a, s);
     if (rc != 1) return rc;
   }
-#define YOLO_CFG(BM, BN, WM, WN, BK, NS, FASTV)                                                           \
-  (epi ? launch_cfg<BM, BN, WM, WN, BK, NS, FASTV, true>(a, s) : launch_cfg<BM, BN, WM, WN, BK, NS, FASTV, false>(a, s))
-  if (d.cout <= 32) return fast32 ? YOLO_CFG(256, 32, 4, 1, 32, 2, true) : YOLO_CFG(256, 32, 4, 1, 32, 2, false);
-  // few pixels, few output channels, long K (MobileNetV2-tiny head: 3x3 1280 -> 64 on 13x13): 256-row tiles leave most
-  // CUs idle, 64x64 tiles quadruple the workgroup count
-  // ... and with one small workgroup per CU nothing hides the LDS-DMA latency of a two-stage ring: four stages
-  if (d.cout == 64 && fast64 && epi && (M + 255) / 256 < g_launch_cus / 2 && conv_variant_override < 0 && !(conv_debug_flags & 2048)) {
-    if (a.splits > 1) return launch_cfg<64, 64, 2, 2, 64, 4, true, true, true, false, 0, true>(a, s);
-    if (conv_debug_flags & 4194304) return launch_cfg<64, 64, 2, 2, 64, 2, true, true, true>(a, s);
-    return launch_cfg<64, 64, 2, 2, 64, 4, true, true, true>(a, s);
+  return launch_igemm(choose_igemm(d, res != nullptr, y_aux != nullptr, hd != nullptr, a.splits, g_launch_cus, t), a, s);
+}
+
+// The descriptor a head op hands to the shared checks: its output view is unused, so give them a consistent one
+YoloConvDesc head_desc(const YoloConvDesc& d) {
+  YoloConvDesc dd = d;
+  dd.out_dtype = YOLO_DT_F32;
+  dd.out_c_total = (d.cout + 3) & ~3;
+  dd.out_c_offset = 0;
+  return dd;
+}
+
+HeadDecodeArgs make_head_args(float* io, float* p, int na, int nc, int io_rows_total, int io_row_offset, float stride_px,
+                              const float* anchors_px) {
+  HeadDecodeArgs h;
+  h.io = io;
+  h.p = p;
+  h.na = na;
+  h.no = nc + 5;
+  h.io_rows_total = io_rows_total;
+  h.io_row_offset = io_row_offset;
+  h.stride = stride_px;
+  for (int i = 0; i < na; ++i) {
+    h.anchor_w[i] = anchors_px[2 * i] / stride_px;
+    h.anchor_h[i] = anchors_px[2 * i + 1] / stride_px;
   }
-  if (d.cout <= 64) return fast32 ? YOLO_CFG(256, 64, 4, 1, 32, 2, true) : YOLO_CFG(256, 64, 4, 1, 32, 2, false);
-  if (!fast64) return fast32 ? YOLO_CFG(128, 128, 2, 2, 32, 3, true) : YOLO_CFG(128, 128, 2, 2, 32, 3, false);
-  // 256x256 (8 waves, one block per CU) halves the operand traffic per FLOP but needs enough tiles to fill
-  // the 256 CUs; otherwise 128x128 (4 waves, two blocks per CU).  Measured on MI355X, see DESIGN.md.
-  int pick = variant;
-  if (conv_variant_override < 0) {
-    const int n_cu = g_launch_cus;
-    const long tiles256 = ((M + 255) / 256) * (d.cout / 256);
-    pick = (d.cout % 256 == 0 && tiles256 >= n_cu * 5 / 8) ? 5 : 0;
-    // ... unless 128x128 tiles (two workgroups per CU) fill their last round much better: on 128 CUs the stride-2 128 -> 256 layer
-    // is 400 tiles of 256x256 = 3.1 rounds (0.78) against 6.25 rounds of 128x128 (0.89): -8 %
-    // (measured on a 128-CU share only; on the whole chip the same round counts at 32 images favour the 256x256 tiles by 5 %)
-    if (pick == 5 && d.ksize == 3 && n_cu <= 128) {
-      const long t128 = ((M + 127) / 128) * (d.cout / 128);
-      const double e256 = (double)tiles256 / (double)(((tiles256 + n_cu - 1) / n_cu) * n_cu);
-      const double e128 = (double)t128 / (double)(((t128 + 2 * n_cu - 1) / (2 * n_cu)) * 2 * n_cu);
-      if (e128 > 1.1 * e256) pick = 0;
-    }
-    // short-K 1x1 layers on big maps are latency/HBM-bound: 256x128 tiles with 32-deep stages keep
-    // 16 waves per CU resident (two 8-wave blocks), which hides the per-tile prologue/epilogue
-    if (d.ksize == 1 && d.cin <= 512 && M >= 40000) pick = 9;
-    // 128x256 tiles (8 waves) when they cover the layer in one round of the 256 CUs: 25 % less operand traffic per
-    // FLOP than 128x128 (-7 % on the 20x20 3x3 and the 40x40 1x1 layers)
-    if (pick == 0 && d.cout % 256 == 0 && ((M + 127) / 128) * (d.cout / 256) <= n_cu && !(conv_debug_flags & 128)) pick = 12;
-    // tiny grids (1x1 layers on the 20x20 maps): 64x64 tiles quadruple the block count so the chip fills
-    if (d.ksize == 1 && ((M + 127) / 128) * ((d.cout + 127) / 128) < n_cu) pick = 11;
-  }
-  // 16x16x32 MFMA mainloop (same LDS traffic and cycles per FLOP as 32x32x16; the chip holds a higher clock on
-  // it: +2..3 % measured on every shape).  YOLO_CONV_DEBUG bit 2048 falls back to 32x32x16.
-  if (epi && !(conv_debug_flags & 2048)) {
-    switch (pick) {
-      case 5:
-        // 16 waves (64x64 each) instead of 8 (64x128): four waves per SIMD hide the LDS-DMA issue stalls of one another
-        // (-7..8 % per layer; loader waves would spill here: 128 accumulators + 3 waves per SIMD).  Bit 512: old form.
-        if (conv_debug_flags & 512) return launch_cfg<256, 256, 4, 2, 64, 2, true, true, true>(a, s);
-        return launch_cfg<256, 256, 4, 4, 64, 2, true, true, true>(a, s);
-      case 3: return launch_cfg<256, 128, 4, 2, 64, 2, true, true, true>(a, s);
-      case 13: return launch_cfg<256, 256, 4, 4, 64, 2, true, true, true>(a, s);
-      case 12:
-        // 3x3 layers: four extra loader waves issue all LDS-DMA, the eight MFMA waves only read LDS and multiply
-        // (-7 % on the 20x20 layers; neutral on 1x1, so those keep the symmetric form).  Bit 256 disables it.
-        // ... and a THREE-stage ring: a K step of this tile is ~0.9 us of MFMA, less than an HBM round trip, and in the
-        // model the weights of these layers (9.4 MB each) come from HBM: 0.094 -> 0.075 ms per layer inside the network
-        // (nothing in a back-to-back micro-benchmark, where they sit in the Infinity Cache).  Bit 16384: two stages.
-        if (d.ksize == 3 && a.splits > 1) return launch_cfg<128, 256, 2, 4, 64, 3, true, true, true, false, 4, true>(a, s);
-        if (d.ksize == 3 && !(conv_debug_flags & (256 | 16384))) return launch_cfg<128, 256, 2, 4, 64, 3, true, true, true, false, 4>(a, s);
-        if (d.ksize == 3 && !(conv_debug_flags & 256)) return launch_cfg<128, 256, 2, 4, 64, 2, true, true, true, false, 4>(a, s);
-        if (d.ksize == 1) return launch_cfg<128, 256, 2, 8, 64, 3, true, true, true>(a, s);   // 16 waves (-7..12 % on the 40x40 1x1 layers), 3 stages
-        return launch_cfg<128, 256, 2, 4, 64, 2, true, true, true>(a, s);
-      case 9: return launch_cfg<256, 128, 4, 2, 32, 2, true, true, true>(a, s);   // (a third stage costs a resident block: slower)
-      case 11:
-        // inside the network (weights from HBM) an 8-wave 128x128 tile with a three-stage ring edges out the 64x64
-        // tiles that win a back-to-back micro-benchmark; layers with fewer than 64 such tiles keep the small ones
-        if (((M + 127) / 128) * ((d.cout + 127) / 128) >= 64 && !(conv_debug_flags & 32768))
-          return launch_cfg<128, 128, 2, 4, 64, 3, true, true, true>(a, s);
-        return launch_cfg<64, 64, 2, 2, 64, 2, true, true, true>(a, s);
-      default:
-        if (conv_debug_flags & 8192) return launch_cfg<128, 128, 2, 2, 64, 2, true, true, true>(a, s);
-        return launch_cfg<128, 128, 2, 4, 64, 2, true, true, true>(a, s);   // 8 waves of 64x32: -13 % on the stride-2 64->128 layer
-    }
-  }
-  switch (pick) {
-    case 3: return YOLO_CFG(256, 128, 4, 2, 64, 2, true);
-    case 7: return YOLO_CFG(128, 128, 2, 2, 32, 2, true);
-    case 8: return YOLO_CFG(128, 64, 2, 2, 64, 2, true);
-    case 10: return YOLO_CFG(64, 128, 2, 2, 64, 2, true);
-    case 11: return YOLO_CFG(64, 64, 2, 2, 64, 2, true);
-    case 9: return YOLO_CFG(256, 128, 4, 2, 32, 2, true);
-    case 5: return YOLO_CFG(256, 256, 4, 2, 64, 2, true);
-    default: return YOLO_CFG(128, 128, 2, 2, 64, 2, true);
-  }
-#undef YOLO_CFG
+  return h;
+}
+
+}  // namespace
+
+namespace yolo_conv {
+int launch_cus() { return g_launch_cus; }
+}  // namespace yolo_conv
+
+// The tile rules size grids against the compute units a launch can use: 256, or what the CU mask of the stream leaves
+// (engine.StreamedPlan gives each sub-batch pipeline half of every XCD).  Thread-local; returns the previous value.
+extern "C" int yolo_set_launch_cus(int n_cu) {
+  YOLO_REQUIRE(n_cu >= 8 && n_cu <= 1024, "set_launch_cus: %d out of range", n_cu);
+  const int old = g_launch_cus;
+  g_launch_cus = n_cu;
+  return old;
+}
+
+int yolo_conv2d_launch(const void* x, const void* w, const float* bias, const void* res, void* y, void* y_aux,
+                       const YoloConvDesc* dp, hipStream_t s) {
+  return conv2d_launch_ex(x, w, bias, res, y, y_aux, dp, nullptr, SplitK(), s);
 }
 
 // First layer straight from the caller's float32 NCHW batch (fuses yolo_pack_input_nchw_f32 + conv), optionally with
@@ -826,23 +889,9 @@ static int conv1_nchw(const float* x_nchw, int cin_real, const void* w_packed, c
   YOLO_REQUIRE((d.stride == 1 && d.ho == d.h && d.wo == d.w) ||
                    (d.stride == 2 && !pool && d.ho == (d.h - 1) / 2 + 1 && d.wo == (d.w - 1) / 2 + 1),
                "conv1: 3x3 / pad 1 at stride 1, or at stride 2 (cout 32, no pool) only");
-  ConvArgs a;
-  a.x = nullptr;
-  a.w = (const bf16_t*)w_packed;
-  a.bias = bias;
-  a.res = nullptr;
-  a.y = y;
-  a.aux = nullptr;
-  a.d = d;
-  a.M = d.n * d.ho * d.wo;
+  ConvArgs a = make_conv_args(nullptr, w_packed, bias, nullptr, y, nullptr, d);
   a.n_tiles = 1;
-  a.steps = 0;
-  a.x_bytes = 0;
-  a.w_bytes = 0;
-  a.debug = 0;
-  a.splits = 1;
-  a.ws = nullptr;
-  a.cnt = nullptr;
+  a.x_bytes = a.w_bytes = 0;   // x is the NCHW batch, and the kernels read both through plain pointers
   YOLO_SET_STAMPS(a);
   const int rc = d.stride == 2 ? launch_conv1_s2_nchw(a, x_nchw, cin_real, (hipStream_t)s)
                                : launch_conv1_nchw(a, x_nchw, cin_real, pool, (hipStream_t)s);
@@ -879,7 +928,9 @@ extern "C" int yolo_conv2d_fwd(const void* x, const void* w_packed, const float*
   return yolo_conv2d_launch(x, w_packed, bias, residual, y, y_preadd, d, (hipStream_t)s);
 }
 
-// Split-K form of yolo_conv2d_fwd for layers with few pixels and a long K (see splitk_shape).
+// Split-K form of yolo_conv2d_fwd for the two shapes it serves: few pixels and a long K, so few tiles that most CUs idle.  The
+// plan sizes its grids against a FIXED 256 compute units, not the stream's share (yolo_set_launch_cus): on a CU-masked stream
+// choose_igemm can take a layer planned here to an instance without split-K.
 extern "C" int yolo_conv2d_splitk_plan(const YoloConvDesc* dp, int has_residual, int has_preadd, int* splits, size_t* ws_bytes,
                                        int* n_counters) {
   YOLO_REQUIRE(dp && splits && ws_bytes && n_counters, "splitk_plan: null pointer");
@@ -887,11 +938,14 @@ extern "C" int yolo_conv2d_splitk_plan(const YoloConvDesc* dp, int has_residual,
   *splits = 1;
   *ws_bytes = 0;
   *n_counters = 0;
-  const bool views_ok = (!has_residual || (d.res_c_offset % 8 == 0 && d.res_c_total % 8 == 0)) &&
-                        (!has_preadd || (d.aux_c_offset % 8 == 0 && d.aux_c_total % 8 == 0));
-  long tiles;
-  int steps;
-  splitk_shape(d, views_ok, &tiles, &steps);
+  constexpr int kPlanCus = 256;
+  const long M = (long)d.n * d.ho * d.wo;
+  if (!lds_epilogue_views(d, has_residual, has_preadd) || d.cin % 64 != 0 || d.upsample2x || (long)d.h * d.w >= 80 * 80) return 0;
+  long tiles;   // of the instance choose_igemm picks
+  if (few_pixels_64_couts(d, M, kPlanCus)) tiles = (M + 63) / 64;
+  else if (d.ksize == 3 && d.stride == 1 && !fills_256x256(d, M, kPlanCus) && one_round_128x256(d, M, kPlanCus)) tiles = ((M + 127) / 128) * (d.cout / 256);
+  else return 0;
+  const int steps = d.ksize * d.ksize * d.cin / 64;   // both instances: BK 64
   if (tiles == 0 || tiles >= 200) return 0;
   int best = 1;
   for (int sp = 2; sp <= 8; ++sp)
@@ -915,12 +969,7 @@ extern "C" int yolo_conv2d_splitk_fwd(const void* x, const void* w_packed, const
   if (rc0) return rc0;
   YOLO_REQUIRE(want >= 2, "splitk: this layer does not take a split-K launch");
   YOLO_REQUIRE((size_t)splits * d->n * d->ho * d->wo * d->cout * sizeof(float) <= ws_bytes, "splitk: workspace too small");
-  g_splitk.splits = splits;
-  g_splitk.ws = (float*)workspace;
-  g_splitk.cnt = counters;
-  const int rc = yolo_conv2d_launch(x, w_packed, bias, residual, y, y_preadd, d, (hipStream_t)s);
-  g_splitk = SplitK();
-  return rc;
+  return conv2d_launch_ex(x, w_packed, bias, residual, y, y_preadd, d, nullptr, SplitK{splits, (float*)workspace, counters}, (hipStream_t)s);
 }
 
 // Head conv + decode in one launch (see the DECODE epilogue of conv_igemm_bf16_kernel).
@@ -938,24 +987,9 @@ extern "C" int yolo_head_decode_fwd(const void* x, const void* w_packed, const f
   YOLO_REQUIRE(d.stride == 1 && !d.upsample2x, "head_decode: stride-1 head convs only");
   YOLO_REQUIRE(io_row_offset >= 0 && io_row_offset + na * d.ho * d.wo <= io_rows_total, "head_decode: rows out of range");
   YOLO_REQUIRE(stride_px > 0.f, "head_decode: bad stride");
-  HeadDecodeArgs h;
-  h.io = io;
-  h.p = p;
-  h.na = na;
-  h.no = nc + 5;
-  h.io_rows_total = io_rows_total;
-  h.io_row_offset = io_row_offset;
-  h.stride = stride_px;
-  for (int i = 0; i < 4; ++i) {
-    h.anchor_w[i] = i < na ? anchors_px[2 * i] / stride_px : 0.f;
-    h.anchor_h[i] = i < na ? anchors_px[2 * i + 1] / stride_px : 0.f;
-  }
-  h.rec = nullptr, h.row_keys = nullptr, h.conf_thres = 0.f, h.min_wh = 0.f;
-  YoloConvDesc dd = d;              // the output view is unused: give the shared checks a consistent one
-  dd.out_dtype = YOLO_DT_F32;
-  dd.out_c_total = (d.cout + 3) & ~3;
-  dd.out_c_offset = 0;
-  return conv2d_launch_ex(x, w_packed, bias, nullptr, nullptr, nullptr, &dd, &h, (hipStream_t)s);
+  const HeadDecodeArgs h = make_head_args(io, p, na, nc, io_rows_total, io_row_offset, stride_px, anchors_px);
+  const YoloConvDesc dd = head_desc(d);
+  return conv2d_launch_ex(x, w_packed, bias, nullptr, nullptr, nullptr, &dd, &h, SplitK(), (hipStream_t)s);
 }
 
 // Which kernel instance and grid a head op would launch (no launch, no GPU): yolo_conv2d_pick for yolo_head_decode_fwd (filter == 0,
@@ -965,25 +999,14 @@ extern "C" int yolo_head_decode_pick(const YoloConvDesc* dp, int na, int nc, int
   YOLO_REQUIRE(yolo_head_decode_supported(dp->cout, na, nc), "head_decode_pick: cout %d != na*(5+nc)", dp->cout);
   out[0] = 0;
   static float dummy[16] = {0};
-  HeadDecodeArgs h;
-  h.io = filter ? nullptr : dummy;
-  h.p = nullptr;
-  h.na = na;
-  h.no = nc + 5;
-  h.io_rows_total = na * dp->ho * dp->wo;
-  h.io_row_offset = 0;
-  h.stride = 1.f;
-  for (int i = 0; i < 4; ++i) h.anchor_w[i] = h.anchor_h[i] = 1.f;
+  static const float ones[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+  HeadDecodeArgs h = make_head_args(filter ? nullptr : dummy, nullptr, na, nc, na * dp->ho * dp->wo, 0, 1.f, ones);
   h.rec = filter ? dummy : nullptr;
   h.row_keys = filter ? (unsigned long long*)dummy : nullptr;
-  h.conf_thres = 0.f, h.min_wh = 0.f;
-  YoloConvDesc dd = *dp;
-  dd.out_dtype = YOLO_DT_F32;
-  dd.out_c_total = (dp->cout + 3) & ~3;
-  dd.out_c_offset = 0;
+  const YoloConvDesc dd = head_desc(*dp);
   yolo_conv::g_pick = out;
   yolo_conv::g_pick_len = out_len;
-  const int rc = conv2d_launch_ex(dummy, dummy, dummy, nullptr, nullptr, nullptr, &dd, &h, nullptr);
+  const int rc = conv2d_launch_ex(dummy, dummy, dummy, nullptr, nullptr, nullptr, &dd, &h, SplitK(), nullptr);
   yolo_conv::g_pick = nullptr;
   return rc;
 }
@@ -1006,27 +1029,13 @@ extern "C" int yolo_head_decode_filter_fwd(const void* x, const void* w_packed, 
                           yolo_nms_compact_workspace_bytes(d.n, io_rows_total, nc));
   YOLO_REQUIRE((size_t)d.n * io_rows_total * yolo_nms::kRecFloats * 4 < kOobOffset, "head_decode_filter: batch too large for 32-bit record offsets");
   const yolo_nms::Workspace w = yolo_nms::carve(workspace, d.n, io_rows_total, nc, true);
-  HeadDecodeArgs h;
-  h.io = nullptr;
-  h.p = p;
-  h.na = na;
-  h.no = nc + 5;
-  h.io_rows_total = io_rows_total;
-  h.io_row_offset = io_row_offset;
-  h.stride = stride_px;
-  for (int i = 0; i < 4; ++i) {
-    h.anchor_w[i] = i < na ? anchors_px[2 * i] / stride_px : 0.f;
-    h.anchor_h[i] = i < na ? anchors_px[2 * i + 1] / stride_px : 0.f;
-  }
+  HeadDecodeArgs h = make_head_args(nullptr, p, na, nc, io_rows_total, io_row_offset, stride_px, anchors_px);
   h.rec = w.rec;
   h.row_keys = w.row_keys;
   h.conf_thres = conf_thres;
   h.min_wh = min_wh;
-  YoloConvDesc dd = d;
-  dd.out_dtype = YOLO_DT_F32;
-  dd.out_c_total = (d.cout + 3) & ~3;
-  dd.out_c_offset = 0;
-  return conv2d_launch_ex(x, w_packed, bias, nullptr, nullptr, nullptr, &dd, &h, (hipStream_t)s);
+  const YoloConvDesc dd = head_desc(d);
+  return conv2d_launch_ex(x, w_packed, bias, nullptr, nullptr, nullptr, &dd, &h, SplitK(), (hipStream_t)s);
 }
 
 // Host-side weight packer: OIHW f32 -> [cout_pad][kpad] bf16, k = (kh*ks+kw)*cin + c, zero padded.

@@ -33,8 +33,7 @@ struct MbArgs {
   int n, h, w, ho, wo, cin, in_ct, in_co, ce, cout, cop, out_ct, out_co, has_res;
   int tiles_x, tiles_y, n_tiles, dstride;
   int th;               // strip form: output rows per band
-  int debug;            // YOLO_MBCONV_DEBUG (timing only, results wrong): 2 no expand stage, 4 no depthwise stage, 8 no projection stage, 16 no x loads;
-                        // form selection: 64 never the strip form (round 5), 1 / 32 tile-shape knobs of the tile form
+  int debug;            // Tuning::mbconv (YOLO_MBCONV_DEBUG, the kMb* bits of tuning.h)
 #ifdef YOLO_STAMPS
   unsigned long long* stamps;   // diagnostic build only (tools/mbstrip_timeline.py)
   int stamp_lds;                // byte offset of the 768-byte stamp area in LDS
@@ -208,7 +207,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void mb
   if (cur.tile < a.n_tiles) {
     stash();
     advance(nxt);
-    if (nxt.tile < a.n_tiles && !(a.debug & 16)) fetch(nxt);
+    if (nxt.tile < a.n_tiles && !(a.debug & kMbNoXLoads)) fetch(nxt);
     lds_barrier();
   }
   for (; cur.tile < a.n_tiles; advance(cur)) {
@@ -229,7 +228,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void mb
       }
     }
     // ---- B: E = relu6(X We^T + be), 0 outside the image
-    if (EXPAND && !(a.debug & 2)) {
+    if (EXPAND && !(a.debug & kMbNoExpand)) {
       // A wave takes a contiguous run of 16x16 tiles in CHANNEL-tile-major order: the weight fragment and the bias (the accumulator's
       // start value) stay in registers over the run's pixel-row tiles, so a tile costs one 1 KB LDS read (its pixel fragment) instead
       // of three (round 4: the phase was bound by LDS traffic and by a read -> MFMA -> pack -> write chain per tile with a scalar
@@ -267,10 +266,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void mb
         }
       }
     }
-    if (EXPAND) { if (a.debug & 256) __syncthreads(); else lds_barrier(); }
+    if (EXPAND) { if (a.debug & kMbFullBarriers) __syncthreads(); else lds_barrier(); }
     // ---- C: D = relu6(dw3x3(E) + bd)
     if constexpr (S == 1 && NT >= 512) {
-      if (dw_on && !(a.debug & 4)) {
+      if (dw_on && !(a.debug & kMbNoDepthwise)) {
       // Stride 1 (round 5, late): a task is a run of FOUR adjacent output pixels of a row x 4 channels - its 3 x 6 window of E is read
       // once (18 eight-byte reads, the same as the two-pixel iteration below) and feeds 16 outputs instead of 8: half the LDS bytes and
       // 13 instead of 22 instructions per output.  The phase is bound by LDS reads (the float32-E experiment: half the instructions,
@@ -319,7 +318,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void mb
         }
       }
       }
-    } else if (dw_on && !(a.debug & 4)) {
+    } else if (dw_on && !(a.debug & kMbNoDepthwise)) {
       for (int p = grp; p < P; p += 2 * groups) {       // two pixels per iteration
         const bool two = p + groups < P;
         const int pp[2] = {p, two ? p + groups : p};
@@ -351,15 +350,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void mb
         }
       }
     }
-    if (a.debug & 256) __syncthreads(); else lds_barrier();
+    if (a.debug & kMbFullBarriers) __syncthreads(); else lds_barrier();
     // ---- the NEXT tile's x halo (fetched during this tile's first phases) -> LDS; the loads of the tile after it go out
     if (cur.tile + G < a.n_tiles) {
       stash();
       advance(nxt);
-      if (nxt.tile < a.n_tiles && !(a.debug & 16)) fetch(nxt);
+      if (nxt.tile < a.n_tiles && !(a.debug & kMbNoXLoads)) fetch(nxt);
     }
     // ---- D: y = D Wp^T + bp (+ x)
-    if (!(a.debug & 8)) {
+    if (!(a.debug & kMbNoProject)) {
       const int nct = nct_p, ntl = (P / 16) * nct, ksteps = ce / 32;
       int ti = 0;
       for (int t = wave; t < ntl; t += nw, ++ti) {
@@ -394,7 +393,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(4))) void mb
         }
       }
     }
-    if (a.debug & 256) __syncthreads(); else lds_barrier();     // E and D are free for the next tile (whose x tile is in LDS already)
+    if (a.debug & kMbFullBarriers) __syncthreads(); else lds_barrier();     // E and D are free for the next tile (whose x tile is in LDS already)
   }
 }
 
@@ -615,7 +614,7 @@ __global__ __launch_bounds__(1024) void mbstrip_kernel(const MbArgs a) {
       }
       fetch(sc, first_new(qn + 4), count_new(qn + 4));
       MB_STAMP(0, k, 1);
-      if (EXPAND && k < K && !(a.debug & 2)) expand(first_new(qn), count_new(qn));
+      if (EXPAND && k < K && !(a.debug & kMbNoExpand)) expand(first_new(qn), count_new(qn));
       MB_STAMP(0, k, 2);
       lds_barrier();
     };
@@ -680,7 +679,7 @@ __global__ __launch_bounds__(1024) void mbstrip_kernel(const MbArgs a) {
       lds_barrier();
       for (int k = 0; k <= K + 1; ++k) {
         MB_STAMP(1, k, 0);
-        if (k >= 1 && k <= K && on && !(a.debug & 4)) {
+        if (k >= 1 && k <= K && on && !(a.debug & kMbNoDepthwise)) {
           const int m = (k - 1) % 3;
           if (m == 0) dw_row(std::integral_constant<int, 0>{}, k);
           else if (m == 1) dw_row(std::integral_constant<int, 1>{}, k);
@@ -707,7 +706,7 @@ __global__ __launch_bounds__(1024) void mbstrip_kernel(const MbArgs a) {
       for (int k = 0; k <= K + 1; ++k) {
         const int oy = oy0 + k - 1;                      // D[k & 1] = relu6(dw3x3(E) + bd) for the TW pixels of output row oy
         MB_STAMP(1, k, 0);
-        if (k >= 1 && k <= K && dw_on && !(a.debug & 4)) {
+        if (k >= 1 && k <= K && dw_on && !(a.debug & kMbNoDepthwise)) {
           const int iy0 = oy * S - 1;
           char* const dbuf = ld + (k & 1) * OPS * dstride;
           const char* const er[3] = {le + eslot(iy0) * IWE * estride, le + eslot(iy0 + 1) * IWE * estride, le + eslot(iy0 + 2) * IWE * estride};
@@ -752,7 +751,7 @@ __global__ __launch_bounds__(1024) void mbstrip_kernel(const MbArgs a) {
     for (int k = 0; k <= K + 1; ++k) {
       const int oy = oy0 + k - 2;                        // y[oy] = D[(k - 1) & 1] Wp^T + bp (+ x)
       MB_STAMP(2, k, 0);
-      if (k >= 2 && !(a.debug & 8)) {
+      if (k >= 2 && !(a.debug & kMbNoProject)) {
         const char* const dbuf = ld + ((k - 1) & 1) * OPS * dstride;
         const int nct = a.cop / 16, ntl = (OPS / 16) * nct, ksteps = ce / 32;
         for (int t = pw; t < ntl; t += G::WP) {
@@ -875,14 +874,6 @@ int launch(const MbArgs& a0, hipStream_t s) {
 
 }  // namespace
 
-// YOLO_MBCONV_DEBUG / yolo_set_tuning(4, .): bit 1 never halve the tile, 64 never the strip form (tests run both forms), 2 / 4 / 8 / 16
-// timing ablations (results wrong)
-int& yolo_conv_mb_debug() {
-  static int v = getenv("YOLO_MBCONV_DEBUG") ? atoi(getenv("YOLO_MBCONV_DEBUG")) : 0;
-  return v;
-}
-#define conv_mb_debug yolo_conv_mb_debug()
-
 // bytes per row of the depthwise-output tile and of W_proj: >= 2*ce, a multiple of 16 and == 96 or 160 (mod 256),
 // which spreads the 16 rows of an MFMA fragment read over all banks
 extern "C" int yolo_mbconv_dstride(int ce) {
@@ -945,9 +936,9 @@ extern "C" int yolo_mbconv_fwd(const void* x, const void* w_exp, const float* b_
   a.has_res = d.has_res;
   a.dstride = yolo_mbconv_dstride(a.ce);
   a.tiles_x = a.tiles_y = a.n_tiles = a.th = 0;
-  a.debug = conv_mb_debug;
+  a.debug = tuning().mbconv;
   hipStream_t st = (hipStream_t)s;
-  if (conv_mb_debug & 128) {        // round 5: the row-strip form, OPT-IN (measured slower than the tile form on every block: DESIGN.md
+  if (a.debug & kMbStripForm) {              // round 5: the row-strip form, OPT-IN (measured slower than the tile form on every block: DESIGN.md
                                     // Appendix A; tests run both); 1: it does not take the block
     const int rc = d.stride == 1 ? (d.has_expand ? launch_strip<1, true>(a, st) : launch_strip<1, false>(a, st))
                                  : (d.has_expand ? launch_strip<2, true>(a, st) : launch_strip<2, false>(a, st));
@@ -955,10 +946,10 @@ extern "C" int yolo_mbconv_fwd(const void* x, const void* w_exp, const float* b_
   }
   // tile: 8x8 outputs (4x8 at stride 2).  192 hidden channels at stride 1: 4x8, which lets two 512-thread workgroups
   // share a CU instead of one of 1024 threads (-10 %; with 144 hidden channels and at stride 2 the larger halo
-  // share of a half tile costs more than the overlap gains: measured, YOLO_MBCONV_DEBUG bit 1 = always the full tile)
+  // share of a half tile costs more than the overlap gains: measured, kMbFullTile = always the full tile)
   if (d.stride == 1) {
     if (!d.has_expand) return launch<1, 8, 8, false>(a, st);
-    if ((a.ce >= 192 || (conv_mb_debug & 32)) && !(conv_mb_debug & 1) && lds_bytes<1, 4, 8, true>(a) <= 80 * 1024) return launch<1, 4, 8, true>(a, st);
+    if ((a.ce >= 192 || (a.debug & kMbHalfTile)) && !(a.debug & kMbFullTile) && lds_bytes<1, 4, 8, true>(a) <= 80 * 1024) return launch<1, 4, 8, true>(a, st);
     return launch<1, 8, 8, true>(a, st);
   }
   return d.has_expand ? launch<2, 4, 8, true>(a, st) : launch<2, 4, 8, false>(a, st);

@@ -37,8 +37,7 @@ struct MbwArgs {
   int n, h, w, ho, wo, cin, in_ct, in_co, ce, cout, cop, out_ct, out_co, has_res;
   int tiles_x, tiles_y, n_tiles;
   uint32_t x_bytes;
-  int debug;            // YOLO_MBWIDE_DEBUG (timing only, results wrong): 2 no expand phase, 4 no depthwise phase, 8 no projection phase,
-                        // 16 no weight DMAs after chunk 0
+  int debug;            // YOLO_MBWIDE_DEBUG (timing only, results wrong: the kMbw* bits of tuning.h)
 };
 
 constexpr int kCH = 64;            // hidden channels per chunk
@@ -153,9 +152,9 @@ __global__ __launch_bounds__(NT) void mbwide_kernel(const MbwArgs a) {
     __syncthreads();
 
     for (int hc = 0; hc < nch; ++hc) {
-      if (!(a.debug & 16) || hc == 0) issue_p(hc);       // lwp is free: phase D of the previous chunk is behind the loop's last barrier
+      if (!(a.debug & kMbwNoWeightDma) || hc == 0) issue_p(hc);       // lwp is free: phase D of the previous chunk is behind the loop's last barrier
       // ---- B: E = relu6(X We^T + be), 0 outside the image.  wave: two of the chunk's four channel tiles, every 8th row tile
-      if (!(a.debug & 2)) {
+      if (!(a.debug & kMbwNoExpand)) {
         const int cg = wave & 1;
         bf16x8 wf[2][5];
 #pragma unroll
@@ -191,9 +190,9 @@ __global__ __launch_bounds__(NT) void mbwide_kernel(const MbwArgs a) {
       }
       __syncthreads();
       // the next chunk's set E: lwe / lbe are free once every wave has left phase B (wd / bd go to the other set)
-      if (hc + 1 < nch && !(a.debug & 16)) issue_e(hc + 1);
+      if (hc + 1 < nch && !(a.debug & kMbwNoWeightDma)) issue_e(hc + 1);
       // ---- C: D = relu6(dw3x3(E) + bd).  thread: 4 channels (its 36 taps in registers), every 64th pixel
-      if (!(a.debug & 4)) {
+      if (!(a.debug & kMbwNoDepthwise)) {
         const int qd = tid & 15;
         const float* const wdc = reinterpret_cast<const float*>(lwd + (hc & 1) * 4096);
         f32x2 wr[9][2];
@@ -273,7 +272,7 @@ __global__ __launch_bounds__(NT) void mbwide_kernel(const MbwArgs a) {
       else wait_vmcnt<4>();
       __syncthreads();
       // ---- D: acc += D Wp^T.  wave: row tiles rg + 4 i, cout tiles cq + NCG j
-      if (!(a.debug & 8)) {
+      if (!(a.debug & kMbwNoProject)) {
         const int rg = wave & 3, cq = wave >> 2;
 #pragma unroll
         for (int k = 0; k < kCH / 32; ++k) {

@@ -109,7 +109,7 @@ __global__ __launch_bounds__(512) void resunit_kernel(const ResUnitArgs ra) {
       char* const base = s_ring + st * A_STAGE;
 #pragma unroll
       for (int it = 0; it < A_XPT; ++it)
-        if (!(a.debug & 8)) lds_dma16s(rx, base + (it * NW + wave) * 1024, xa_off[it], (uint32_t)step * 64u);
+        if (!(a.debug & kRuNoPixelDma)) lds_dma16s(rx, base + (it * NW + wave) * 1024, xa_off[it], (uint32_t)step * 64u);
       if (wave < A_WPIECES) lds_dma16s(rw1, base + A_XB + wave * 1024, wa_off, (uint32_t)step * 64u);
     };
 
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(512) void resunit_kernel(const ResUnitArgs ra) {
           xf[p] = *reinterpret_cast<const bf16x8*>(xb + (R < 384 ? R : 0) * 64 + ((g ^ ((R >> 2) & 3)) << 4));
         }
 #pragma unroll
-        for (int i = 0; i < MI1 && !(a.debug & 1); ++i) {
+        for (int i = 0; i < MI1 && !(a.debug & kRuNoMfmaA); ++i) {
           acc1[0][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], xf[0], acc1[0][i], 0, 0, 0);
           if (two) acc1[1][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], xf[1], acc1[1][i], 0, 0, 0);
         }
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(512) void resunit_kernel(const ResUnitArgs ra) {
     // mid rows: lane = halo pixel, registers = mid channels (e&3) + 8*(e>>2) + 4*khalf
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-      if ((p == 1 && !two) || (a.debug & 16)) break;
+      if ((p == 1 && !two) || (a.debug & kRuNoMidRows)) break;
       const int hr = (wave + 8 * p) * 32 + r32;
       const int hy = hr / HW2, hx = hr - hy * HW2;
       const int yy = y0 - 1 + hy, xx = x0 - 1 + hx;
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(512) void resunit_kernel(const ResUnitArgs ra) {
         for (int i = 0; i < MI; ++i)
 #pragma unroll
           for (int j = 0; j < NI; ++j)
-            if (!(a.debug & 2)) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], xf[j], acc[i][j], 0, 0, 0);
+            if (!(a.debug & kRuNoMfmaB)) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], xf[j], acc[i][j], 0, 0, 0);
       }
       wb ^= 1;
     }
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(512) void resunit_kernel(const ResUnitArgs ra) {
     return (yy < d.h && xx < d.w) ? ((long)(b * d.h + yy) * d.w + xx) : -1L;
   };
   __syncthreads();
-  if (a.debug & 4) {
+  if (a.debug & kRuNoEpilogue) {
 #pragma unroll
     for (int i = 0; i < MI; ++i)
 #pragma unroll
@@ -572,11 +572,6 @@ int launch(const ResUnitArgs& ra, hipStream_t s) {
 
 }  // namespace
 
-int& yolo_conv::resunit_debug() {
-  static int v = getenv("YOLO_RESUNIT_DEBUG") ? atoi(getenv("YOLO_RESUNIT_DEBUG")) : 0;
-  return v;
-}
-
 extern "C" int yolo_resunit_supported(int c, int h, int w) {
   if (c != 64 && c != 128 && c != 256) return 0;
   const long tiles = (long)((h + 15) / 16) * ((w + 15) / 16);
@@ -605,34 +600,22 @@ extern "C" int yolo_resunit_fwd(const void* x, const void* w1_packed, const floa
   YOLO_REQUIRE(d.kpad % 64 == 0 && d.kpad >= 9 * d.cin && d.cout_pad % 128 == 0 && d.cout_pad >= C, "resunit: bad W2 packing");
   YOLO_REQUIRE(kpad1 % 64 == 0 && kpad1 >= C && cout_pad1 % 128 == 0 && cout_pad1 >= d.cin, "resunit: bad W1 packing");
   YOLO_REQUIRE(x != y, "resunit: y must not alias x (blocks read their neighbours' x halo)");
-  const size_t x_bytes = (size_t)d.n * d.h * d.w * d.in_c_total * 2;
-  const size_t w_bytes = (size_t)d.cout_pad * d.kpad * 2, w1_bytes = (size_t)cout_pad1 * kpad1 * 2;
-  YOLO_REQUIRE(x_bytes < kOobOffset && w_bytes < kOobOffset, "resunit: tensor larger than 3.75 GiB not supported");
+  YOLO_REQUIRE(conv_x_bytes(d) < kOobOffset && conv_w_bytes(d) < kOobOffset, "resunit: tensor larger than 3.75 GiB not supported");
   ResUnitArgs ra;
-  ra.c.x = (const bf16_t*)x;
-  ra.c.w = (const bf16_t*)w2_packed;
-  ra.c.bias = b2;
-  ra.c.res = (const bf16_t*)x;
-  ra.c.y = y;
-  ra.c.aux = (bf16_t*)y_preadd;
-  ra.c.d = d;
+  ra.c = make_conv_args(x, w2_packed, b2, x, y, y_preadd, d);   // (ho x wo = h x w: checked above)
   ra.c.d.res_c_total = d.in_c_total;
   ra.c.d.res_c_offset = d.in_c_offset;
-  ra.c.M = d.n * d.h * d.w;
   ra.c.n_tiles = 1;
-  ra.c.steps = 0;
-  ra.c.x_bytes = (uint32_t)x_bytes;
-  ra.c.w_bytes = (uint32_t)w_bytes;
-  ra.c.debug = resunit_debug();      // YOLO_RESUNIT_DEBUG / yolo_set_tuning(3, .): timing ablations and A/B forms only
+  ra.c.debug = tuning().resunit;     // timing ablations and A/B forms only
   ra.w1 = (const bf16_t*)w1_packed;
   ra.b1 = b1;
   ra.kpad1 = kpad1;
-  ra.w1_bytes = (uint32_t)w1_bytes;
-  if (!(ra.c.debug & 128)) {       // the 20-pixel-wide tile kernels (conv_resunit_t20.hip) where their tiles cover the map; bit 128: never, 64: always
-    const int rc = launch_resunit_t20(ra.c, ra.w1, ra.b1, ra.kpad1, ra.w1_bytes, (ra.c.debug & 64) != 0, (hipStream_t)s);
+  ra.w1_bytes = (uint32_t)((size_t)cout_pad1 * kpad1 * 2);
+  if (!(ra.c.debug & kRuT20Never)) {       // the 20-pixel-wide tile kernels (conv_resunit_t20.hip) where their tiles cover the map, or on every unit (kRuT20Always)
+    const int rc = launch_resunit_t20(ra.c, ra.w1, ra.b1, ra.kpad1, ra.w1_bytes, (ra.c.debug & kRuT20Always) != 0, (hipStream_t)s);
     if (rc != 1) return rc;
   }
-  if (C == 64 && !(ra.c.debug & 32)) {        // persistent, software-pipelined form (YOLO_RESUNIT_DEBUG bit 32: generic kernel)
+  if (C == 64 && !(ra.c.debug & kRuGeneric64)) {        // persistent, software-pipelined form (kRuGeneric64: generic kernel)
     static const int n_cu = [] {
       int dev = 0, v = 0;
       if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)

@@ -244,7 +244,7 @@ __global__ __launch_bounds__(256, 2) void resunit64_t20_kernel(const RU20Args ra
     asm volatile("s_nop 15\n\ts_nop 15");
 #endif
     RU_STAMP(3);
-    if (a.debug & 8) return;
+    if (a.debug & kRuT20NoEpilogue) return;
 
     // ---- epilogue: pair r = patches 2 r (waves 0, 1) and 2 r + 1 (waves 2, 3)
     static_for<13>([&](auto rc) {
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(256, 2) void resunit_t20w_kernel(const RU20Args ra)
   __builtin_amdgcn_s_barrier();                            // the image buffers now hold the whole intermediate halo
   RU_STAMP(3);
 
-  if (a.debug & 1024) {                                    // diagnosis: block 0 dumps its t images into y, nobody computes
+  if (a.debug & kRuT20DumpTile0) {                                    // diagnosis: block 0 dumps its t images into y, nobody computes
     if (blockIdx.x == 0)
       for (int i = tid; i < G::LDS_B / 16; i += 256) reinterpret_cast<u32x4*>(a.y)[i] = reinterpret_cast<const u32x4*>(smem)[i];
     return;
@@ -597,7 +597,7 @@ __global__ __launch_bounds__(256, 2) void resunit_t20w_kernel(const RU20Args ra)
 #ifdef YOLO_STAMPS
   if (a.stamps && tid == 0) a.stamps[8 * (size_t)blockIdx.x + 6] = __builtin_amdgcn_s_getreg((31 << 11) | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32);
 #endif
-  if (a.debug & 8) return;
+  if (a.debug & kRuT20NoEpilogue) return;
   __syncthreads();                                         // every wave is done with t: the staging slabs reuse the image buffers
 
   // ---- epilogue
@@ -689,7 +689,7 @@ int launch_ruw(const RU20Args& ra, bool force, hipStream_t s) {
   if (!force && !resunit_t20_applies(2 * CMID, d.n, d.h, d.w)) return 1;
   if (tiles > 0x7fffffffL) return 1;
   if (pick_only("resunit_t20w<C %d, %dpx x %d couts, 4 waves> grid %ld", 2 * CMID, 80 * TPH, 2 * CMID, tiles)) return 0;
-  const size_t dyn = (ra.c.debug & 512) ? 40 * 1024 : 0;                    // bit 512: one workgroup per CU (diagnosis)
+  const size_t dyn = (ra.c.debug & kRuT20OnePerCu) ? 40 * 1024 : 0;                    // one workgroup per CU (diagnosis)
   if (ra.c.d.act == YOLO_ACT_LEAKY01) hipLaunchKernelGGL((resunit_t20w_kernel<CMID, TPH, true>), dim3((unsigned)tiles), dim3(256), dyn, s, ra);
   else hipLaunchKernelGGL((resunit_t20w_kernel<CMID, TPH, false>), dim3((unsigned)tiles), dim3(256), dyn, s, ra);
   return yolo_check_launch("yolo_resunit_fwd(t20w)");

@@ -330,20 +330,9 @@ extern "C" int yolo_conv3x3_pool_fwd(const void* x, const void* w_packed, const 
   YOLO_REQUIRE(d.in_c_offset % 8 == 0 && d.in_c_total % 8 == 0 && d.in_c_offset + d.cin <= d.in_c_total, "conv3x3_pool: bad input view");
   YOLO_REQUIRE(d.out_c_offset % 8 == 0 && d.out_c_total % 8 == 0 && d.out_c_offset + d.cout <= d.out_c_total, "conv3x3_pool: bad output view");
   YOLO_REQUIRE(d.n > 0 && d.h > 0 && d.w > 0 && (!pool || (d.h >= 2 && d.w >= 2)), "conv3x3_pool: empty input");
-  ConvArgs a;
-  a.x = (const bf16_t*)x;
-  a.w = (const bf16_t*)w_packed;
-  a.bias = bias;
-  a.res = nullptr;
-  a.y = y;
-  a.aux = nullptr;
-  a.d = d;
-  a.M = d.n * d.h * d.w;
+  ConvArgs a = make_conv_args(x, w_packed, bias, nullptr, y, nullptr, d);
   a.n_tiles = 1;
-  a.steps = 0;
-  a.x_bytes = 0;
-  a.w_bytes = 0;
-  a.debug = 0;
+  a.x_bytes = a.w_bytes = 0;   // the kernel reads both through plain pointers
   YOLO_SET_STAMPS(a);
   hipStream_t st = (hipStream_t)s;
   if (d.cin == 16) return d.cout == 32 ? launch_small<16, 32>(a, pool != 0, st) : launch_small<16, 64>(a, pool != 0, st);

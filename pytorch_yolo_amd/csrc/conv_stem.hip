@@ -31,8 +31,7 @@ struct StemArgs {
   const float* b2;
   bf16_t* y;            // NHWC view
   int n, h, w, cin_real, ho, wo, out_c_total, out_c_offset, kpad1, kpad2, act;
-  int debug;            // timing ablations (YOLO_STEM_DEBUG): 1 no input loads, 2 no phase A, 4 no phase B (stem_kernel only), 8 no
-                        // stores, 64 producer waves alone (stem2_kernel only)
+  int debug;            // timing ablations (YOLO_STEM_DEBUG, the kStem* bits of tuning.h)
   unsigned long long* stamps;   // diagnostic build only (-DYOLO_STAMPS, tools/stem_timeline.py)
 };
 
@@ -151,13 +150,13 @@ __global__ __launch_bounds__(512) void stem_kernel(const StemArgs a) {
   auto fetch = [&](int b, int ty, int tx) {
     const int iy0 = 2 * ty * 16 - 2, ix0 = 2 * tx * 16 - 2;     // halo origin in input coordinates
     const float* const base = a.x + ((long)b * a.cin_real) * plane + (long)iy0 * a.w + ix0;
-    const bool interior = iy0 >= 0 && iy0 + IW <= a.h && ix0 >= 0 && ix0 + IW <= a.w && !(a.debug & 1);
+    const bool interior = iy0 >= 0 && iy0 + IW <= a.h && ix0 >= 0 && ix0 + IW <= a.w && !(a.debug & kStemNoLoads);
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
       bool ok = h_rel[u] >= 0;
       if (!interior)
         ok = ok && (unsigned)(iy0 + (h_yx[u] >> 8)) < (unsigned)a.h && (unsigned)(ix0 + (h_yx[u] & 255)) < (unsigned)a.w &&
-             !(a.debug & 1);
+             !(a.debug & kStemNoLoads);
       const float* src = base + h_rel[u];
 #pragma unroll
       for (int e = 0; e < NCH; ++e) pre[u][e] = (ok && (CIN || e < a.cin_real)) ? src[e * plane] : 0.f;
@@ -220,7 +219,7 @@ __global__ __launch_bounds__(512) void stem_kernel(const StemArgs a) {
     const bool interior = 2 * oy0 - 1 >= 0 && 2 * oy0 + 31 < a.h && 2 * ox0 - 1 >= 0 && 2 * ox0 + 31 < a.w;
 #pragma unroll
     for (int sl = 0; sl < A_SLOTS; ++sl) {
-      if (wave + NW * sl >= A_BLOCKS || (a.debug & 2)) break;
+      if (wave + NW * sl >= A_BLOCKS || (a.debug & kStemNoPhaseA)) break;
       f32x16 acc = bias1;
 #pragma unroll
       for (int ks = 0; ks < 5; ++ks) {
@@ -250,7 +249,7 @@ __global__ __launch_bounds__(512) void stem_kernel(const StemArgs a) {
     // ================= phase B: y = act(conv3x3/s2(mid) + b2), 32 pixels x 64 couts per wave =================
     f32x16 acc2[2] = {bias2[0], bias2[1]};
 #pragma unroll
-    for (int tap = 0; tap < ((a.debug & 4) ? 0 : 9); ++tap) {
+    for (int tap = 0; tap < ((a.debug & kStemNoPhaseB) ? 0 : 9); ++tap) {
       const int dh = tap / 3, dw = tap - 3 * dh;
       const int my = 2 * qy + dh, mxh = qx + (dw >> 1);
       const int R = (dw & 1) ? OD_BASE + my * OD_COLS + mxh : my * EV_COLS + mxh;
@@ -288,7 +287,7 @@ __global__ __launch_bounds__(512) void stem_kernel(const StemArgs a) {
 #pragma unroll
       for (int pass = 0; pass < 2; ++pass) {
         const int k = hh * 2 + pass;
-        const bool ok = (full || (oy0 + (o_yx[k] >> 8) < a.ho && ox0 + (o_yx[k] & 255) < a.wo)) && !(a.debug & 8);
+        const bool ok = (full || (oy0 + (o_yx[k] >> 8) < a.ho && ox0 + (o_yx[k] & 255) < a.wo)) && !(a.debug & kStemNoStores);
         if (ok) {
           const u32x4 val = *reinterpret_cast<const u32x4*>(stg + (pass * 8 + (lane >> 3)) * SP + (lane & 7) * 16);
           *reinterpret_cast<u32x4*>(ytile + o_rel[k]) = val;
@@ -437,7 +436,7 @@ __global__ __launch_bounds__(512) void stem2_kernel(const StemArgs a) {
 #pragma unroll
       for (int u = 0; u < 3; ++u) {
         const bool ok = (h_rel[u] >= 0) & ((unsigned)(iy0 + (h_yx[u] >> 8)) < (unsigned)a.h) &
-                        ((unsigned)(ix0 + (h_yx[u] & 255)) < (unsigned)a.w) & !(a.debug & 1);
+                        ((unsigned)(ix0 + (h_yx[u] & 255)) < (unsigned)a.w) & !(a.debug & kStemNoLoads);
         const uint32_t vo = ok ? (uint32_t)(base + h_rel[u]) * 4u : kOobOffset;
 #pragma unroll
         for (int e = 0; e < 3; ++e)
@@ -532,7 +531,7 @@ __global__ __launch_bounds__(512) void stem2_kernel(const StemArgs a) {
             __builtin_amdgcn_sched_barrier(0);
           }
         };
-        if (!(a.debug & 2)) {
+        if (!(a.debug & kStemNoPhaseA)) {
           if (interior) conv1(std::false_type{});
           else conv1(std::true_type{});
         }
@@ -623,7 +622,7 @@ __global__ __launch_bounds__(512) void stem2_kernel(const StemArgs a) {
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int k = 0; k < 4; ++k) {                        // (no branches: pixels past the map get the out-of-range offset)
-          const bool ok = (oy0 + bw * 2 + (k >> 1) < a.ho) & (ox0 + (k & 1) * 8 + o_x < a.wo) & !(a.debug & 8);
+          const bool ok = (oy0 + bw * 2 + (k >> 1) < a.ho) & (ox0 + (k & 1) * 8 + o_x < a.wo) & !(a.debug & kStemNoStores);
           const u32x4 val = *reinterpret_cast<const u32x4*>(stg + (k * 8 + (lane >> 3)) * SP + (lane & 7) * 16);
           const uint32_t off = tile_off + (uint32_t)(((k >> 1) * a.wo + (k & 1) * 8) * a.out_c_total) * 2u + o_rel;
           __builtin_amdgcn_raw_buffer_store_b128(val, ry, ok ? off : kOobOffset, 0, 0);
@@ -641,7 +640,7 @@ __global__ __launch_bounds__(512) void stem2_kernel(const StemArgs a) {
     step(P0{}, std::true_type{}, std::false_type{}, 0);
     wait_lds();
     __builtin_amdgcn_s_barrier();
-    if (a.debug & 64) {                                      // timing only: the producers alone
+    if (a.debug & kStemProducersOnly) {                                      // timing only: the producers alone
       for (int t = 1; t < count; ++t) __builtin_amdgcn_s_barrier();
       return;
     }

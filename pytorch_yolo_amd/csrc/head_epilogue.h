@@ -1,6 +1,5 @@
 // The YOLOLayer decode + NMS row filter that a head conv runs as its epilogue (reference models/yolo_layer.py:57-69,90-96 and
-// utils/utils.py:212-218), shared by the tiled head kernel (conv_igemm.hip, DECODE instances) and the pipelined weight-stationary
-// one (conv_head_stream.hip, round 5).
+// utils/utils.py:212-218), run by the tiled head kernel (conv_igemm.hip, DECODE instances).
 #pragma once
 #include "conv_common.h"
 #include "nms_common.h"

@@ -437,7 +437,7 @@ static int launch_dw_strip(const bf16_t* x, const float* w, const float* bias, b
   return yolo_check_launch("yolo_dwconv3x3_fwd");
 }
 
-static const int dw_debug = [] {      // YOLO_DWCONV_DEBUG: 1 = one-pixel form, 2 = strips of 4 rows instead of 8 (tuning only)
+static const int dw_debug = [] {      // YOLO_DWCONV_DEBUG (tuning only: the kDw* bits of tuning.h)
   const char* e = getenv("YOLO_DWCONV_DEBUG");
   return e ? atoi(e) : 0;
 }();
@@ -450,11 +450,11 @@ extern "C" int yolo_dwconv3x3_fwd(const void* x, const float* w, const float* bi
   YOLO_REQUIRE(ho == (h + 2 - 3) / stride + 1 && wo == (w_ + 2 - 3) / stride + 1, "dwconv: bad output size");
   YOLO_REQUIRE(in_c_total % 8 == 0 && in_c_offset % 8 == 0 && out_c_total % 8 == 0 && out_c_offset % 8 == 0,
                "dwconv: views must be 8-channel aligned");
-  if (!(dw_debug & 1)) {
+  if (!(dw_debug & kDwOnePixel)) {
     const bf16_t* xb = (const bf16_t*)x;
     bf16_t* yb = (bf16_t*)y;
     hipStream_t st = (hipStream_t)s;
-    if (dw_debug & 2)
+    if (dw_debug & kDwFourRows)
       return stride == 1 ? launch_dw_strip<1, 4>(xb, w, bias, yb, n, h, w_, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, act, st)
                          : launch_dw_strip<2, 4>(xb, w, bias, yb, n, h, w_, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, act, st);
     // 8-row strips: 0.040 -> 0.028 ms on the 26x26x384 maps of 64 images (4-row strips 0.032), also on 13x13 (13 -> 16 rows)

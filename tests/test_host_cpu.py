@@ -648,3 +648,25 @@ def test_tile_rules_follow_the_cu_share_of_a_partitioned_stream():
     assert _pick(16, 20, 20, 1024, 512, 1, 1) == "igemm<128x128,2x4 waves,BK64,3 stages,16x16x32> grid 200"
     with pytest.raises(RuntimeError):
         K.set_launch_cus(3)
+
+
+def test_tuning_table_names_single_bits_and_the_knobs_round_trip():
+    """csrc/tuning.h is the one table of knobs: every named bit is a single bit, a value appears once per knob word (the fused
+    units' bit 8 excepted: it is an ablation in both of their kernel families and has a name in each), and yolo_set_tuning(knob, v)
+    returns the previous value for knobs 0..4 and refuses any other knob."""
+    text = open(os.path.join(ROOT, "pytorch_yolo_amd", "csrc", "tuning.h")).read()
+    groups = re.findall(r"enum : int \{(.*?)\};", text, re.S)
+    assert len(groups) == 7
+    for body in groups:
+        values = [int(v) for v in re.findall(r"^\s*k\w+ = (\d+),", body, re.M)]
+        assert values and all(v > 0 and v & (v - 1) == 0 for v in values)
+        assert len(set(values)) == len(values) - ("kRuT20NoEpilogue" in body)
+    lib = _lib.load()
+    for knob in range(5):
+        old = lib.yolo_set_tuning(knob, 12345)
+        try:
+            assert lib.yolo_set_tuning(knob, 777) == 12345
+        finally:
+            assert lib.yolo_set_tuning(knob, old) == 777
+    assert lib.yolo_set_tuning(5, 0) != 0 and lib.yolo_set_tuning(-1, 0) != 0
+    assert b"unknown knob" in lib.yolo_last_error()
