@@ -38,7 +38,7 @@ typedef void* yolo_stream_t; /* hipStream_t */
 enum { YOLO_E_ARG = -1, YOLO_E_UNSUPPORTED = -2, YOLO_E_WORKSPACE = -3 };
 enum { YOLO_ACT_NONE = 0, YOLO_ACT_LEAKY01 = 1, YOLO_ACT_RELU6 = 2, YOLO_ACT_RELU = 3,
        YOLO_ACT_SWISH = 4 /* x * sigmoid(x): SwissActivation, models/yolov3_tiny_efficient.py:13-19 */ };
-enum { YOLO_DT_BF16 = 0, YOLO_DT_F32 = 1 };
+enum { YOLO_DT_BF16 = 0, YOLO_DT_F32 = 1, YOLO_DT_F16 = 2 /* IEEE half: the fp16-operand entry points below */ };
 
 YOLO_API const char* yolo_last_error(void);
 /* ABI version of this header: 2.  History: 1 -> 2 (round 5; the change itself dates from round 4): YoloOp's two former padding words
@@ -313,6 +313,35 @@ YOLO_API int yolo_pack_input_nchw_f32_nhwc(const float* x, float* y, int n, int 
 YOLO_API int yolo_pack_conv_weight_f32_f32(const float* w_oihw, int cout, int cin_w, int ksize, int cin, int cout_pad, int kpad,
                                            float* out);
 
+/* ---- fp16-operand mode (model.precision = "fp16"): the rounding points of the bf16 path with IEEE half instead - fp16 NHWC
+ *  activations and packed weights (same bytes and layout as bf16), fp32 accumulation on v_mfma_f32_16x16x32_f16 /
+ *  v_mfma_f32_32x32x16_f16, the residual sum formed in fp32 and stored once, fp32 head outputs.  Narrowing: round to nearest even; a
+ *  FINITE value beyond +-65504 stores +-65504; NaN and +-inf stay.  Every launch is an instance of the gather kernel's fp16 table
+ *  (csrc/conv_igemm.hip); there is no split-K form and the tuning word of yolo_set_tuning does not apply.
+ *  yolo_conv2d_f16_fwd: as yolo_conv2d_fwd; d->out_dtype is YOLO_DT_F16 or YOLO_DT_F32; w_packed from yolo_pack_conv_weight_f32_f16
+ *  (same sizes and k order as the bf16 packing).  yolo_conv2d_f16_pick / yolo_head_decode_f16_pick: the instance + grid
+ *  ("igemm_f16<...> grid N"), no launch, no GPU.  yolo_head_decode_f16_fwd / yolo_head_decode_filter_f16_fwd: as their bf16 forms
+ *  (the decode works on the fp32 accumulators).  yolo_maxpool_f16_fwd: MaxPool on fp16 views.  The SPP pyramid of an fp16 buffer is
+ *  yolo_spp_fwd itself: it orders 16-bit sign-magnitude patterns, which IEEE half is too.
+ *  yolo_pack_input_nchw_f32_f16: x f32 NCHW -> y fp16 NHWC [n,h,w,c_pad]. */
+YOLO_API int yolo_conv2d_f16_fwd(const void* x, const void* w_packed, const float* bias, const void* residual, void* y,
+                                 void* y_preadd, const YoloConvDesc* d, yolo_stream_t s);
+YOLO_API int yolo_conv2d_f16_pick(const YoloConvDesc* d, int has_residual, int has_preadd, char* out, int out_len);
+YOLO_API int yolo_head_decode_f16_pick(const YoloConvDesc* d, int na, int nc, int filter, char* out, int out_len);
+YOLO_API int yolo_head_decode_f16_fwd(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* d,
+                                      const float* anchors_px, int na, int nc, float stride_px, float* io,
+                                      int io_rows_total, int io_row_offset, float* p, yolo_stream_t s);
+YOLO_API int yolo_head_decode_filter_f16_fwd(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* d,
+                                             const float* anchors_px, int na, int nc, float stride_px, int io_rows_total,
+                                             int io_row_offset, float conf_thres, float min_wh, void* workspace,
+                                             size_t workspace_bytes, float* p, yolo_stream_t s);
+YOLO_API int yolo_maxpool_f16_fwd(const void* x, void* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho,
+                                  int wo, int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation,
+                                  yolo_stream_t s);
+YOLO_API int yolo_pack_input_nchw_f32_f16(const float* x, void* y, int n, int c, int h, int w, int c_pad, yolo_stream_t s);
+YOLO_API int yolo_pack_conv_weight_f32_f16(const float* w_oihw, int cout, int cin_w, int ksize, int cin, int cout_pad, int kpad,
+                                           uint16_t* out);
+
 /* ---- batched launcher: run a recorded list of ops with one FFI crossing (host overhead only). */
 enum { YOLO_OP_CONV = 1, YOLO_OP_MAXPOOL = 2, YOLO_OP_SPP = 3, YOLO_OP_DWCONV = 4, YOLO_OP_CONV1_NCHW = 5,
        YOLO_OP_RESUNIT = 6, YOLO_OP_STEM = 7, YOLO_OP_HEAD_DECODE = 8, YOLO_OP_CONV1_POOL = 9, YOLO_OP_MBCONV = 10,
@@ -320,7 +349,9 @@ enum { YOLO_OP_CONV = 1, YOLO_OP_MAXPOOL = 2, YOLO_OP_SPP = 3, YOLO_OP_DWCONV = 
        YOLO_OP_SHUFFLE = 12 /* yolo_channel_shuffle2_fwd: x = a, residual = b, conv.cin = c_slot, conv.cout = half, res_* = view of b */,
        YOLO_OP_CONV_F32 = 13 /* yolo_conv2d_f32_fwd */, YOLO_OP_MAXPOOL_F32 = 14 /* yolo_maxpool_f32_fwd, fields as MAXPOOL */,
        YOLO_OP_SE = 15 /* yolo_se_fwd: x / y views in conv (n, h, w, cin, in_*, out_*), w / bias = W1 / b1, w_pre / bias_pre = W2 / b2,
-                          kpad_pre = squeezed channels, workspace / ws_bytes */ };
+                          kpad_pre = squeezed channels, workspace / ws_bytes */,
+       YOLO_OP_CONV_F16 = 16 /* yolo_conv2d_f16_fwd */, YOLO_OP_MAXPOOL_F16 = 17 /* yolo_maxpool_f16_fwd, fields as MAXPOOL */,
+       YOLO_OP_HEAD_DECODE_F16 = 18 /* yolo_head_decode_f16_fwd / yolo_head_decode_filter_f16_fwd, fields as HEAD_DECODE */ };
 typedef struct YoloOp {
   int32_t kind, _pad;
   const void* x; const void* w; const float* bias; const void* residual; void* y; void* y_aux;

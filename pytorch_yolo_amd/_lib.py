@@ -13,9 +13,10 @@ LIB_PATH = os.environ.get("YOLO_HIP_LIB") or os.path.join(_HERE, "csrc", "libyol
 
 ABI_VERSION = 2          # include/yolo_hip.h, yolo_abi_version
 ACT_NONE, ACT_LEAKY01, ACT_RELU6, ACT_RELU, ACT_SWISH = 0, 1, 2, 3, 4
-DT_BF16, DT_F32 = 0, 1
+DT_BF16, DT_F32, DT_F16 = 0, 1, 2
 OP_CONV, OP_MAXPOOL, OP_SPP, OP_DWCONV, OP_CONV1_NCHW, OP_RESUNIT, OP_STEM, OP_HEAD_DECODE, OP_CONV1_POOL = 1, 2, 3, 4, 5, 6, 7, 8, 9
 OP_MBCONV, OP_CONV_POOL, OP_SHUFFLE, OP_CONV_F32, OP_MAXPOOL_F32, OP_SE = 10, 11, 12, 13, 14, 15
+OP_CONV_F16, OP_MAXPOOL_F16, OP_HEAD_DECODE_F16 = 16, 17, 18          # the fp16-operand mode
 
 
 class YoloConvDesc(C.Structure):
@@ -113,6 +114,16 @@ SIGNATURES = {
     "yolo_maxpool_f32_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 14 + [C.c_void_p]),
     "yolo_pack_input_nchw_f32_nhwc": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "yolo_pack_conv_weight_f32_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "yolo_conv2d_f16_fwd": (C.c_int, [C.c_void_p] * 6 + [C.POINTER(YoloConvDesc), C.c_void_p]),
+    "yolo_conv2d_f16_pick": (C.c_int, [C.POINTER(YoloConvDesc), C.c_int, C.c_int, C.c_char_p, C.c_int]),
+    "yolo_head_decode_f16_pick": (C.c_int, [C.POINTER(YoloConvDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
+    "yolo_head_decode_f16_fwd": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YoloConvDesc), C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "yolo_head_decode_filter_f16_fwd": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YoloConvDesc), C.c_void_p, C.c_int, C.c_int, C.c_float,
+                                                  C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "yolo_maxpool_f16_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 14 + [C.c_void_p]),
+    "yolo_pack_input_nchw_f32_f16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "yolo_pack_conv_weight_f32_f16": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "yolo_run_ops": (C.c_int, [C.POINTER(YoloOp), C.c_int, C.c_void_p]),
     "yolo_stream_create_cu_mask": (C.c_int, [C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_void_p)]),
     "yolo_stream_destroy": (C.c_int, [C.c_void_p]),

@@ -13,6 +13,9 @@
 typedef __bf16 bf16_t;
 typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
 typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16_t;      // IEEE half: the operand type of model.precision = "fp16" (same bytes and layout as bf16)
+typedef f16_t f16x4 __attribute__((ext_vector_type(4)));
+typedef f16_t f16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));

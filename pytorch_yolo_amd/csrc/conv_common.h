@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 
+#include <type_traits>
 #include <utility>
 
 namespace yolo_conv {
@@ -16,6 +17,30 @@ __device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int
 template <int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
+}
+
+// The 16-bit operand types of the gather kernel (conv_igemm.hip): their 4- and 8-element vectors, and the narrowing store.
+template <typename T>
+struct Pack;
+template <>
+struct Pack<bf16_t> {
+  using x4 = bf16x4;
+  using x8 = bf16x8;
+};
+template <>
+struct Pack<f16_t> {
+  using x4 = f16x4;
+  using x8 = f16x8;
+};
+// fp32 -> T, round to nearest even.  fp16: a FINITE value beyond +-65504 stores +-65504 (bf16 has fp32's range and needs no clamp);
+// NaN and +-inf stay what they are - both compares are false for a NaN, and an inf is not "< inf" - so a broken layer stays visible.
+template <typename T>
+__device__ __forceinline__ T narrow(float v) {
+  if constexpr (std::is_same<T, f16_t>::value) {
+    const float m = __builtin_fabsf(v);
+    if (m > 65504.f && m < __builtin_inff()) v = __builtin_copysignf(65504.f, v);
+  }
+  return (T)v;
 }
 
 constexpr uint32_t kOobOffset = 0xF0000000u;  // > any buffer we accept (host checks < 0xF0000000 bytes)
@@ -35,7 +60,7 @@ struct HeadDecodeArgs {
 };
 
 struct ConvArgs {
-  const bf16_t* x = nullptr;
+  const bf16_t* x = nullptr;   // (fp16 launches of conv_igemm.hip carry their f16 pointers in these fields: same bytes)
   const bf16_t* w = nullptr;
   const float* bias = nullptr;
   const bf16_t* res = nullptr;
@@ -47,7 +72,7 @@ struct ConvArgs {
   int steps = 0;    // kpad / 32
   uint32_t x_bytes = 0, w_bytes = 0;
   HeadDecodeArgs hd;   // DECODE instances only
-  // split-K launches (conv_igemm_bf16_kernel<..., SPLITK>): grid.y = splits, `steps` = K steps PER split; every split
+  // split-K launches (conv_igemm_kernel<..., SPLITK>): grid.y = splits, `steps` = K steps PER split; every split
   // writes its fp32 partial tile to ws[split][M][cout], the last one to arrive at a tile (cnt[tile], self-resetting)
   // adds the partials in split order and runs the normal epilogue
   int splits = 1;
@@ -219,9 +244,10 @@ struct ResPrefetch {
 // writes whole 128-byte lines.  With one 32-cout slab at a time a line was written as two 64-byte halves in two
 // different passes, and the partially written lines cost the memory system about twice the traffic of the store.
 constexpr int kEpiPitch2 = 272;   // 64 f32 + 16 B pad
-template <int MI, int TM, typename WriteRows, typename PixOf>
+template <int MI, int TM, typename T = bf16_t, typename WriteRows, typename PixOf>
 __device__ __forceinline__ void epilogue_lds_core(const ConvArgs& a, char* stg, int lane, int cout0, WriteRows write_rows,
                                                   PixOf pix_of, const ResPrefetch<MI, TM>* rpre) {
+  using X8 = typename Pack<T>::x8;
   const YoloConvDesc& d = a.d;
   const int hw_out = d.ho * d.wo;
   constexpr bool PAIR = MI % 2 == 0;
@@ -253,30 +279,30 @@ __device__ __forceinline__ void epilogue_lds_core(const ConvArgs& a, char* stg, 
           const f32x4 hi = *reinterpret_cast<const f32x4*>(stg + lrow * PITCH + cchunk * 32 + 16);
           float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
           if (a.aux) {
-            bf16x8 o;
+            X8 o;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (bf16_t)v[e];
-            *reinterpret_cast<bf16x8*>(a.aux + pix * d.aux_c_total + d.aux_c_offset + cofs) = o;
+            for (int e = 0; e < 8; ++e) o[e] = narrow<T>(v[e]);
+            *reinterpret_cast<X8*>(reinterpret_cast<T*>(a.aux) + pix * d.aux_c_total + d.aux_c_offset + cofs) = o;
           }
           if (a.res) {
-            const bf16x8 rv = rpre ? rpre->v[rp_idx]
-                                   : *reinterpret_cast<const bf16x8*>(a.res + pix * d.res_c_total + d.res_c_offset + cofs);
+            const X8 rv = rpre ? __builtin_bit_cast(X8, rpre->v[rp_idx])
+                               : *reinterpret_cast<const X8*>(reinterpret_cast<const T*>(a.res) + pix * d.res_c_total + d.res_c_offset + cofs);
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] += (float)rv[e];
           }
-          bf16x8 o;
+          X8 o;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) o[e] = (bf16_t)v[e];
-          bf16_t* const ybase = reinterpret_cast<bf16_t*>(a.y) + d.out_c_offset + cofs;
+          for (int e = 0; e < 8; ++e) o[e] = narrow<T>(v[e]);
+          T* const ybase = reinterpret_cast<T*>(a.y) + d.out_c_offset + cofs;
           if (d.upsample2x) {
             const int b = (int)(pix / hw_out), rem = (int)(pix - (long)b * hw_out);
             const int oh = rem / d.wo, ow = rem - oh * d.wo;
             const long op = ((long)(b * 2 * d.ho + 2 * oh)) * (2 * d.wo) + 2 * ow;
 #pragma unroll
             for (int rep = 0; rep < 4; ++rep)
-              *reinterpret_cast<bf16x8*>(ybase + (op + (rep >> 1) * 2 * d.wo + (rep & 1)) * d.out_c_total) = o;
+              *reinterpret_cast<X8*>(ybase + (op + (rep >> 1) * 2 * d.wo + (rep & 1)) * d.out_c_total) = o;
           } else {
-            *reinterpret_cast<bf16x8*>(ybase + pix * d.out_c_total) = o;
+            *reinterpret_cast<X8*>(ybase + pix * d.out_c_total) = o;
           }
         }
       }
@@ -287,11 +313,11 @@ __device__ __forceinline__ void epilogue_lds_core(const ConvArgs& a, char* stg, 
 
 // 32x32x16 accumulators: acc[i][j] = couts [32i, 32i+32) x pixels [32j, 32j+32); lane = pixel column r32,
 // register e -> cout (e&3) + 8*(e>>2) + 4*(lane>>5).
-template <int MI, int NI, int TM, typename PixOf>
+template <int MI, int NI, int TM, typename T = bf16_t, typename PixOf>
 __device__ __forceinline__ void epilogue_lds(const ConvArgs& a, const f32x16 (&acc)[MI][NI], char* stg, int lane,
                                              int cout0, PixOf pix_of, const ResPrefetch<MI, TM>* rpre = nullptr) {
   const int r32 = lane & 31, khalf = lane >> 5;
-  epilogue_lds_core<MI, TM>(a, stg, lane, cout0, [&](int i, int cbase, int row_lo, int nrows, int pitch, int col_off) {
+  epilogue_lds_core<MI, TM, T>(a, stg, lane, cout0, [&](int i, int cbase, int row_lo, int nrows, int pitch, int col_off) {
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
       const int row = j * 32 + r32 - row_lo;
@@ -312,11 +338,11 @@ __device__ __forceinline__ void epilogue_lds(const ConvArgs& a, const f32x16 (&a
 
 // 16x16x32 accumulators: acc[i][j] = couts [16i, 16i+16) x pixels [16j, 16j+16); lane = pixel column lane&15,
 // register e -> cout 4*(lane>>4) + e.  MI16 = 2*MI cout tiles, NI16 pixel tiles.
-template <int MI, int NI16, int TM, typename PixOf>
+template <int MI, int NI16, int TM, typename T = bf16_t, typename PixOf>
 __device__ __forceinline__ void epilogue_lds16(const ConvArgs& a, const f32x4 (&acc)[2 * MI][NI16], char* stg, int lane,
                                                int cout0, PixOf pix_of) {
   const int c16 = lane & 15, q = lane >> 4;
-  epilogue_lds_core<MI, TM>(a, stg, lane, cout0, [&](int i, int cbase, int row_lo, int nrows, int pitch, int col_off) {
+  epilogue_lds_core<MI, TM, T>(a, stg, lane, cout0, [&](int i, int cbase, int row_lo, int nrows, int pitch, int col_off) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int cl = t * 16 + q * 4;

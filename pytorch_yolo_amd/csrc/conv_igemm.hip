@@ -1,5 +1,5 @@
-// Implicit-GEMM convolution for gfx950 (MI355X): bf16 NHWC activations, fp32 accumulate on
-// v_mfma_f32_32x32x16_bf16, fused bias / LeakyReLU(0.1) / ReLU6 / residual add / pre-add copy /
+// Implicit-GEMM convolution for gfx950 (MI355X): 16-bit NHWC activations (bf16, or IEEE half for model.precision = "fp16"), fp32
+// accumulate on v_mfma_f32_32x32x16_bf16 / _f16, fused bias / LeakyReLU(0.1) / ReLU6 / residual add / pre-add copy /
 // channel-offset (concat) store / 2x nearest-upsample store / fp32 head store.
 //
 // Replaces the ATen dispatches of ConvBlock.forward (reference models/yolo_base.py:19-44, BN folded
@@ -26,17 +26,24 @@ using namespace yolo_conv;
 // fragment read from LDS; the timing-only ablation build YOLO_ABL_NOLDS (tools/block_timeline.py) feeds the MFMAs
 // whatever the registers hold instead
 #ifdef YOLO_ABL_NOLDS
-__device__ __forceinline__ bf16x8 lds_frag_stub() {
-  bf16x8 v;
+template <typename X8>
+__device__ __forceinline__ X8 lds_frag_stub() {
+  X8 v;
   asm volatile("" : "=v"(v));
   return v;
 }
-#define YOLO_LDS_FRAG(p) lds_frag_stub()
+#define YOLO_LDS_FRAG(p) lds_frag_stub<X8>()
 #else
-#define YOLO_LDS_FRAG(p) (*reinterpret_cast<const bf16x8*>(p))
+#define YOLO_LDS_FRAG(p) (*reinterpret_cast<const X8*>(p))
 #endif
 
 namespace {
+
+// The two MFMA shapes for either operand type (same cycles; v_mfma_f32_16x16x32_f16 / v_mfma_f32_32x32x16_f16 for IEEE half)
+__device__ __forceinline__ f32x4 mfma16(bf16x8 w, bf16x8 x, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma16(f16x8 w, f16x8 x, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(w, x, c, 0, 0, 0); }
+__device__ __forceinline__ f32x16 mfma32(bf16x8 w, bf16x8 x, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, x, c, 0, 0, 0); }
+__device__ __forceinline__ f32x16 mfma32(f16x8 w, f16x8 x, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(w, x, c, 0, 0, 0); }
 
 // BM pixels x BN couts block tile, WAVES_M x WAVES_N waves (4 or 8), K step BK (32 or 64), NS-stage LDS ring.
 // Stage s+NS-1 is in flight (LDS-DMA) while stage s is multiplied: the waits are COUNTED
@@ -45,11 +52,15 @@ namespace {
 // FAST (cin % BK == 0): a K step never straddles a filter tap, so tap / channel offset are wave-uniform
 // scalars, the image-border test is one precomputed bit per tap, and the weight address advances through
 // the instruction's scalar offset: ~3 VALU per LDS-DMA instead of ~15.
-// LDS_EPI (bf16 output, cout % 32 == 0): the finished tile goes registers -> LDS (fp32) -> global so that
+// T: the operand element type, bf16_t or f16_t - the LDS-DMA ring, the gathers and the swizzle move bytes and do not depend on it; the
+// MFMA calls, the narrowing stores and the residual load do.
+// LDS_EPI (16-bit output, cout % 32 == 0): the finished tile goes registers -> LDS (fp32) -> global so that
 // residual read, pre-add copy and store are 16-byte-per-lane accesses over whole channel runs.
 template <int BM, int BN, int WAVES_M, int WAVES_N, int BK, int NS, bool FAST, bool LDS_EPI, bool MFMA16 = false, bool DECODE = false,
-          int NP = 0, bool SPLITK = false>
-__global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16_kernel(const ConvArgs a) {
+          int NP = 0, bool SPLITK = false, typename T = bf16_t>
+__global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_kernel(const ConvArgs a) {
+  using X4 = typename Pack<T>::x4;
+  using X8 = typename Pack<T>::x8;
   static_assert(!SPLITK || (FAST && LDS_EPI && MFMA16 && !DECODE), "split-K: 16x16x32 path with the LDS epilogue");
   constexpr int NW = WAVES_M * WAVES_N;
   // NP > 0: NP extra LOADER waves issue every LDS-DMA of the block; the NW MFMA waves only read LDS and multiply
@@ -314,29 +325,29 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16
         if (!(a.debug & kCdNoMfma)) {
           const char* const wk = wbuf + (kk ? (wo ^ 64) : wo);
           const char* const xk = xbuf + (kk ? (xo ^ 64) : xo);
-          bf16x8 xf[NI16];
+          X8 xf[NI16];
 #pragma unroll
           for (int j = 0; j < NI16; ++j) xf[j] = YOLO_LDS_FRAG(xk + j * 16 * ROWB);
           if constexpr (NP > 0) {
             // register-lean order (3 waves per SIMD leave 168 registers): weight fragments one ahead of their MFMAs
-            bf16x8 wcur = *reinterpret_cast<const bf16x8*>(wk);
+            X8 wcur = *reinterpret_cast<const X8*>(wk);
 #pragma unroll
             for (int i = 0; i < MI16; ++i) {
-              const bf16x8 wnext = *reinterpret_cast<const bf16x8*>(wk + (i + 1 < MI16 ? i + 1 : i) * 16 * ROWB);
+              const X8 wnext = *reinterpret_cast<const X8*>(wk + (i + 1 < MI16 ? i + 1 : i) * 16 * ROWB);
 #pragma unroll
               for (int j = 0; j < NI16; ++j)
-                acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wcur, xf[j], acc16[i][j], 0, 0, 0);
+                acc16[i][j] = mfma16(wcur, xf[j], acc16[i][j]);
               wcur = wnext;
             }
           } else {
-            bf16x8 wf[MI16];
+            X8 wf[MI16];
 #pragma unroll
             for (int i = 0; i < MI16; ++i) wf[i] = YOLO_LDS_FRAG(wk + i * 16 * ROWB);
 #pragma unroll
             for (int i = 0; i < MI16; ++i)
 #pragma unroll
               for (int j = 0; j < NI16; ++j)
-                acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[i], xf[j], acc16[i][j], 0, 0, 0);
+                acc16[i][j] = mfma16(wf[i], xf[j], acc16[i][j]);
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -347,24 +358,24 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16
       if (more) issue(nb, s + NS - 1, ks * LPS / KS, (ks + 1) * LPS / KS);
       if (!(a.debug & kCdNoMfma)) {
         const int g = ks * 2 + khalf;
-        bf16x8 wf[MI], xf[NI];
+        X8 wf[MI], xf[NI];
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
           const int R = wn * TN + i * 32 + r32;
           const int sw = (BK == 32) ? swz32(R >> 2) : ((R >> 1) & 7);
-          wf[i] = *reinterpret_cast<const bf16x8*>(wbuf + R * ROWB + ((g ^ sw) << 4));
+          wf[i] = *reinterpret_cast<const X8*>(wbuf + R * ROWB + ((g ^ sw) << 4));
         }
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
           const int R = wm * TM + j * 32 + r32;
           const int sw = (BK == 32) ? swz32(R >> 2) : ((R >> 1) & 7);
-          xf[j] = *reinterpret_cast<const bf16x8*>(xbuf + R * ROWB + ((g ^ sw) << 4));
+          xf[j] = *reinterpret_cast<const X8*>(xbuf + R * ROWB + ((g ^ sw) << 4));
         }
 #pragma unroll
         for (int i = 0; i < MI; ++i)
 #pragma unroll
           for (int j = 0; j < NI; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], xf[j], acc[i][j], 0, 0, 0);
+            acc[i][j] = mfma32(wf[i], xf[j], acc[i][j]);
       }
       __builtin_amdgcn_sched_barrier(0);   // keep each DMA slice in front of its MFMA group
     }
@@ -461,10 +472,10 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16
         }
       if (tid == 0) __hip_atomic_store(a.cnt + blockIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
     }
-    epilogue_lds16<MI, NI16, TM>(a, acc16, smem + wave * (TM * kEpiPitch), lane, n0 + wn * TN, pix_of);
+    epilogue_lds16<MI, NI16, TM, T>(a, acc16, smem + wave * (TM * kEpiPitch), lane, n0 + wn * TN, pix_of);
   } else if constexpr (LDS_EPI) {
     __syncthreads();                                 // every wave is done with the last stage: LDS is free
-    epilogue_lds<MI, NI, TM>(a, acc, smem + wave * (TM * kEpiPitch), lane, n0 + wn * TN, pix_of);
+    epilogue_lds<MI, NI, TM, T>(a, acc, smem + wave * (TM * kEpiPitch), lane, n0 + wn * TN, pix_of);
   } else {
 #pragma unroll
   for (int j = 0; j < NI; ++j) {
@@ -490,18 +501,18 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16
         for (int e = 0; e < 4; ++e) v[e] = apply_act(acc[i][j][g4 * 4 + e] + bv[e], d.act);
         const bool full = c0 + 3 < d.cout;
         if (a.aux) {
-          bf16_t* ap = a.aux + (long)pix * d.aux_c_total + d.aux_c_offset + c0;
+          T* ap = reinterpret_cast<T*>(a.aux) + (long)pix * d.aux_c_total + d.aux_c_offset + c0;
           if (full) {
-            bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-            *reinterpret_cast<bf16x4*>(ap) = o;
+            X4 o = {narrow<T>(v[0]), narrow<T>(v[1]), narrow<T>(v[2]), narrow<T>(v[3])};
+            *reinterpret_cast<X4*>(ap) = o;
           } else {
-            for (int e = 0; e < 4 && c0 + e < d.cout; ++e) ap[e] = (bf16_t)v[e];
+            for (int e = 0; e < 4 && c0 + e < d.cout; ++e) ap[e] = narrow<T>(v[e]);
           }
         }
         if (a.res) {
-          const bf16_t* rp = a.res + (long)pix * d.res_c_total + d.res_c_offset + c0;
+          const T* rp = reinterpret_cast<const T*>(a.res) + (long)pix * d.res_c_total + d.res_c_offset + c0;
           if (full) {
-            const bf16x4 rv = *reinterpret_cast<const bf16x4*>(rp);
+            const X4 rv = *reinterpret_cast<const X4*>(rp);
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] += (float)rv[e];
           } else {
@@ -521,12 +532,12 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16
               for (int e = 0; e < 4 && c0 + e < d.cout; ++e) yp[e] = v[e];
             }
           } else {
-            bf16_t* yp = reinterpret_cast<bf16_t*>(a.y) + eo;
+            T* yp = reinterpret_cast<T*>(a.y) + eo;
             if (full) {
-              bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-              *reinterpret_cast<bf16x4*>(yp) = o;
+              X4 o = {narrow<T>(v[0]), narrow<T>(v[1]), narrow<T>(v[2]), narrow<T>(v[3])};
+              *reinterpret_cast<X4*>(yp) = o;
             } else {
-              for (int e = 0; e < 4 && c0 + e < d.cout; ++e) yp[e] = (bf16_t)v[e];
+              for (int e = 0; e < 4 && c0 + e < d.cout; ++e) yp[e] = narrow<T>(v[e]);
             }
           }
         }
@@ -537,7 +548,7 @@ __global__ __launch_bounds__(64 * (WAVES_M * WAVES_N + NP)) void conv_igemm_bf16
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int BK, int NS, bool FAST, bool LDS_EPI, bool MFMA16 = false, bool DECODE = false,
-          int NP = 0, bool SPLITK = false>
+          int NP = 0, bool SPLITK = false, typename T = bf16_t>
 int launch_cfg(const ConvArgs& a, hipStream_t s) {
   const int m_tiles = (a.M + BM - 1) / BM;
   ConvArgs b = a;
@@ -545,7 +556,7 @@ int launch_cfg(const ConvArgs& a, hipStream_t s) {
   b.steps = (a.d.ksize * a.d.ksize * a.d.cin + BK - 1) / BK;   // kpad >= steps*BK: the K tail is zero-padded
   const long grid = (long)m_tiles * b.n_tiles;
   if (grid > 0x7fffffffL) return yolo_set_error(YOLO_E_UNSUPPORTED, "conv grid too large");
-  if (pick_only("igemm<%dx%d,%dx%d waves%s,BK%d,%d stages%s%s%s%s> grid %ld", BM, BN, WAVES_M, WAVES_N, NP ? "+4 loaders" : "", BK, NS,
+  if (pick_only("%s<%dx%d,%dx%d waves%s,BK%d,%d stages%s%s%s%s> grid %ld", std::is_same<T, f16_t>::value ? "igemm_f16" : "igemm", BM, BN, WAVES_M, WAVES_N, NP ? "+4 loaders" : "", BK, NS,
                 FAST ? "" : ",generic", MFMA16 ? ",16x16x32" : ",32x32x16", DECODE ? ",decode" : "", SPLITK ? ",splitK" : "", grid))
     return 0;
   unsigned gy = 1;
@@ -554,7 +565,7 @@ int launch_cfg(const ConvArgs& a, hipStream_t s) {
     b.steps /= a.splits;
     gy = (unsigned)a.splits;
   }
-  hipLaunchKernelGGL((conv_igemm_bf16_kernel<BM, BN, WAVES_M, WAVES_N, BK, NS, FAST, LDS_EPI, MFMA16, DECODE, NP, SPLITK>),
+  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WAVES_M, WAVES_N, BK, NS, FAST, LDS_EPI, MFMA16, DECODE, NP, SPLITK, T>),
                      dim3((unsigned)grid, gy), dim3(64 * (WAVES_M * WAVES_N + NP)), 0, s, b);
   return yolo_check_launch("yolo_conv2d_fwd");
 }
@@ -596,7 +607,7 @@ extern "C" int yolo_set_tuning(int knob, int value) {
 
 namespace {
 
-// Every instance of conv_igemm_bf16_kernel in the library: X(id, BM, BN, WAVES_M, WAVES_N, BK, NS, FAST, LDS_EPI, MFMA16, DECODE, NP,
+// Every bf16 instance of conv_igemm_kernel in the library: X(id, BM, BN, WAVES_M, WAVES_N, BK, NS, FAST, LDS_EPI, MFMA16, DECODE, NP,
 // SPLITK).  Names: tile (pixels x couts), then what departs from 4 waves / BK 64 / 2 stages / 16x16x32 MFMA / fast gather / LDS-staged
 // epilogue: _Nw waves, _bk32, _Nst stages, _loaders (+4 loader waves), _m32 (32x32x16 MFMA), _generic (gather for any cin % 8 == 0),
 // _direct (stores from the accumulator registers: f32 output, couts or views the 16-byte epilogue cannot address).
@@ -667,8 +678,8 @@ int launch_igemm(IgemmId id, const ConvArgs& a, hipStream_t s) {
 thread_local int g_launch_cus = 256;   // compute units the coming launches may use (a CU-masked stream: yolo_set_launch_cus)
 
 // Output, residual and pre-add views that the LDS-staged epilogue (16-byte accesses, whole 32-cout slabs) can address
-bool lds_epilogue_views(const YoloConvDesc& d, bool has_res, bool has_aux) {
-  return d.out_dtype == YOLO_DT_BF16 && d.cout % 32 == 0 && d.out_c_offset % 8 == 0 && d.out_c_total % 8 == 0 &&
+bool lds_epilogue_views(const YoloConvDesc& d, bool has_res, bool has_aux, int dt = YOLO_DT_BF16) {
+  return d.out_dtype == dt && d.cout % 32 == 0 && d.out_c_offset % 8 == 0 && d.out_c_total % 8 == 0 &&
          (!has_res || (d.res_c_offset % 8 == 0 && d.res_c_total % 8 == 0)) && (!has_aux || (d.aux_c_offset % 8 == 0 && d.aux_c_total % 8 == 0));
 }
 
@@ -769,6 +780,84 @@ IgemmId choose_igemm(const YoloConvDesc& d, bool has_res, bool has_aux, bool hea
 #undef EPI
 }
 
+// ---- fp16 operands (model.precision = "fp16"): a table of its own, the forms choose_igemm takes by default and no A/B variants ----
+// X(id, ...) as above; names as above.  No split-K, no loader waves (the 3x3 layers of a one-round 128x256 grid run the symmetric
+// 8-wave form), no 32x32x16 twins of the 16x16x32 tiles except as the `_direct` partner.
+#define YOLO_IGEMM_F16_INSTANCES(X)                                                     \
+  X(k64x256_8w_decode, 64, 256, 1, 8, 64, 2, true, false, false, true, 0, false)        \
+  X(k64x256_bk32_decode, 64, 256, 1, 4, 32, 2, true, false, false, true, 0, false)      \
+  X(k64x256_bk32_generic_decode, 64, 256, 1, 4, 32, 2, false, false, false, true, 0, false) \
+  X(k256x32_m32, 256, 32, 4, 1, 32, 2, true, true, false, false, 0, false)              \
+  X(k256x32_m32_direct, 256, 32, 4, 1, 32, 2, true, false, false, false, 0, false)      \
+  X(k256x32_m32_generic, 256, 32, 4, 1, 32, 2, false, true, false, false, 0, false)     \
+  X(k256x32_m32_generic_direct, 256, 32, 4, 1, 32, 2, false, false, false, false, 0, false) \
+  X(k256x64_m32, 256, 64, 4, 1, 32, 2, true, true, false, false, 0, false)              \
+  X(k256x64_m32_direct, 256, 64, 4, 1, 32, 2, true, false, false, false, 0, false)      \
+  X(k256x64_m32_generic, 256, 64, 4, 1, 32, 2, false, true, false, false, 0, false)     \
+  X(k256x64_m32_generic_direct, 256, 64, 4, 1, 32, 2, false, false, false, false, 0, false) \
+  X(k128x128_bk32_3st_m32, 128, 128, 2, 2, 32, 3, true, true, false, false, 0, false)   \
+  X(k128x128_bk32_3st_m32_direct, 128, 128, 2, 2, 32, 3, true, false, false, false, 0, false) \
+  X(k128x128_bk32_3st_m32_generic, 128, 128, 2, 2, 32, 3, false, true, false, false, 0, false) \
+  X(k128x128_bk32_3st_m32_generic_direct, 128, 128, 2, 2, 32, 3, false, false, false, false, 0, false) \
+  X(k64x64_4st, 64, 64, 2, 2, 64, 4, true, true, true, false, 0, false)                 \
+  X(k64x64, 64, 64, 2, 2, 64, 2, true, true, true, false, 0, false)                     \
+  X(k64x64_m32_direct, 64, 64, 2, 2, 64, 2, true, false, false, false, 0, false)        \
+  X(k128x128_8w, 128, 128, 2, 4, 64, 2, true, true, true, false, 0, false)              \
+  X(k128x128_8w_3st, 128, 128, 2, 4, 64, 3, true, true, true, false, 0, false)          \
+  X(k128x128_m32_direct, 128, 128, 2, 2, 64, 2, true, false, false, false, 0, false)    \
+  X(k128x256_8w, 128, 256, 2, 4, 64, 2, true, true, true, false, 0, false)              \
+  X(k128x256_16w_3st, 128, 256, 2, 8, 64, 3, true, true, true, false, 0, false)         \
+  X(k256x128_8w_bk32, 256, 128, 4, 2, 32, 2, true, true, true, false, 0, false)         \
+  X(k256x128_8w_bk32_m32_direct, 256, 128, 4, 2, 32, 2, true, false, false, false, 0, false) \
+  X(k256x256_16w, 256, 256, 4, 4, 64, 2, true, true, true, false, 0, false)             \
+  X(k256x256_8w_m32_direct, 256, 256, 4, 2, 64, 2, true, false, false, false, 0, false)
+
+enum class IgemmF16Id {
+#define X(id, ...) id,
+  YOLO_IGEMM_F16_INSTANCES(X)
+#undef X
+};
+
+int launch_igemm_f16(IgemmF16Id id, const ConvArgs& a, hipStream_t s) {
+  switch (id) {
+#define X(id, ...) \
+  case IgemmF16Id::id: return launch_cfg<__VA_ARGS__, f16_t>(a, s);
+    YOLO_IGEMM_F16_INSTANCES(X)
+#undef X
+  }
+  return yolo_set_error(YOLO_E_UNSUPPORTED, "conv: unknown fp16 kernel instance %d", (int)id);
+}
+
+// choose_igemm for fp16 operands: the same shape rules (and their measurements) with the tuning word at its defaults.  No side
+// effects.  `epi`: the LDS-staged epilogue can address the views (fp16 output, whole 32-cout slabs, 8-channel-aligned views).
+IgemmF16Id choose_igemm_f16(const YoloConvDesc& d, bool has_res, bool has_aux, bool head, int n_cu) {
+  using I = IgemmF16Id;
+  if (head) {
+    if (d.cin % 64 == 0) return I::k64x256_8w_decode;
+    return d.cin % 32 == 0 ? I::k64x256_bk32_decode : I::k64x256_bk32_generic_decode;
+  }
+  const long M = (long)d.n * d.ho * d.wo;
+  const bool one_tap = d.ksize == 1 && d.cin % 8 == 0;
+  const bool fast64 = d.cin % 64 == 0, fast32 = d.cin % 32 == 0 || one_tap;
+  const bool epi = lds_epilogue_views(d, has_res, has_aux, YOLO_DT_F16);
+#define EPI(id) (epi ? I::id : I::id##_direct)
+  if (d.cout <= 32) return fast32 ? EPI(k256x32_m32) : EPI(k256x32_m32_generic);
+  if (few_pixels_64_couts(d, M, n_cu) && epi) return I::k64x64_4st;
+  if (d.cout <= 64) return fast32 ? EPI(k256x64_m32) : EPI(k256x64_m32_generic);
+  if (!fast64) return fast32 ? EPI(k128x128_bk32_3st_m32) : EPI(k128x128_bk32_3st_m32_generic);
+#undef EPI
+  const long tiles128 = ((M + 127) / 128) * ((d.cout + 127) / 128);
+  if (d.ksize == 1 && tiles128 < n_cu) {     // tiny grids
+    if (!epi) return I::k64x64_m32_direct;
+    return tiles128 >= 64 ? I::k128x128_8w_3st : I::k64x64;
+  }
+  if (d.ksize == 1 && d.cin <= 512 && M >= 40000) return epi ? I::k256x128_8w_bk32 : I::k256x128_8w_bk32_m32_direct;   // short-K 1x1, big maps
+  if (fills_256x256(d, M, n_cu)) return epi ? I::k256x256_16w : I::k256x256_8w_m32_direct;
+  if (!epi) return I::k128x128_m32_direct;
+  if (one_round_128x256(d, M, n_cu)) return d.ksize == 1 ? I::k128x256_16w_3st : I::k128x256_8w;
+  return I::k128x128_8w;
+}
+
 // split-K request of a yolo_conv2d_splitk_fwd call
 struct SplitK {
   int splits = 1;
@@ -777,7 +866,7 @@ struct SplitK {
 };
 
 int conv2d_launch_ex(const void* x, const void* w, const float* bias, const void* res, void* y, void* y_aux, const YoloConvDesc* dp,
-                     const HeadDecodeArgs* hd, const SplitK& sk, hipStream_t s) {
+                     const HeadDecodeArgs* hd, const SplitK& sk, hipStream_t s, int dt = YOLO_DT_BF16) {
   YOLO_REQUIRE(x && w && bias && (y || hd) && dp, "conv: null pointer");
   const YoloConvDesc& d = *dp;
   YOLO_REQUIRE(d.ksize == 1 || d.ksize == 3, "conv: ksize %d unsupported (1 or 3)", d.ksize);
@@ -810,6 +899,14 @@ int conv2d_launch_ex(const void* x, const void* w, const float* bias, const void
   a.cnt = sk.cnt;
   YOLO_SET_STAMPS(a);
   if (hd) a.hd = *hd;
+  if (dt == YOLO_DT_F16) {
+    // fp16 operands: the gather kernel only.  The t20 / stream / halo families (and the stem, the fused units, conv_small, mbconv)
+    // hold bf16 in asm or registers and never see an fp16 launch; the tuning word does not apply either.
+    YOLO_REQUIRE(d.out_dtype == YOLO_DT_F16 || d.out_dtype == YOLO_DT_F32, "conv_f16: out_dtype %d (YOLO_DT_F16 or YOLO_DT_F32)", d.out_dtype);
+    YOLO_REQUIRE(a.splits <= 1, "conv_f16: no split-K form");
+    a.debug = 0;
+    return launch_igemm_f16(choose_igemm_f16(d, res != nullptr, y_aux != nullptr, hd != nullptr, g_launch_cus), a, s);
+  }
   // the other kernel families, each on the layers it takes (1 = not this one); never with a forced variant, a head or, the first
   // two, a split-K request
   const bool others = !hd && t.variant < 0 && std_out && lds_epilogue_views(d, res != nullptr, y_aux != nullptr) && !(t.conv_debug & kCdNoLdsEpilogue);
@@ -911,16 +1008,30 @@ extern "C" int yolo_conv1_pool_nchw_f32_fwd(const float* x_nchw, int cin_real, c
 
 // Which kernel instance and grid yolo_conv2d_fwd would launch for this layer (no launch, no GPU): the regression guard of the
 // tile rules (tests/test_host_cpu.py pins the BASELINE shapes).
-extern "C" int yolo_conv2d_pick(const YoloConvDesc* d, int has_residual, int has_preadd, char* out, int out_len) {
+static int conv2d_pick(const YoloConvDesc* d, int has_residual, int has_preadd, char* out, int out_len, int dt) {
   YOLO_REQUIRE(d && out && out_len > 0, "conv2d_pick: bad arguments");
   out[0] = 0;
   yolo_conv::g_pick = out;
   yolo_conv::g_pick_len = out_len;
   static const char dummy[16] = {0};
-  const int rc = yolo_conv2d_launch(dummy, dummy, (const float*)dummy, has_residual ? dummy : nullptr, (void*)dummy,
-                                    has_preadd ? (void*)dummy : nullptr, d, nullptr);
+  const int rc = conv2d_launch_ex(dummy, dummy, (const float*)dummy, has_residual ? dummy : nullptr, (void*)dummy,
+                                  has_preadd ? (void*)dummy : nullptr, d, nullptr, SplitK(), nullptr, dt);
   yolo_conv::g_pick = nullptr;
   return rc;
+}
+extern "C" int yolo_conv2d_pick(const YoloConvDesc* d, int has_residual, int has_preadd, char* out, int out_len) {
+  return conv2d_pick(d, has_residual, has_preadd, out, out_len, YOLO_DT_BF16);
+}
+// ... and the instance of the fp16 table yolo_conv2d_f16_fwd would launch ("igemm_f16<...> grid N")
+extern "C" int yolo_conv2d_f16_pick(const YoloConvDesc* d, int has_residual, int has_preadd, char* out, int out_len) {
+  return conv2d_pick(d, has_residual, has_preadd, out, out_len, YOLO_DT_F16);
+}
+
+// fp16 operands (model.precision = "fp16"): x / residual / y / y_preadd are IEEE-half NHWC views, w_packed comes from
+// yolo_pack_conv_weight_f32_f16; d->out_dtype is YOLO_DT_F16 or YOLO_DT_F32.  Always an instance of the gather kernel.
+extern "C" int yolo_conv2d_f16_fwd(const void* x, const void* w_packed, const float* bias, const void* residual, void* y,
+                                   void* y_preadd, const YoloConvDesc* d, yolo_stream_t s) {
+  return conv2d_launch_ex(x, w_packed, bias, residual, y, y_preadd, d, nullptr, SplitK(), (hipStream_t)s, YOLO_DT_F16);
 }
 
 extern "C" int yolo_conv2d_fwd(const void* x, const void* w_packed, const float* bias, const void* residual, void* y,
@@ -972,14 +1083,13 @@ extern "C" int yolo_conv2d_splitk_fwd(const void* x, const void* w_packed, const
   return conv2d_launch_ex(x, w_packed, bias, residual, y, y_preadd, d, nullptr, SplitK{splits, (float*)workspace, counters}, (hipStream_t)s);
 }
 
-// Head conv + decode in one launch (see the DECODE epilogue of conv_igemm_bf16_kernel).
+// Head conv + decode in one launch (see the DECODE epilogue of conv_igemm_kernel).
 extern "C" int yolo_head_decode_supported(int cout, int na, int nc) {
   return na >= 1 && na <= 4 && nc >= 1 && cout == na * (5 + nc) && cout <= 256 && 5 + nc <= 128;
 }
 
-extern "C" int yolo_head_decode_fwd(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* dp,
-                                    const float* anchors_px, int na, int nc, float stride_px, float* io, int io_rows_total,
-                                    int io_row_offset, float* p, yolo_stream_t s) {
+static int head_decode(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* dp, const float* anchors_px, int na,
+                       int nc, float stride_px, float* io, int io_rows_total, int io_row_offset, float* p, yolo_stream_t s, int dt) {
   YOLO_REQUIRE(dp && anchors_px && io, "head_decode: null pointer");
   const YoloConvDesc& d = *dp;
   YOLO_REQUIRE(yolo_head_decode_supported(d.cout, na, nc), "head_decode: cout %d != na*(5+nc) = %d*%d or out of range", d.cout, na,
@@ -989,12 +1099,22 @@ extern "C" int yolo_head_decode_fwd(const void* x, const void* w_packed, const f
   YOLO_REQUIRE(stride_px > 0.f, "head_decode: bad stride");
   const HeadDecodeArgs h = make_head_args(io, p, na, nc, io_rows_total, io_row_offset, stride_px, anchors_px);
   const YoloConvDesc dd = head_desc(d);
-  return conv2d_launch_ex(x, w_packed, bias, nullptr, nullptr, nullptr, &dd, &h, SplitK(), (hipStream_t)s);
+  return conv2d_launch_ex(x, w_packed, bias, nullptr, nullptr, nullptr, &dd, &h, SplitK(), (hipStream_t)s, dt);
+}
+extern "C" int yolo_head_decode_fwd(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* dp,
+                                    const float* anchors_px, int na, int nc, float stride_px, float* io, int io_rows_total,
+                                    int io_row_offset, float* p, yolo_stream_t s) {
+  return head_decode(x, w_packed, bias, dp, anchors_px, na, nc, stride_px, io, io_rows_total, io_row_offset, p, s, YOLO_DT_BF16);
+}
+extern "C" int yolo_head_decode_f16_fwd(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* dp,
+                                        const float* anchors_px, int na, int nc, float stride_px, float* io, int io_rows_total,
+                                        int io_row_offset, float* p, yolo_stream_t s) {
+  return head_decode(x, w_packed, bias, dp, anchors_px, na, nc, stride_px, io, io_rows_total, io_row_offset, p, s, YOLO_DT_F16);
 }
 
 // Which kernel instance and grid a head op would launch (no launch, no GPU): yolo_conv2d_pick for yolo_head_decode_fwd (filter == 0,
 // with io) / yolo_head_decode_filter_fwd (filter != 0: the compact NMS form without p).
-extern "C" int yolo_head_decode_pick(const YoloConvDesc* dp, int na, int nc, int filter, char* out, int out_len) {
+static int head_decode_pick(const YoloConvDesc* dp, int na, int nc, int filter, char* out, int out_len, int dt) {
   YOLO_REQUIRE(dp && out && out_len > 0, "head_decode_pick: bad arguments");
   YOLO_REQUIRE(yolo_head_decode_supported(dp->cout, na, nc), "head_decode_pick: cout %d != na*(5+nc)", dp->cout);
   out[0] = 0;
@@ -1006,16 +1126,21 @@ extern "C" int yolo_head_decode_pick(const YoloConvDesc* dp, int na, int nc, int
   const YoloConvDesc dd = head_desc(*dp);
   yolo_conv::g_pick = out;
   yolo_conv::g_pick_len = out_len;
-  const int rc = conv2d_launch_ex(dummy, dummy, dummy, nullptr, nullptr, nullptr, &dd, &h, SplitK(), nullptr);
+  const int rc = conv2d_launch_ex(dummy, dummy, dummy, nullptr, nullptr, nullptr, &dd, &h, SplitK(), nullptr, dt);
   yolo_conv::g_pick = nullptr;
   return rc;
 }
+extern "C" int yolo_head_decode_pick(const YoloConvDesc* dp, int na, int nc, int filter, char* out, int out_len) {
+  return head_decode_pick(dp, na, nc, filter, out, out_len, YOLO_DT_BF16);
+}
+extern "C" int yolo_head_decode_f16_pick(const YoloConvDesc* dp, int na, int nc, int filter, char* out, int out_len) {
+  return head_decode_pick(dp, na, nc, filter, out, out_len, YOLO_DT_F16);
+}
 
 // Head conv + decode + the NMS row filter in one launch: io is never written (include/yolo_hip.h, the compact NMS form).
-extern "C" int yolo_head_decode_filter_fwd(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* dp,
-                                           const float* anchors_px, int na, int nc, float stride_px, int io_rows_total,
-                                           int io_row_offset, float conf_thres, float min_wh, void* workspace,
-                                           size_t workspace_bytes, float* p, yolo_stream_t s) {
+static int head_decode_filter(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* dp, const float* anchors_px,
+                              int na, int nc, float stride_px, int io_rows_total, int io_row_offset, float conf_thres, float min_wh,
+                              void* workspace, size_t workspace_bytes, float* p, yolo_stream_t s, int dt) {
   YOLO_REQUIRE(dp && anchors_px && workspace, "head_decode_filter: null pointer");
   const YoloConvDesc& d = *dp;
   YOLO_REQUIRE(yolo_head_decode_supported(d.cout, na, nc), "head_decode_filter: cout %d != na*(5+nc) = %d*%d or out of range", d.cout,
@@ -1035,7 +1160,21 @@ extern "C" int yolo_head_decode_filter_fwd(const void* x, const void* w_packed, 
   h.conf_thres = conf_thres;
   h.min_wh = min_wh;
   const YoloConvDesc dd = head_desc(d);
-  return conv2d_launch_ex(x, w_packed, bias, nullptr, nullptr, nullptr, &dd, &h, SplitK(), (hipStream_t)s);
+  return conv2d_launch_ex(x, w_packed, bias, nullptr, nullptr, nullptr, &dd, &h, SplitK(), (hipStream_t)s, dt);
+}
+extern "C" int yolo_head_decode_filter_fwd(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* dp,
+                                           const float* anchors_px, int na, int nc, float stride_px, int io_rows_total,
+                                           int io_row_offset, float conf_thres, float min_wh, void* workspace,
+                                           size_t workspace_bytes, float* p, yolo_stream_t s) {
+  return head_decode_filter(x, w_packed, bias, dp, anchors_px, na, nc, stride_px, io_rows_total, io_row_offset, conf_thres, min_wh,
+                            workspace, workspace_bytes, p, s, YOLO_DT_BF16);
+}
+extern "C" int yolo_head_decode_filter_f16_fwd(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* dp,
+                                               const float* anchors_px, int na, int nc, float stride_px, int io_rows_total,
+                                               int io_row_offset, float conf_thres, float min_wh, void* workspace,
+                                               size_t workspace_bytes, float* p, yolo_stream_t s) {
+  return head_decode_filter(x, w_packed, bias, dp, anchors_px, na, nc, stride_px, io_rows_total, io_row_offset, conf_thres, min_wh,
+                            workspace, workspace_bytes, p, s, YOLO_DT_F16);
 }
 
 // Host-side weight packer: OIHW f32 -> [cout_pad][kpad] bf16, k = (kh*ks+kw)*cin + c, zero padded.
@@ -1055,5 +1194,38 @@ extern "C" int yolo_pack_conv_weight_f32(const float* w, int cout, int cin_w, in
     for (int c = 0; c < cin_w; ++c)
       for (int t = 0; t < ksize * ksize; ++t)
         out[(size_t)o * kpad + (size_t)t * cin + c] = f32_to_bf16_rne(w[((size_t)o * cin_w + c) * ksize * ksize + t]);
+  return 0;
+}
+
+// fp16 twin: OIHW f32 -> [cout_pad][kpad] IEEE half, same k order; round to nearest even, a finite value beyond +-65504 packs to
+// +-65504 (the kernels' narrowing rule), NaN and +-inf stay.
+static inline uint16_t f32_to_f16_rne(float f) {
+  uint32_t u;
+  __builtin_memcpy(&u, &f, 4);
+  const uint32_t sign = (u >> 16) & 0x8000u;
+  u &= 0x7fffffffu;
+  if (u > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);                  // NaN stays NaN
+  if (u == 0x7f800000u) return (uint16_t)(sign | 0x7c00u);                 // inf stays inf
+  if (u > 0x477fe000u) return (uint16_t)(sign | 0x7bffu);                  // finite beyond 65504: clamp
+  if (u < (113u << 23)) {                                                  // below 2^-14: a half subnormal (or zero)
+    float a;
+    __builtin_memcpy(&a, &u, 4);
+    a += 0.5f;                                                             // aligns the ulp to 2^-24: the FPU rounds to nearest even
+    __builtin_memcpy(&u, &a, 4);
+    return (uint16_t)(sign | (u - 0x3f000000u));
+  }
+  u += ((uint32_t)(15 - 127) << 23) + 0xfffu + ((u >> 13) & 1u);
+  return (uint16_t)(sign | (u >> 13));
+}
+
+extern "C" int yolo_pack_conv_weight_f32_f16(const float* w, int cout, int cin_w, int ksize, int cin, int cout_pad, int kpad,
+                                             uint16_t* out) {
+  YOLO_REQUIRE(w && out, "pack: null pointer");
+  YOLO_REQUIRE(cin_w <= cin && cout <= cout_pad && ksize * ksize * cin <= kpad, "pack: bad sizes");
+  for (size_t i = 0; i < (size_t)cout_pad * kpad; ++i) out[i] = 0;
+  for (int o = 0; o < cout; ++o)
+    for (int c = 0; c < cin_w; ++c)
+      for (int t = 0; t < ksize * ksize; ++t)
+        out[(size_t)o * kpad + (size_t)t * cin + c] = f32_to_f16_rne(w[((size_t)o * cin_w + c) * ksize * ksize + t]);
   return 0;
 }

@@ -2,22 +2,37 @@
 // depthwise 3x3, YOLO-layer decode.  All are coalesced 16-byte-per-lane streams over NHWC data.
 #include "common.h"
 
+#include <type_traits>
+
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// NCHW f32 -> NHWC bf16, channels padded with zeros (first-layer layout).
-__global__ __launch_bounds__(256) void pack_input_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, int c,
+// fp32 -> IEEE half as the conv epilogues narrow (conv_common.h narrow<f16_t>): RNE, finite overflow clamps to +-65504
+__device__ __forceinline__ f16_t to_f16(float v) {
+  const float m = __builtin_fabsf(v);
+  if (m > 65504.f && m < __builtin_inff()) v = __builtin_copysignf(65504.f, v);
+  return (f16_t)v;
+}
+template <typename T>
+__device__ __forceinline__ T to_elem(float v) {
+  if constexpr (std::is_same<T, f16_t>::value) return to_f16(v);
+  else return (T)v;
+}
+
+// NCHW f32 -> NHWC bf16 / fp16 (T), channels padded with zeros (first-layer layout).
+template <typename T, typename X8>
+__global__ __launch_bounds__(256) void pack_input_kernel(const float* __restrict__ x, T* __restrict__ y, int c,
                                                          long hw, long total_pix, int c_pad) {
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
   if (p >= total_pix) return;
   const long b = p / hw, sp = p - b * hw;
   const float* src = x + b * c * hw + sp;
-  bf16_t* dst = y + p * c_pad;
+  T* dst = y + p * c_pad;
   for (int c0 = 0; c0 < c_pad; c0 += 8) {
-    bf16x8 o;
+    X8 o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = (bf16_t)((c0 + e < c) ? src[(long)(c0 + e) * hw] : 0.f);
-    *reinterpret_cast<bf16x8*>(dst + c0) = o;
+    for (int e = 0; e < 8; ++e) o[e] = to_elem<T>((c0 + e < c) ? src[(long)(c0 + e) * hw] : 0.f);
+    *reinterpret_cast<X8*>(dst + c0) = o;
   }
 }
 
@@ -37,7 +52,27 @@ __device__ __forceinline__ u32x4 pack8(const float (&m)[8]) {
   return o;
 }
 
+// ... and for IEEE half, which widens by a real convert (exact) and narrows back exactly: the maximum IS one of the inputs
+struct PoolBf16 {
+  static __device__ __forceinline__ void max8(float (&m)[8], const u32x4 v) { ::max8(m, v); }
+  static __device__ __forceinline__ u32x4 pack8(const float (&m)[8]) { return ::pack8(m); }
+};
+struct PoolF16 {
+  static __device__ __forceinline__ void max8(float (&m)[8], const u32x4 v) {
+    const f16x8 h = __builtin_bit_cast(f16x8, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], (float)h[e]);
+  }
+  static __device__ __forceinline__ u32x4 pack8(const float (&m)[8]) {
+    f16x8 h;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) h[e] = (f16_t)m[e];
+    return __builtin_bit_cast(u32x4, h);
+  }
+};
+
 // Generic max pool, -inf padding (nn.MaxPool2d semantics), one thread = 8 channels of one output pixel.
+template <typename P>
 __global__ __launch_bounds__(256) void maxpool_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int h, int w,
                                                       int cg, int in_ct, int in_co, int ho, int wo, int out_ct, int out_co,
                                                       int k, int stride, int pad, int dil, long total) {
@@ -58,17 +93,18 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const bf16_t* __restrict__
     for (int j = 0; j < k; ++j) {
       const int wi = ow * stride - pad + j * dil;
       if ((unsigned)wi >= (unsigned)w) continue;
-      max8(m, *reinterpret_cast<const u32x4*>(x + ((b * h + hi) * w + wi) * in_ct + in_co + g * 8));
+      P::max8(m, *reinterpret_cast<const u32x4*>(x + ((b * h + hi) * w + wi) * in_ct + in_co + g * 8));
     }
   }
-  *reinterpret_cast<u32x4*>(y + ((b * ho + oh) * wo + ow) * out_ct + out_co + g * 8) = pack8(m);
+  *reinterpret_cast<u32x4*>(y + ((b * ho + oh) * wo + ow) * out_ct + out_co + g * 8) = P::pack8(m);
 }
 
 // SPP pyramid: one block = one image x 8 channels; the hxw plane lives in LDS; separable running max
 // (rows then columns) gives 5/9/13 windows in one pass.  Reads slice [3c,4c) of the concat buffer,
 // writes slices [0,c) [c,2c) [2c,3c).
 // bf16 pairs as order-preserving int16 pairs (x ^ 0x7fff for negative halves; an involution): the 5/9/13 window maxima
-// then cost ONE v_pk_max_i16 per 32-bit word and tap instead of unpack + two fmax
+// then cost ONE v_pk_max_i16 per 32-bit word and tap instead of unpack + two fmax.  The map orders ANY 16-bit sign-magnitude
+// pattern, so the two SPP kernels serve IEEE-half buffers (model.precision = "fp16") unchanged.
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ u32x4 bf16_sortable(u32x4 v) {
   return v ^ (((v >> 15) & 0x00010001u) * 0x7fffu);
@@ -265,14 +301,23 @@ extern "C" int yolo_pack_input_nchw_f32(const float* x, void* y, int n, int c, i
   YOLO_REQUIRE(x && y && n > 0 && c > 0 && h > 0 && w > 0, "pack_input: bad arguments");
   YOLO_REQUIRE(c_pad % 8 == 0 && c_pad >= c, "pack_input: c_pad %d must be a multiple of 8 and >= c %d", c_pad, c);
   const long total = (long)n * h * w;
-  hipLaunchKernelGGL(pack_input_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, x, (bf16_t*)y, c,
+  hipLaunchKernelGGL((pack_input_kernel<bf16_t, bf16x8>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, x, (bf16_t*)y, c,
                      (long)h * w, total, c_pad);
   return yolo_check_launch("yolo_pack_input_nchw_f32");
 }
 
-extern "C" int yolo_maxpool_fwd(const void* x, void* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho,
-                                int wo, int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation,
-                                yolo_stream_t s) {
+extern "C" int yolo_pack_input_nchw_f32_f16(const float* x, void* y, int n, int c, int h, int w, int c_pad, yolo_stream_t s) {
+  YOLO_REQUIRE(x && y && n > 0 && c > 0 && h > 0 && w > 0, "pack_input_f16: bad arguments");
+  YOLO_REQUIRE(c_pad % 8 == 0 && c_pad >= c, "pack_input_f16: c_pad %d must be a multiple of 8 and >= c %d", c_pad, c);
+  const long total = (long)n * h * w;
+  hipLaunchKernelGGL((pack_input_kernel<f16_t, f16x8>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, x, (f16_t*)y, c,
+                     (long)h * w, total, c_pad);
+  return yolo_check_launch("yolo_pack_input_nchw_f32_f16");
+}
+
+template <typename P>
+static int maxpool16(const void* x, void* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho, int wo,
+                     int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation, yolo_stream_t s) {
   YOLO_REQUIRE(x && y && n > 0 && c > 0 && c % 8 == 0, "maxpool: bad arguments (c %d must be a multiple of 8)", c);
   YOLO_REQUIRE(in_c_total % 8 == 0 && in_c_offset % 8 == 0 && out_c_total % 8 == 0 && out_c_offset % 8 == 0,
                "maxpool: views must be 8-channel aligned");
@@ -283,9 +328,21 @@ extern "C" int yolo_maxpool_fwd(const void* x, void* y, int n, int h, int w, int
   YOLO_REQUIRE((ho == hf || (ho == hf + 1 && (ho - 1) * stride < h + pad)) && (wo == wf || (wo == wf + 1 && (wo - 1) * stride < w + pad)),
                "maxpool: output %dx%d inconsistent with %dx%d k%d s%d p%d d%d", ho, wo, h, w, ksize, stride, pad, dilation);
   const long total = (long)n * ho * wo * (c / 8);
-  hipLaunchKernelGGL(maxpool_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (bf16_t*)y, h,
+  hipLaunchKernelGGL(maxpool_kernel<P>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (bf16_t*)y, h,
                      w, c / 8, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, total);
   return yolo_check_launch("yolo_maxpool_fwd");
+}
+
+extern "C" int yolo_maxpool_fwd(const void* x, void* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho,
+                                int wo, int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation,
+                                yolo_stream_t s) {
+  return maxpool16<PoolBf16>(x, y, n, h, w, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, s);
+}
+// IEEE-half NHWC views (the 16-bit pointers are passed as bytes: same size and alignment)
+extern "C" int yolo_maxpool_f16_fwd(const void* x, void* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho,
+                                    int wo, int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation,
+                                    yolo_stream_t s) {
+  return maxpool16<PoolF16>(x, y, n, h, w, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, s);
 }
 
 // channel_shuffle(cat(a, b), 2) in the two-slot layout (see include/yolo_hip.h): thread = 8 physical output channels of a pixel

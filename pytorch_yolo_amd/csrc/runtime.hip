@@ -107,6 +107,23 @@ extern "C" int yolo_run_ops(const YoloOp* ops, int n_ops, yolo_stream_t s) {
         rc = yolo_maxpool_f32_fwd((const float*)o.x, (float*)o.y, d.n, d.h, d.w, d.cin, d.in_c_total, d.in_c_offset, d.ho, d.wo,
                                   d.out_c_total, d.out_c_offset, d.ksize, d.stride, d.pad, d.upsample2x /* dilation */, s);
         break;
+      case YOLO_OP_CONV_F16:
+        rc = yolo_conv2d_f16_fwd(o.x, o.w, o.bias, o.residual, o.y, o.y_aux, &d, s);
+        break;
+      case YOLO_OP_MAXPOOL_F16:
+        rc = yolo_maxpool_f16_fwd(o.x, o.y, d.n, d.h, d.w, d.cin, d.in_c_total, d.in_c_offset, d.ho, d.wo, d.out_c_total, d.out_c_offset,
+                                  d.ksize, d.stride, d.pad, d.upsample2x /* dilation */, s);
+        break;
+      case YOLO_OP_HEAD_DECODE_F16:
+        if (!o.y && o.workspace) {
+          rc = yolo_head_decode_filter_f16_fwd(o.x, o.w, o.bias, &d, o.head_anchors_px, o.head_na, o.head_nc, o.head_stride_px,
+                                               o.io_rows_total, o.io_row_offset, o.head_filter_conf, o.head_filter_min_wh, o.workspace,
+                                               o.ws_bytes, (float*)o.y_aux, s);
+          break;
+        }
+        rc = yolo_head_decode_f16_fwd(o.x, o.w, o.bias, &d, o.head_anchors_px, o.head_na, o.head_nc, o.head_stride_px, (float*)o.y,
+                                      o.io_rows_total, o.io_row_offset, (float*)o.y_aux, s);
+        break;
       case YOLO_OP_CONV_POOL:
         rc = yolo_conv3x3_pool_fwd(o.x, o.w, o.bias, o.y, &d, 1, s);
         break;

@@ -76,7 +76,7 @@ class GuardedAlloc:
 def rewrite_list(plan, ops, op_launches):
     """The two list rewrites, on the emitted bf16 list (``op_launches``: the Launch record of each op); sets
     ``plan.depth_first`` and ``plan._x_patch``."""
-    if plan.f32:
+    if plan.f32 or plan.f16:
         return ops, op_launches
     _shrink(plan, ops)
     return _depth_first(plan, ops, op_launches)

@@ -2,8 +2,9 @@
 accounting over such an array.
 
 One emitter per launch kind (``EMITTERS``), each returning the op(s) of one launch; ``build_ops`` is the loop over the records
-for both precisions (fp32: the same conv emitter with the fp32 packing and op kind, max pools instead of the SPP kernel, no
-kernel for the depthwise / SE / shuffle layers)."""
+for every precision (fp32: the same conv emitter with the fp32 packing and op kind, max pools instead of the SPP kernel, no
+kernel for the depthwise / SE / shuffle layers; fp16: the fp16 packing and op kinds, the SPP kernel itself - it orders 16-bit
+patterns -, no kernel for those three layer kinds either)."""
 from __future__ import annotations
 
 import os
@@ -12,9 +13,9 @@ import torch
 
 from . import diag
 from . import kernels as K
-from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, DT_BF16, DT_F32, OP_SE, OP_CONV, OP_CONV1_NCHW, OP_CONV_F32, OP_DWCONV,
-                   OP_CONV1_POOL, OP_CONV_POOL, OP_MAXPOOL_F32, OP_MBCONV, OP_SHUFFLE, OP_HEAD_DECODE, OP_MAXPOOL, OP_RESUNIT, OP_SPP,
-                   OP_STEM, YoloOp)
+from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, DT_BF16, DT_F16, DT_F32, OP_SE, OP_CONV, OP_CONV1_NCHW, OP_CONV_F16,
+                   OP_CONV_F32, OP_DWCONV, OP_CONV1_POOL, OP_CONV_POOL, OP_HEAD_DECODE_F16, OP_MAXPOOL_F16, OP_MAXPOOL_F32, OP_MBCONV,
+                   OP_SHUFFLE, OP_HEAD_DECODE, OP_MAXPOOL, OP_RESUNIT, OP_SPP, OP_STEM, YoloOp)
 
 _ACT = {"leaky": ACT_LEAKY01, "relu6": ACT_RELU6, "relu": ACT_RELU, "none": ACT_NONE, "swish": ACT_SWISH}
 
@@ -67,8 +68,8 @@ def _emit_head(plan, L):
     nd, x = L.node, L.src
     hd = next(h for h in plan.heads if h["sym"] is nd.outs[0])
     w, b = nd.attrs["weight"]
-    wp, bp, kpad, cout_pad = K.pack_conv_weight(w, b, x.c)
-    op = _op(OP_HEAD_DECODE, x=_ptr(x), y=None, y_aux=None)                     # io / p of the call: bound in _bind_outputs
+    wp, bp, kpad, cout_pad = (K.pack_conv_weight_f16 if plan.f16 else K.pack_conv_weight)(w, b, x.c)
+    op = _op(OP_HEAD_DECODE_F16 if plan.f16 else OP_HEAD_DECODE, x=_ptr(x), y=None, y_aux=None)                     # io / p of the call: bound in _bind_outputs
     op.w, op.bias = _keep(plan, wp, bp)
     op.conv = K.conv_desc(n=x.n, h=x.h, w=x.w, cin=x.c, in_c_total=x.buf.c_total, in_c_offset=x.c_offset,
                           cout=w.shape[0], out_c_total=K.roundup(w.shape[0], 8), out_c_offset=0,
@@ -116,6 +117,8 @@ def _emit_conv(plan, L):
     y = nd.outs[0]
     w, b = nd.attrs["weight"]
     pack, plain = (K.pack_conv_weight_f32, OP_CONV_F32) if plan.f32 else (K.pack_conv_weight, OP_CONV)
+    if plan.f16:
+        pack, plain = K.pack_conv_weight_f16, OP_CONV_F16
     wp, bp, kpad, cout_pad = pack(w, b, x.c)
     res = nd.srcs[1] if nd.attrs["has_res"] else None
     aux = nd.outs[1] if len(nd.outs) > 1 else None
@@ -123,7 +126,7 @@ def _emit_conv(plan, L):
                     cout=w.shape[0], out_c_total=dst.buf.c_total, out_c_offset=dst.c_offset,
                     ksize=w.shape[2], stride=nd.attrs["stride"], act=_ACT[nd.attrs["act"]],
                     kpad=kpad, cout_pad=cout_pad, upsample2x=1 if L.up else 0,
-                    out_dtype=DT_F32 if (plan.f32 or y.f32) else DT_BF16, pad=nd.attrs.get("pad"),
+                    out_dtype=DT_F32 if (plan.f32 or y.f32) else (DT_F16 if plan.f16 else DT_BF16), pad=nd.attrs.get("pad"),
                     res=_slice_of(res), aux=_slice_of(aux))
     if not L.up and not L.pooled:
         d.ho, d.wo = y.h, y.w                  # (tf_same convs: one more row / column than the symmetric-pad formula)
@@ -197,7 +200,7 @@ def _maxpool(kind, x, y, size, stride, pad, dil, out_c_offset):
 
 def _emit_pool(plan, L):
     a = L.node.attrs
-    return [_maxpool(OP_MAXPOOL_F32 if plan.f32 else OP_MAXPOOL, L.src, L.dst, a["size"], a["stride"], a["pad"], a["dil"], L.dst.c_offset)]
+    return [_maxpool(OP_MAXPOOL_F32 if plan.f32 else (OP_MAXPOOL_F16 if plan.f16 else OP_MAXPOOL), L.src, L.dst, a["size"], a["stride"], a["pad"], a["dil"], L.dst.c_offset)]
 
 
 def _emit_spp(plan, L):
@@ -227,9 +230,9 @@ def build_ops(plan):
     plan.rows_total = row
     ops, op_launches = [], []
     for L in plan.launches:
-        if plan.f32 and L.kind in ("dwconv", "shuffle", "se"):
-            raise NotImplementedError("precision='fp32' covers the Darknet families (YOLOv3-SPP / -tiny / YOLOv3 / Lite); "
-                                      f"no fp32 kernel for '{L.kind}' layers")
+        if (plan.f32 or plan.f16) and L.kind in ("dwconv", "shuffle", "se"):
+            raise NotImplementedError(f"precision='{plan.precision}' covers the Darknet families (YOLOv3-SPP / -tiny / YOLOv3 / Lite); "
+                                      f"no {plan.precision} kernel for '{L.kind}' layers")
         assert not (L.reads_nchw and ops)               # feed() patches op 0's x with the caller's batch
         for op in EMITTERS[L.kind](plan, L):
             ops.append(op); op_launches.append(L)
@@ -252,7 +255,7 @@ def build_ops(plan):
 
 
 # -- accounting --------------------------------------------------------------------------------------
-_CONVS = (OP_CONV, OP_CONV1_NCHW, OP_CONV1_POOL, OP_CONV_POOL, OP_HEAD_DECODE, OP_CONV_F32)
+_CONVS = (OP_CONV, OP_CONV1_NCHW, OP_CONV1_POOL, OP_CONV_POOL, OP_HEAD_DECODE, OP_CONV_F32, OP_CONV_F16, OP_HEAD_DECODE_F16)
 
 
 def conv_flops(op_array, n_ops: int, c_in: int) -> float:
@@ -295,8 +298,8 @@ def algorithmic_bytes(op_array, n_ops: int, c_in: int, detect: bool = False) -> 
             x_b = m_in * (c_in * 4 if (first and op.kind in (OP_CONV1_NCHW, OP_CONV1_POOL)) else d.cin * (4 if op.kind == OP_CONV_F32 else 2))
             first = False
             pooled = 4 if op.kind in (OP_CONV1_POOL, OP_CONV_POOL) else 1       # only the 2x2-pooled map is written
-            y_b = m_out * d.cout * (4 if d.out_dtype else 2) * (4 if d.upsample2x else 1) / pooled
-            if op.kind == OP_HEAD_DECODE:
+            y_b = m_out * d.cout * (4 if d.out_dtype == DT_F32 else 2) * (4 if d.upsample2x else 1) / pooled
+            if op.kind in (OP_HEAD_DECODE, OP_HEAD_DECODE_F16):
                 y_b = 2.0 * m_out * d.cout * 4                                   # p (raw) + io (decoded), fp32
                 if detect:
                     y_b = m_out * op.head_na * 8.0                               # one sort key per (pixel, anchor) row
@@ -309,7 +312,7 @@ def algorithmic_bytes(op_array, n_ops: int, c_in: int, detect: bool = False) -> 
             total += m_in * d.cout * 2 * (3 if op.y_aux else 2)
         elif op.kind == OP_MBCONV:
             total += m_in * d.cin * 2 + m_out * d.cout * 2
-        elif op.kind in (OP_MAXPOOL, OP_DWCONV, OP_MAXPOOL_F32):
+        elif op.kind in (OP_MAXPOOL, OP_DWCONV, OP_MAXPOOL_F32, OP_MAXPOOL_F16):
             total += (m_in + m_out) * d.cin * (4 if op.kind == OP_MAXPOOL_F32 else 2)
         elif op.kind == OP_SE:
             total += 3.0 * m_in * d.cin * 2                                      # pooled once, read again for the rescale, written

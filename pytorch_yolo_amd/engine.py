@@ -83,15 +83,18 @@ class _Runs:
 class Plan(GuardedAlloc, _Runs):
     """Buffers + packed weights + launch list for one (batch, H, W) on one device.
 
-    ``precision``: "bf16" (default: bf16 activations / weights, fp32 accumulate, every fusion) or "fp32" (the
+    ``precision``: "bf16" (default: bf16 activations / weights, fp32 accumulate, every fusion), "fp32" (the
     reference-precision parity mode: float32 activations and weights on the f32 MFMA, one plain launch per layer,
-    csrc/conv_f32.hip)."""
+    csrc/conv_f32.hip) or "fp16" (the rounding points of the bf16 mode with IEEE-half activations / weights: three more
+    mantissa bits at the bf16 MFMA rate; one launch of the gather kernel per layer, heads decoded in their conv, the Darknet
+    families only)."""
     n_streams = 1
 
     def __init__(self, rec: Recorder, device, n_class: int, img_size: int, precision: str = "bf16"):
-        if precision not in ("bf16", "fp32"):
-            raise ValueError(f"precision must be 'bf16' or 'fp32', got {precision!r}")
+        if precision not in ("bf16", "fp32", "fp16"):
+            raise ValueError(f"precision must be 'bf16', 'fp32' or 'fp16', got {precision!r}")
         self.f32 = precision == "fp32"
+        self.f16 = precision == "fp16"
         self.precision = precision
         self.device = device
         self.rec = rec
@@ -105,10 +108,10 @@ class Plan(GuardedAlloc, _Runs):
         self._graph = None
         self._static_out = None
         self.depth_first, self._x_patch = [], [(0, 0)]
-        self.launches = planner.fuse(rec, self.f32, n_class)
+        self.launches = planner.fuse(rec, self.f32, n_class, self.f16)
         self.fused_input = any(L.reads_nchw for L in self.launches)
         self._bufs = planner.place(rec, self.launches)
-        self.shared_buffers = planner.alloc(rec, self.launches, self._bufs, self.f32, self._zeros)
+        self.shared_buffers = planner.alloc(rec, self.launches, self._bufs, self.f32, self._zeros, self.f16)
         emit.build_ops(self)            # -> heads, rows_total, op_array, n_ops, op_launches, op_nodes
 
     def set_input_ptr(self, ptr: int):
@@ -123,13 +126,15 @@ class Plan(GuardedAlloc, _Runs):
 
     def feed(self, x: torch.Tensor):
         """Hand the float32 NCHW batch to the layer list: either the first conv reads it directly
-        (pointer patched into its op) or it is packed to NHWC bf16 first."""
+        (pointer patched into its op) or it is packed to NHWC (bf16, fp16 or float32: the plan's precision) first."""
         if self.fused_input:
             if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape[1:]) != (self.rec.c_in, self.rec.input.h, self.rec.input.w):
                 raise RuntimeError("input must be contiguous float32 NCHW of the planned shape")
             self.set_input_ptr(x.data_ptr())
         elif self.f32:
             K.pack_input_f32(x, self.input_buffer)
+        elif self.f16:
+            K.pack_input_f16(x, self.input_buffer)
         else:
             K.pack_input(x, self.input_buffer)
 
@@ -160,7 +165,7 @@ class Plan(GuardedAlloc, _Runs):
 
     @property
     def compact_ok(self) -> bool:
-        """Every head decodes in its conv epilogue (bf16 mode): detect() can take the compact NMS form (no io)."""
+        """Every head decodes in its conv epilogue (bf16 and fp16 modes): detect() can take the compact NMS form (no io)."""
         return not self.f32 and all(hd["op"] is not None for hd in self.heads)
 
     def compact_workspace(self) -> torch.Tensor:
@@ -524,6 +529,8 @@ class StreamedPlan(_Runs):
         as ONE FFI call per batch, or None when this plan cannot take it (a head that decodes in a launch of its own, an input the
         first layer does not read itself: then ``launch_detect`` does the same work)."""
         k = slot % len(self.streams)
+        if not self.subs[0].fused_input:        # (fp32 / fp16 plans pack their input: no whole-batch plans are built for nothing)
+            return None
         pl = self._whole_batch_plans()[k]
         if not pl.fused_input or any(hd["op"] is None for hd in pl.heads) or pl.f32:
             return None

@@ -10,7 +10,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU6, DT_BF16, DT_F32, YoloConvDesc, YoloMbconvDesc,
+from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU6, DT_BF16, DT_F16, DT_F32, YoloConvDesc, YoloMbconvDesc,
                    check, load)
 
 __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pick", "stem", "resunit", "resunit_supported", "resunit_form", "maxpool", "spp", "dwconv3x3", "dwconv", "se", "se_workspace_bytes", "mbconv", "mbconv_supported", "mbconv_form", "pack_mbconv", "conv3x3_pool", "conv3x3_pool_supported", "conv2d_splitk", "conv2d_splitk_plan", "decode", "head_decode", "head_decode_supported",
@@ -63,6 +63,90 @@ def pack_conv_weight_f32(w_oihw: torch.Tensor, bias: torch.Tensor | None, cin: i
     if bias is not None:
         b[:cout] = bias.detach().float().cpu()
     return packed.contiguous(), b, kpad, cout_pad
+
+
+def pack_conv_weight_f16(w_oihw: torch.Tensor, bias: torch.Tensor | None, cin: int):
+    """fp16 mode: OIHW f32 weights (+bias) -> (fp16 [cout_pad, kpad], f32 [cout_pad]) on the host through the library's packer
+    (yolo_pack_conv_weight_f32_f16): sizes and k order of the bf16 form, round to nearest even, finite values beyond +-65504
+    clamped to +-65504."""
+    w = w_oihw.detach().float().cpu().contiguous()
+    cout, cin_w, k, _ = w.shape
+    kpad, cout_pad = roundup(k * k * cin, 64), roundup(cout, 128)
+    packed = torch.empty((cout_pad, kpad), dtype=torch.float16)
+    check(load().yolo_pack_conv_weight_f32_f16(_ptr(w), cout, cin_w, k, cin, cout_pad, kpad, _ptr(packed)), "pack_conv_weight_f16")
+    b = torch.zeros(cout_pad, dtype=torch.float32)
+    if bias is not None:
+        b[:cout] = bias.detach().float().cpu()
+    return packed, b, kpad, cout_pad
+
+
+def pack_input_f16(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """fp16 mode: f32 NCHW -> fp16 NHWC (channels zero-padded to out.shape[-1])."""
+    _need_cuda(x, out)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise RuntimeError("pack_input_f16: x must be contiguous float32 NCHW")
+    n, c, h, w = x.shape
+    if out.dtype != torch.float16 or tuple(out.shape[:3]) != (n, h, w) or not out.is_contiguous():
+        raise RuntimeError("pack_input_f16: out must be contiguous fp16 [n,h,w,c_pad]")
+    check(load().yolo_pack_input_nchw_f32_f16(_ptr(x), _ptr(out), n, c, h, w, out.shape[3], stream_ptr()), "pack_input_f16")
+    return out
+
+
+def conv2d_f16(x, w_packed, bias, y, desc: YoloConvDesc, residual=None, y_preadd=None):
+    """fp16 mode conv (yolo_conv2d_f16_fwd): x / residual / y_preadd / w_packed fp16, y fp16 or (desc.out_dtype = DT_F32) float32."""
+    _need_cuda(x, w_packed, bias, y, residual, y_preadd)
+    for t in (x, w_packed, residual, y_preadd):
+        if t is not None and t.dtype != torch.float16:
+            raise RuntimeError("conv2d_f16: x, w_packed, residual and y_preadd must be float16")
+    if y.dtype != (torch.float32 if desc.out_dtype == DT_F32 else torch.float16):
+        raise RuntimeError("conv2d_f16: y must match desc.out_dtype (DT_F16 or DT_F32)")
+    check(load().yolo_conv2d_f16_fwd(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(residual), _ptr(y), _ptr(y_preadd),
+                                     C.byref(desc), stream_ptr()), "conv2d_f16")
+    return y
+
+
+def conv2d_f16_pick(desc: YoloConvDesc, has_residual=False, has_preadd=False) -> str:
+    """Name + grid of the fp16 instance yolo_conv2d_f16_fwd would launch for ``desc`` (no launch, works without a GPU)."""
+    buf = C.create_string_buffer(256)
+    check(load().yolo_conv2d_f16_pick(C.byref(desc), int(has_residual), int(has_preadd), buf, 256), "conv2d_f16_pick")
+    return buf.value.decode()
+
+
+def head_decode_f16_pick(desc: YoloConvDesc, na: int, nc: int, filter: bool = False) -> str:
+    buf = C.create_string_buffer(256)
+    check(load().yolo_head_decode_f16_pick(C.byref(desc), na, nc, int(filter), buf, 256), "head_decode_f16_pick")
+    return buf.value.decode()
+
+
+def maxpool_f16(x, y, *, n, h, w, c, in_view, out_view, ksize, stride, pad, dilation=1):
+    _need_cuda(x, y)
+    ho = (h + 2 * pad - dilation * (ksize - 1) - 1) // stride + 1
+    wo = (w + 2 * pad - dilation * (ksize - 1) - 1) // stride + 1
+    check(load().yolo_maxpool_f16_fwd(_ptr(x), _ptr(y), n, h, w, c, in_view[0], in_view[1], ho, wo, out_view[0],
+                                      out_view[1], ksize, stride, pad, dilation, stream_ptr()), "maxpool_f16")
+    return y
+
+
+def head_decode_f16(x, w_packed, bias, desc: YoloConvDesc, anchors_px, nc, stride_px, io, io_row_offset, p=None):
+    """fp16 head conv + YOLOLayer decode in one launch (yolo_head_decode_f16_fwd)."""
+    _need_cuda(x, w_packed, bias, io, p)
+    na = len(anchors_px)
+    flat = (C.c_float * (2 * na))(*[float(v) for a in anchors_px for v in a])
+    check(load().yolo_head_decode_f16_fwd(_ptr(x), _ptr(w_packed), _ptr(bias), C.byref(desc), flat, na, nc, float(stride_px),
+                                          _ptr(io), io.shape[1], io_row_offset, _ptr(p), stream_ptr()), "head_decode_f16")
+    return io
+
+
+def head_decode_filter_f16(x, w_packed, bias, desc: YoloConvDesc, anchors_px, nc, stride_px, rows_total, io_row_offset, conf_thres,
+                           workspace, *, min_wh=2.0, p=None):
+    """fp16 head conv + decode + NMS row filter in one launch (yolo_head_decode_filter_f16_fwd)."""
+    _need_cuda(x, w_packed, bias, workspace, p)
+    na = len(anchors_px)
+    flat = (C.c_float * (2 * na))(*[float(v) for a in anchors_px for v in a])
+    check(load().yolo_head_decode_filter_f16_fwd(_ptr(x), _ptr(w_packed), _ptr(bias), C.byref(desc), flat, na, nc, float(stride_px),
+                                                 rows_total, io_row_offset, float(conf_thres), float(min_wh), _ptr(workspace),
+                                                 workspace.numel() * workspace.element_size(), _ptr(p), stream_ptr()),
+          "head_decode_filter_f16")
 
 
 def pack_input_f32(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:

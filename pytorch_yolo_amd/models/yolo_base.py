@@ -129,7 +129,9 @@ class YOLOBase(nn.Module):
         self.use_hip_graph = False
         self.n_streams = 2          # sub-batches run concurrently on this many HIP streams (engine.StreamedPlan)
         # "bf16": bf16 activations / weights with fp32 accumulation (the fast path); "fp32": float32 end to end on the f32
-        # MFMA — the reference's arithmetic up to summation order, ~20x slower, for parity checks (csrc/conv_f32.hip)
+        # MFMA — the reference's arithmetic up to summation order, ~20x slower, for parity checks (csrc/conv_f32.hip);
+        # "fp16": the bf16 mode's rounding points with IEEE-half activations / weights (three more mantissa bits, activations
+        # must stay below 65504): one gather-kernel launch per layer, the Darknet families only
         self.precision = os.environ.get("YOLO_PRECISION", "bf16")
 
     def _create_yolo_layers(self, device="cpu"):

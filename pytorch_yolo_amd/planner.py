@@ -41,17 +41,21 @@ class Launch:
 # -- fusion rules ------------------------------------------------------------------------------------
 class _Fusion:
     """What the rules may look at besides the graph; the planner's env knobs are read here and nowhere else.  ``f32`` (the
-    reference-precision mode) keeps the epilogue options - upsample here; concat and residual placement - and fuses nothing else."""
+    reference-precision mode) keeps the epilogue options - upsample here; concat and residual placement - and fuses nothing else.
+    ``f16`` (the fp16-operand mode) does the same, except that the head fusion stays on: it lives in the gather kernel, the one
+    kernel family with an fp16 form - the fused stem / units / blocks / pools and the NCHW-reading first layers are bf16-only."""
 
-    def __init__(self, rec: Recorder, f32: bool, n_class: int):
+    def __init__(self, rec: Recorder, f32: bool, n_class: int, f16: bool = False):
         env = os.environ.get
         self.rec, self.n_class = rec, n_class
-        self.resunit_mask = 0 if f32 else int(env("YOLO_FUSE_RESUNIT", str(FUSE_RESUNIT_DEFAULT)))
+        plain = f32 or f16
+        self.resunit_mask = 0 if plain else int(env("YOLO_FUSE_RESUNIT", str(FUSE_RESUNIT_DEFAULT)))
         # "1" all covered blocks, "narrow" only those of csrc/conv_mbconv.hip (hidden <= 192), "0" none
-        self.mbconv = "0" if f32 else env("YOLO_FUSE_MBCONV", "1")
-        self.pool, self.stem, self.head, self.conv1_s2 = (not f32 and env(k, "1") == "1" for k in (
-            "YOLO_FUSE_POOL", "YOLO_FUSE_STEM", "YOLO_FUSE_HEAD", "YOLO_FUSE_CONV1_S2"))
-        self.nchw = not f32
+        self.mbconv = "0" if plain else env("YOLO_FUSE_MBCONV", "1")
+        self.pool, self.stem, self.conv1_s2 = (not plain and env(k, "1") == "1" for k in (
+            "YOLO_FUSE_POOL", "YOLO_FUSE_STEM", "YOLO_FUSE_CONV1_S2"))
+        self.head = not f32 and env("YOLO_FUSE_HEAD", "1") == "1"
+        self.nchw = not plain
 
 
 def _ksize(nd):
@@ -205,9 +209,9 @@ RULES = (fuse_upsample,        # OP_CONV with the 2x2-replicating store
          fuse_head)            # OP_HEAD_DECODE
 
 
-def fuse(rec: Recorder, f32: bool, n_class: int) -> List[Launch]:
+def fuse(rec: Recorder, f32: bool, n_class: int, f16: bool = False) -> List[Launch]:
     """The launches of the graph in node order: what the rules claimed, and one plain launch for every other layer."""
-    fz = _Fusion(rec, f32, n_class)
+    fz = _Fusion(rec, f32, n_class, f16)
     claimed = {}                                               # id(node) -> the Launch that took it
     for rule in RULES:
         for nd in rec.nodes:
@@ -323,7 +327,7 @@ def _live_ranges(rec: Recorder, launches: List[Launch]):
     return rng, pinned
 
 
-def alloc(rec: Recorder, launches: List[Launch], bufs: List[Buf], f32: bool, zeros) -> int:
+def alloc(rec: Recorder, launches: List[Launch], bufs: List[Buf], f32: bool, zeros, f16: bool = False) -> int:
     """One torch tensor (``zeros(shape, dtype)``) per buffer; buffers of identical shape whose live ranges do not overlap share
     storage (YOLO_REUSE_BUFFERS=0 turns that off); returns how many share.  Sharing keeps a residual stage's working set - the
     stream x (in place) and ONE intermediate t instead of one per unit - inside the 256 MB Infinity Cache, and a dead
@@ -339,7 +343,7 @@ def alloc(rec: Recorder, launches: List[Launch], bufs: List[Buf], f32: bool, zer
     pool = {}                                                   # shape key -> [(last use, tensor)]
     shared = 0
     for b in sorted(bufs, key=lambda b_: rng.get(id(b_), (0, 0))[0]):
-        dt = torch.float32 if (b.f32 or f32) else torch.bfloat16
+        dt = torch.float32 if (b.f32 or f32) else (torch.float16 if f16 else torch.bfloat16)
         ct = K.roundup(b.c_total, 8)
         exact = ct == b.c_total and filled.get(id(b), 0) == b.c_total
         b.c_total = ct

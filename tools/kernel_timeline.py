@@ -16,7 +16,7 @@ def fam(name):
     n = re.sub(r"\(anonymous namespace\)::|yolo_conv::|void ", "", name)
     m = re.match(r"(\w+)(<[^>]*>)?", n)
     base = m.group(1)
-    if base == "conv_igemm_bf16_kernel":
+    if base in ("conv_igemm_kernel", "conv_igemm_bf16_kernel"):      # (the name before the kernel took an operand type)
         t = m.group(2).strip("<>").split(",")
         return f"igemm<{t[0].strip()}x{t[1].strip()}>"
     return base[:40]

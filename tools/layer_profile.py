@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-layer timing of one forward (HIP events around each recorded op, median of R repeats).
 
-    python tools/layer_profile.py --workload spp --bs 32 [--repeat 5]
+    python tools/layer_profile.py --workload spp --bs 32 [--repeat 5]          (YOLO_PRECISION=fp16: the fp16-operand mode's list)
 Prints one row per launch: kind, GEMM view (M, N, K), ms, TFLOP/s, algorithmic GB/s.
 """
 import argparse
@@ -81,18 +81,18 @@ def main():
             tot_fl += fl
             by = d.n * d.h * d.w * 3 * 4 + M * 64 * 2
             print(f"{i:3d} {'stem':7} {M:9d} {64:5d} {288:5d} 3 2 {ms:8.4f} {fl / ms / 1e9:8.1f} {by / ms / 1e6:7.0f}  conv1+s2")
-        elif op.kind in (OP_CONV, OP_CONV1_NCHW, OP_HEAD_DECODE, 9, 11):
+        elif op.kind in (OP_CONV, OP_CONV1_NCHW, OP_HEAD_DECODE, 9, 11, 16, 18):      # (16 / 18: OP_CONV_F16 / OP_HEAD_DECODE_F16)
             M, N, Kd = d.n * d.ho * d.wo, d.cout, d.ksize * d.ksize * d.cin
             fl = 2.0 * M * N * Kd
-            by = d.n * d.h * d.w * d.cin * 2 + M * N * (4 if d.out_dtype else 2) * (4 if d.upsample2x else 1) + N * Kd * 2
-            if op.kind == OP_HEAD_DECODE:
+            by = d.n * d.h * d.w * d.cin * 2 + M * N * (4 if d.out_dtype == 1 else 2) * (4 if d.upsample2x else 1) + N * Kd * 2
+            if op.kind in (OP_HEAD_DECODE, 18):
                 by += M * N * 4
             if op.residual:
                 by += M * N * 2
             if op.y_aux:
                 by += M * N * 2
             tot_fl += fl
-            flags = ("head+decode " if op.kind == OP_HEAD_DECODE else "") + ("res " if op.residual else "") + ("aux " if op.y_aux else "") + ("up " if d.upsample2x else "") + ("f32" if d.out_dtype else "")
+            flags = ("head+decode " if op.kind in (OP_HEAD_DECODE, 18) else "") + ("res " if op.residual else "") + ("aux " if op.y_aux else "") + ("up " if d.upsample2x else "") + ("f32" if d.out_dtype == 1 else "")
             print(f"{i:3d} {'conv':7} {M:9d} {N:5d} {Kd:5d} {d.ksize:1d} {d.stride:1d} {ms:8.4f} {fl / ms / 1e9:8.1f} {by / ms / 1e6:7.0f}  {flags}")
         elif op.kind == OP_RESUNIT:
             M, Cc = d.n * d.h * d.w, d.cout
@@ -107,7 +107,7 @@ def main():
             by = d.n * d.h * d.w * d.cin * 2 + M * d.cout * 2
             print(f"{i:3d} {'mbconv':7} {M:9d} {d.cout:5d} {hid:5d} 3 {d.stride:1d} {ms:8.4f} {fl / ms / 1e9:8.1f} {by / ms / 1e6:7.0f}  {'res' if d.res_c_total else ''}")
         else:
-            kind = {OP_MAXPOOL: "pool", OP_SPP: "spp", OP_DWCONV: "dwconv", 12: "shuffle", 15: "se"}.get(op.kind, f"op{op.kind}")
+            kind = {OP_MAXPOOL: "pool", 17: "pool", OP_SPP: "spp", OP_DWCONV: "dwconv", 12: "shuffle", 15: "se"}.get(op.kind, f"op{op.kind}")
             by = d.n * d.h * d.w * d.cin * 2 * (4 if op.kind == OP_SPP else 3 if op.kind == 15 else 2)
             print(f"{i:3d} {kind:7} {d.n * d.h * d.w:9d} {d.cin:5d} {'':5} {d.ksize:1d} {d.stride:1d} {ms:8.4f} {'':8} {by / ms / 1e6:7.0f}")
     print(f"total {tot_ms:.3f} ms  conv {tot_fl / 1e12:.3f} TFLOP -> {tot_fl / tot_ms / 1e9:.1f} TFLOP/s over the per-op sum")
