@@ -326,6 +326,19 @@ YOLO_API int yolo_pack_conv_weight_f32_f32(const float* w_oihw, int cout, int ci
  *  yolo_pack_input_nchw_f32_f16: x f32 NCHW -> y fp16 NHWC [n,h,w,c_pad]. */
 YOLO_API int yolo_conv2d_f16_fwd(const void* x, const void* w_packed, const float* bias, const void* residual, void* y,
                                  void* y_preadd, const YoloConvDesc* d, yolo_stream_t s);
+/* The large 3x3 / pad 1 layers of the fp16 mode on the 20x20-output-tile kernels (stride 1 and stride 2; csrc/conv3x3_t20.h), the
+ *  fp16 forms of the kernels yolo_conv2d_fwd runs such layers on: v_mfma_f32_16x16x32_f16, fp16 residual / pre-add copy, the
+ *  narrowing above.  Arguments as yolo_conv2d_f16_fwd with d->out_dtype = YOLO_DT_F16.  yolo_conv2d_f16_fwd itself never
+ *  dispatches here: whoever builds a launch list chooses per layer.
+ *  yolo_conv3x3_t20_f16_supported: 1 when the shipped rule takes the layer - 3x3, pad 1, stride 1 or 2, cin % 32 == 0,
+ *  cout % 128 == 0, no swish, no upsampling store, every view in multiples of 8 channels, the map covered >= 90 % by 20x20 tiles and
+ *  tiles * cout / 128 >= CUs / 2 (stride 1) or >= 2 * CUs (stride 2), CUs = 256 or what yolo_set_launch_cus said.  A pure function
+ *  of its arguments and that number; launches nothing, needs no GPU, and no yolo_set_tuning knob changes it.
+ *  yolo_conv3x3_t20_f16_fwd: force = 0 returns YOLO_E_UNSUPPORTED where _supported says 0; force = 1 runs every layer the
+ *  kernels can compute (everything above but the last two conditions; tests, A/B runs). */
+YOLO_API int yolo_conv3x3_t20_f16_supported(const YoloConvDesc* d, int has_residual, int has_aux);
+YOLO_API int yolo_conv3x3_t20_f16_fwd(const void* x, const void* w_packed, const float* bias, const void* residual, void* y,
+                                      void* y_aux, const YoloConvDesc* d, int force, yolo_stream_t s);
 YOLO_API int yolo_conv2d_f16_pick(const YoloConvDesc* d, int has_residual, int has_preadd, char* out, int out_len);
 YOLO_API int yolo_head_decode_f16_pick(const YoloConvDesc* d, int na, int nc, int filter, char* out, int out_len);
 YOLO_API int yolo_head_decode_f16_fwd(const void* x, const void* w_packed, const float* bias, const YoloConvDesc* d,
@@ -351,7 +364,9 @@ enum { YOLO_OP_CONV = 1, YOLO_OP_MAXPOOL = 2, YOLO_OP_SPP = 3, YOLO_OP_DWCONV = 
        YOLO_OP_SE = 15 /* yolo_se_fwd: x / y views in conv (n, h, w, cin, in_*, out_*), w / bias = W1 / b1, w_pre / bias_pre = W2 / b2,
                           kpad_pre = squeezed channels, workspace / ws_bytes */,
        YOLO_OP_CONV_F16 = 16 /* yolo_conv2d_f16_fwd */, YOLO_OP_MAXPOOL_F16 = 17 /* yolo_maxpool_f16_fwd, fields as MAXPOOL */,
-       YOLO_OP_HEAD_DECODE_F16 = 18 /* yolo_head_decode_f16_fwd / yolo_head_decode_filter_f16_fwd, fields as HEAD_DECODE */ };
+       YOLO_OP_HEAD_DECODE_F16 = 18 /* yolo_head_decode_f16_fwd / yolo_head_decode_filter_f16_fwd, fields as HEAD_DECODE */,
+       YOLO_OP_CONV_T20_F16 = 19 /* yolo_conv3x3_t20_f16_fwd with force = 1 (the list's builder asked yolo_conv3x3_t20_f16_supported),
+                                    fields as CONV_F16 */ };
 typedef struct YoloOp {
   int32_t kind, _pad;
   const void* x; const void* w; const float* bias; const void* residual; void* y; void* y_aux;

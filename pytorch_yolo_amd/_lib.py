@@ -17,6 +17,7 @@ DT_BF16, DT_F32, DT_F16 = 0, 1, 2
 OP_CONV, OP_MAXPOOL, OP_SPP, OP_DWCONV, OP_CONV1_NCHW, OP_RESUNIT, OP_STEM, OP_HEAD_DECODE, OP_CONV1_POOL = 1, 2, 3, 4, 5, 6, 7, 8, 9
 OP_MBCONV, OP_CONV_POOL, OP_SHUFFLE, OP_CONV_F32, OP_MAXPOOL_F32, OP_SE = 10, 11, 12, 13, 14, 15
 OP_CONV_F16, OP_MAXPOOL_F16, OP_HEAD_DECODE_F16 = 16, 17, 18          # the fp16-operand mode
+OP_CONV_T20_F16 = 19                                                  # ... its large 3x3 layers on the 20x20-tile kernels
 
 
 class YoloConvDesc(C.Structure):
@@ -115,6 +116,8 @@ SIGNATURES = {
     "yolo_pack_input_nchw_f32_nhwc": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "yolo_pack_conv_weight_f32_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "yolo_conv2d_f16_fwd": (C.c_int, [C.c_void_p] * 6 + [C.POINTER(YoloConvDesc), C.c_void_p]),
+    "yolo_conv3x3_t20_f16_supported": (C.c_int, [C.POINTER(YoloConvDesc), C.c_int, C.c_int]),
+    "yolo_conv3x3_t20_f16_fwd": (C.c_int, [C.c_void_p] * 6 + [C.POINTER(YoloConvDesc), C.c_int, C.c_void_p]),
     "yolo_conv2d_f16_pick": (C.c_int, [C.POINTER(YoloConvDesc), C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "yolo_head_decode_f16_pick": (C.c_int, [C.POINTER(YoloConvDesc), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "yolo_head_decode_f16_fwd": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YoloConvDesc), C.c_void_p, C.c_int, C.c_int, C.c_float,

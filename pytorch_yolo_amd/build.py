@@ -20,6 +20,7 @@ SOURCES = {
     "conv_igemm.hip": [],
     "conv3x3_halo.hip": [],
     "conv3x3_t20.hip": [],
+    "conv3x3_t20_f16.hip": [],
     "conv_resunit.hip": [],
     "conv_resunit_t20.hip": [],
     "conv_stem.hip": [],
@@ -45,7 +46,7 @@ def _stale(out: str, deps) -> bool:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
-    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "nms_common.h"),
+    headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv3x3_t20.h"), os.path.join(CSRC, "nms_common.h"),
                os.path.join(CSRC, "head_epilogue.h"), os.path.join(CSRC, "tuning.h"),
                os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "yolo_hip.h"),
                os.path.abspath(__file__)]        # per-file flags live here: a flag change rebuilds too

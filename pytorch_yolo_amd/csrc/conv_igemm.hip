@@ -900,8 +900,9 @@ int conv2d_launch_ex(const void* x, const void* w, const float* bias, const void
   YOLO_SET_STAMPS(a);
   if (hd) a.hd = *hd;
   if (dt == YOLO_DT_F16) {
-    // fp16 operands: the gather kernel only.  The t20 / stream / halo families (and the stem, the fused units, conv_small, mbconv)
-    // hold bf16 in asm or registers and never see an fp16 launch; the tuning word does not apply either.
+    // fp16 operands: the gather kernel only.  The stream / halo families (and the stem, the fused units, conv_small, mbconv)
+    // hold bf16 in asm or registers and never see an fp16 launch; the 20x20-tile kernels have fp16 forms behind an entry point of
+    // their own, which whoever builds a launch list chooses (conv3x3_t20_f16.hip), never this one; the tuning word does not apply either.
     YOLO_REQUIRE(d.out_dtype == YOLO_DT_F16 || d.out_dtype == YOLO_DT_F32, "conv_f16: out_dtype %d (YOLO_DT_F16 or YOLO_DT_F32)", d.out_dtype);
     YOLO_REQUIRE(a.splits <= 1, "conv_f16: no split-K form");
     a.debug = 0;

@@ -110,6 +110,11 @@ extern "C" int yolo_run_ops(const YoloOp* ops, int n_ops, yolo_stream_t s) {
       case YOLO_OP_CONV_F16:
         rc = yolo_conv2d_f16_fwd(o.x, o.w, o.bias, o.residual, o.y, o.y_aux, &d, s);
         break;
+      case YOLO_OP_CONV_T20_F16:
+        // (the planner chose this kernel with yolo_conv3x3_t20_f16_supported when it built the list; a launch does not decide again
+        // against the CU share of the stream it happens to run on)
+        rc = yolo_conv3x3_t20_f16_fwd(o.x, o.w, o.bias, o.residual, o.y, o.y_aux, &d, 1, s);
+        break;
       case YOLO_OP_MAXPOOL_F16:
         rc = yolo_maxpool_f16_fwd(o.x, o.y, d.n, d.h, d.w, d.cin, d.in_c_total, d.in_c_offset, d.ho, d.wo, d.out_c_total, d.out_c_offset,
                                   d.ksize, d.stride, d.pad, d.upsample2x /* dilation */, s);

@@ -4,7 +4,7 @@ accounting over such an array.
 One emitter per launch kind (``EMITTERS``), each returning the op(s) of one launch; ``build_ops`` is the loop over the records
 for every precision (fp32: the same conv emitter with the fp32 packing and op kind, max pools instead of the SPP kernel, no
 kernel for the depthwise / SE / shuffle layers; fp16: the fp16 packing and op kinds, the SPP kernel itself - it orders 16-bit
-patterns -, no kernel for those three layer kinds either)."""
+patterns -, no kernel for those three layer kinds either; its large 3x3 layers go to the 20x20-tile kernels)."""
 from __future__ import annotations
 
 import os
@@ -13,7 +13,7 @@ import torch
 
 from . import diag
 from . import kernels as K
-from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, DT_BF16, DT_F16, DT_F32, OP_SE, OP_CONV, OP_CONV1_NCHW, OP_CONV_F16,
+from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, DT_BF16, DT_F16, DT_F32, OP_SE, OP_CONV, OP_CONV1_NCHW, OP_CONV_F16, OP_CONV_T20_F16,
                    OP_CONV_F32, OP_DWCONV, OP_CONV1_POOL, OP_CONV_POOL, OP_HEAD_DECODE_F16, OP_MAXPOOL_F16, OP_MAXPOOL_F32, OP_MBCONV,
                    OP_SHUFFLE, OP_HEAD_DECODE, OP_MAXPOOL, OP_RESUNIT, OP_SPP, OP_STEM, YoloOp)
 
@@ -112,7 +112,9 @@ def _emit_resunit(plan, L):
 
 def _emit_conv(plan, L):
     """The plain conv of either precision with its epilogue options (upsampling store, residual, pre-add copy) and, bf16 only,
-    the NCHW-reading / pooling / split-K forms."""
+    the NCHW-reading / pooling / split-K forms.  fp16: the layers the shipped rule of the 20x20-tile 3x3 kernels takes
+    (yolo_conv3x3_t20_f16_supported, asked here, once, with the CUs of the whole chip) become OP_CONV_T20_F16 - same fields, same
+    buffers; YOLO_FP16_T20=0 (read when the plan is built) keeps every layer in the gather kernel for A/B runs."""
     nd, x, dst = L.node, L.src, L.dst
     y = nd.outs[0]
     w, b = nd.attrs["weight"]
@@ -135,6 +137,8 @@ def _emit_conv(plan, L):
         d.res_c_total = plan.rec.c_in          # real input channels (x pointer is patched per call)
     else:
         kind = OP_CONV_POOL if L.pooled else plain
+        if kind == OP_CONV_F16 and os.environ.get("YOLO_FP16_T20", "1") != "0" and K.conv3x3_t20_f16_supported(d, res is not None, aux is not None):
+            kind = OP_CONV_T20_F16
     op = _op(kind, x=None if L.reads_nchw else _ptr(x), y=_ptr(dst), residual=_ptr(res) if res is not None else None,
              y_aux=_ptr(aux) if aux is not None else None, conv=d)
     op.w, op.bias = _keep(plan, wp, bp)
@@ -255,7 +259,7 @@ def build_ops(plan):
 
 
 # -- accounting --------------------------------------------------------------------------------------
-_CONVS = (OP_CONV, OP_CONV1_NCHW, OP_CONV1_POOL, OP_CONV_POOL, OP_HEAD_DECODE, OP_CONV_F32, OP_CONV_F16, OP_HEAD_DECODE_F16)
+_CONVS = (OP_CONV, OP_CONV1_NCHW, OP_CONV1_POOL, OP_CONV_POOL, OP_HEAD_DECODE, OP_CONV_F32, OP_CONV_F16, OP_HEAD_DECODE_F16, OP_CONV_T20_F16)
 
 
 def conv_flops(op_array, n_ops: int, c_in: int) -> float:

@@ -86,7 +86,7 @@ class Plan(GuardedAlloc, _Runs):
     ``precision``: "bf16" (default: bf16 activations / weights, fp32 accumulate, every fusion), "fp32" (the
     reference-precision parity mode: float32 activations and weights on the f32 MFMA, one plain launch per layer,
     csrc/conv_f32.hip) or "fp16" (the rounding points of the bf16 mode with IEEE-half activations / weights: three more
-    mantissa bits at the bf16 MFMA rate; one launch of the gather kernel per layer, heads decoded in their conv, the Darknet
+    mantissa bits at the bf16 MFMA rate; one launch per layer - the 20x20-tile kernels on the large 3x3 layers, the gather kernel elsewhere -, heads decoded in their conv, the Darknet
     families only)."""
     n_streams = 1
 

@@ -105,6 +105,24 @@ def conv2d_f16(x, w_packed, bias, y, desc: YoloConvDesc, residual=None, y_preadd
     return y
 
 
+def conv3x3_t20_f16_supported(desc: YoloConvDesc, has_residual=False, has_preadd=False) -> bool:
+    """The shipped rule hands this fp16 layer to the 20x20-tile 3x3 kernels (yolo_conv3x3_t20_f16_supported: no launch, works
+    without a GPU; sized against the thread's launch CUs)."""
+    return bool(load().yolo_conv3x3_t20_f16_supported(C.byref(desc), int(has_residual), int(has_preadd)))
+
+
+def conv3x3_t20_f16(x, w_packed, bias, y, desc: YoloConvDesc, residual=None, y_preadd=None, force=False):
+    """fp16 3x3 conv on the 20x20-tile kernels (yolo_conv3x3_t20_f16_fwd): tensors as conv2d_f16, y fp16.  ``force``: every layer
+    the kernels can compute instead of the shipped rule's."""
+    _need_cuda(x, w_packed, bias, y, residual, y_preadd)
+    for t in (x, w_packed, y, residual, y_preadd):
+        if t is not None and t.dtype != torch.float16:
+            raise RuntimeError("conv3x3_t20_f16: x, w_packed, y, residual and y_preadd must be float16")
+    check(load().yolo_conv3x3_t20_f16_fwd(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(residual), _ptr(y), _ptr(y_preadd),
+                                          C.byref(desc), int(force), stream_ptr()), "conv3x3_t20_f16")
+    return y
+
+
 def conv2d_f16_pick(desc: YoloConvDesc, has_residual=False, has_preadd=False) -> str:
     """Name + grid of the fp16 instance yolo_conv2d_f16_fwd would launch for ``desc`` (no launch, works without a GPU)."""
     buf = C.create_string_buffer(256)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-layer timing of one forward (HIP events around each recorded op, median of R repeats).
 
-    python tools/layer_profile.py --workload spp --bs 32 [--repeat 5]          (YOLO_PRECISION=fp16: the fp16-operand mode's list)
+    python tools/layer_profile.py --workload spp --bs 32 [--repeat 5]          (YOLO_PRECISION=fp16: the fp16-operand mode's list; its
+                                                                                launches of the 20x20-tile 3x3 kernels print as kind
+                                                                                t20_f16, YOLO_FP16_T20=0 keeps them in the gather kernel)
 Prints one row per launch: kind, GEMM view (M, N, K), ms, TFLOP/s, algorithmic GB/s.
 """
 import argparse
@@ -81,7 +83,7 @@ def main():
             tot_fl += fl
             by = d.n * d.h * d.w * 3 * 4 + M * 64 * 2
             print(f"{i:3d} {'stem':7} {M:9d} {64:5d} {288:5d} 3 2 {ms:8.4f} {fl / ms / 1e9:8.1f} {by / ms / 1e6:7.0f}  conv1+s2")
-        elif op.kind in (OP_CONV, OP_CONV1_NCHW, OP_HEAD_DECODE, 9, 11, 16, 18):      # (16 / 18: OP_CONV_F16 / OP_HEAD_DECODE_F16)
+        elif op.kind in (OP_CONV, OP_CONV1_NCHW, OP_HEAD_DECODE, 9, 11, 16, 18, 19):      # (16 / 18 / 19: OP_CONV_F16 / OP_HEAD_DECODE_F16 / OP_CONV_T20_F16)
             M, N, Kd = d.n * d.ho * d.wo, d.cout, d.ksize * d.ksize * d.cin
             fl = 2.0 * M * N * Kd
             by = d.n * d.h * d.w * d.cin * 2 + M * N * (4 if d.out_dtype == 1 else 2) * (4 if d.upsample2x else 1) + N * Kd * 2
@@ -93,7 +95,7 @@ def main():
                 by += M * N * 2
             tot_fl += fl
             flags = ("head+decode " if op.kind in (OP_HEAD_DECODE, 18) else "") + ("res " if op.residual else "") + ("aux " if op.y_aux else "") + ("up " if d.upsample2x else "") + ("f32" if d.out_dtype == 1 else "")
-            print(f"{i:3d} {'conv':7} {M:9d} {N:5d} {Kd:5d} {d.ksize:1d} {d.stride:1d} {ms:8.4f} {fl / ms / 1e9:8.1f} {by / ms / 1e6:7.0f}  {flags}")
+            print(f"{i:3d} {'t20_f16' if op.kind == 19 else 'conv':7} {M:9d} {N:5d} {Kd:5d} {d.ksize:1d} {d.stride:1d} {ms:8.4f} {fl / ms / 1e9:8.1f} {by / ms / 1e6:7.0f}  {flags}")
         elif op.kind == OP_RESUNIT:
             M, Cc = d.n * d.h * d.w, d.cout
             fl = 2.0 * M * (Cc * Cc // 2) * 10

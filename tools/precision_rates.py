@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """images/s of model.detect() on SPP-640 x 32 in the three precision modes, interleaved in ONE process over several rounds (the chip's
-clock and temperature drift between processes: only numbers from the same run compare).
+clock and temperature drift between processes: only numbers from the same run compare).  The fp16 mode is timed twice: as shipped
+(large 3x3 layers on the 20x20-tile kernels, OP_CONV_T20_F16) and with YOLO_FP16_T20=0 (every layer in the gather kernel: the list
+before those kernels existed) - a second model object whose plans are built under that switch.
     python tools/precision_rates.py [rounds] [calls per round]  > profiles/fp16_mode_rates.md"""
 import os
 import statistics
@@ -15,7 +17,15 @@ from pytorch_yolo_amd import YOLOv3SPP                                          
 from pytorch_yolo_amd.utils.synthetic import synth_images, synth_state_dict      # noqa: E402
 
 SPP_ANCHORS = (((10., 13.), (16., 30.), (33., 23.)), ((30., 61.), (62., 45.), (59., 119.)), ((116., 90.), (156., 198.), (373., 326.)))
-MODES = ("bf16", "fp16", "fp32")
+MODES = ("bf16", "fp16", "fp16 gather-only", "fp32")
+GATHER = "fp16 gather-only"
+
+
+def _op_kinds(plan):
+    """{op kind: launches} of the whole-batch list detect() runs (or of the first sub-batch list)."""
+    from collections import Counter
+    one = (getattr(plan, "_full", None) or getattr(plan, "subs", None) or [plan])[0]
+    return Counter(one.op_array[i].kind for i in range(one.n_ops))
 
 
 def main():
@@ -26,18 +36,35 @@ def main():
     model = YOLOv3SPP(n_class=80, anchors=SPP_ANCHORS).eval()
     model.load_state_dict(synth_state_dict(model.state_dict(), 1234, n_class=80))
     model = model.to(dev)
+    gather = YOLOv3SPP(n_class=80, anchors=SPP_ANCHORS).eval()
+    gather.load_state_dict(model.state_dict())
+    gather = gather.to(dev)
+    gather.precision = "fp16"
+    models = {m: (gather if m == GATHER else model) for m in MODES}
     x = torch.cat([synth_images(1, hw, hw, i) for i in range(bs)], 0).to(dev)
     per_mode = {m: [] for m in MODES}
-    n_det = {}
+    n_det, kinds = {}, {}
     with torch.no_grad():
         for m in MODES:                                    # plans, packed weights, first-launch costs
-            model.precision = m
-            for _ in range(2):
-                dets = model.detect(x, conf, iou)
+            model = models[m]
+            if m != GATHER:
+                model.precision = m
+            old = os.environ.get("YOLO_FP16_T20")
+            if m == GATHER:
+                os.environ["YOLO_FP16_T20"] = "0"          # read when a plan is built: all of this model's are built in these calls
+            try:
+                for _ in range(2):
+                    dets = model.detect(x, conf, iou)
+            finally:
+                if m == GATHER:
+                    os.environ.pop("YOLO_FP16_T20") if old is None else os.environ.__setitem__("YOLO_FP16_T20", old)
             n_det[m] = sum(0 if d is None else len(d) for d in dets)
+            kinds[m] = _op_kinds(model.plan_for(x))
         for rnd in range(rounds):
             for m in MODES:
-                model.precision = m
+                model = models[m]
+                if m != GATHER:
+                    model.precision = m
                 n = calls if m != "fp32" else max(3, calls // 5)
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -53,7 +80,12 @@ def main():
     med = {m: statistics.median(per_mode[m]) for m in MODES}
     for m in MODES:
         print(f"| {m} | " + " | ".join(f"{v:.0f}" for v in per_mode[m]) + f" | {med[m]:.0f} | {med[m] / med['bf16']:.3f} | {n_det[m]} |")
-    print(f"\nfp16 / fp32 = {med['fp16'] / med['fp32']:.2f}")
+    print(f"\nfp16 / fp32 = {med['fp16'] / med['fp32']:.2f}; fp16 / fp16 gather-only = {med['fp16'] / med[GATHER]:.3f} "
+          f"(smallest round of fp16 {min(per_mode['fp16']):.0f}, largest of gather-only {max(per_mode[GATHER]):.0f})")
+    from pytorch_yolo_amd._lib import OP_CONV_F16, OP_CONV_T20_F16
+    for m in ("fp16", GATHER):
+        print(f"{m} launch list: {kinds[m][OP_CONV_T20_F16]} OP_CONV_T20_F16 (20x20-tile 3x3 kernels) + {kinds[m][OP_CONV_F16]} OP_CONV_F16 "
+              f"(gather kernel) of {sum(kinds[m].values())} launches")
     if not all(a > b for a, b in zip(per_mode["fp16"], per_mode["fp32"])):
         raise SystemExit("fp16 detect() is not faster than the fp32 mode in this run")
 
