@@ -17,7 +17,11 @@
 //   YOLO_DWCONV_DEBUG     pointwise.hip           kDw* bits
 //   YOLO_SPP_NO_LINES     pointwise.hip           set: the 8-channel SPP form for every shape
 //   YOLO_RESUNIT_STAGGER  conv_resunit_t20.hip    start offset between the workgroups of a CU (tuning only)
-// A bit without a name below is tested nowhere.
+// A bit without a name below is tested nowhere.  Of the named ones, the recipes of tests/_exact_cases.py launch the gather-kernel
+// instances behind knob 0 (variants 0, 3, 5, 7, 8, 9, 10, 11) and behind kCdNoLdsEpilogue, kCdNoLoaderWaves, kCd256x256EightWaves,
+// kCdMfma32x32, kCdFourWaves, kCdLoadersTwoStages, kCd64x64TwoStages and kCdStreamFirstForm, and compare them bit for bit
+// (tests/test_conv_exact_gpu.py); kFamT20Always / kFamT20Never, kFamStreamAlways / kFamStreamNever and the form bits of knobs 3 and 4
+// have their cases in tests/test_gpu_parity.py.  The ablation bits give wrong results by design and have no test.
 #pragma once
 
 struct Tuning {

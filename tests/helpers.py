@@ -128,3 +128,108 @@ def strict_share(da, db, iou_min=0.9, dconf=0.03):
         return 0.0
     return sum(any(int(r[6]) == int(q[6]) and abs(float(r[4]) - float(q[4])) <= dconf and box_iou(r[:4], q[:4]) >= iou_min
                    for q in db) for r in da) / len(da)
+
+
+# ---- exact conv cases: operands whose conv has ONE right answer in every bit ---------------------------------------------------------
+# Small integers are exact in bf16 and fp16, every product and partial sum of them is exact in fp32 in whatever order, tile shape,
+# split-K partition or MFMA shape it is formed: the conv output before the activation is THE integer sum plus the bias.  What remains
+# is the epilogue: one fp32 multiply by 0.1f on the LeakyReLU negative side, one narrowing for the pre-add copy, one fp32 add of the
+# residual, one round-to-nearest-even narrowing.  The comparison with a kernel is torch.equal.
+_EXACT_BITS = {torch.bfloat16: 16, torch.float16: 13}       # fp32 mantissa bits the 16-bit type drops (normal range)
+_EXACT_CACHE = {}
+
+
+def exact_conv_case(shape, seed, dtype):
+    """Seeded CPU tensors (x, w, bias, res) as float32 for shape = (n, h, w, cin, cout, k, stride, act, use_res); res is None
+    without a residual.
+      * bf16 / fp16: x and w are integers in {-3..3}; the bias is an integer of magnitude 260..1000 (bf16) / 2100..7000 (fp16) on
+        five channels of six, positive on four of those five, so that most outputs lie where integers need rounding (bf16: from 256 on,
+        fp16: from 2048 on) and the binades where every second / fourth integer is an exact tie carry most of them; res holds integers
+        in [-300, 300], rounded to the type.
+      * ReLU6 clamps to [0, 6], where every integer is representable: there x and the bias are scaled by 2^-8 (bf16) / 2^-11 (fp16) -
+        a power of two, so every product and sum stays exact - and the bias spreads the channels over [1, 4) (where multiples of
+        2^-8 / 2^-11 need rounding), below 0 and around 6 (both clamps).
+      * float32 (yolo_conv2d_f32_fwd): x holds integers of magnitude < 2^11 - eleven significant bits, more than bf16, fp16's
+        subnormal-free products or a reduced-precision MFMA would keep -, w is in {-1, 0, 1}, bias and res are small integers."""
+    n, h, w, cin, cout, k, stride, act, use_res = shape
+    g = torch.Generator().manual_seed(seed)
+    ri = lambda lo, hi, *size: torch.randint(lo, hi + 1, size, generator=g).float()
+    pad = (k - 1) // 2
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    ch = torch.arange(cout)
+    if dtype == torch.float32:
+        assert k * k * cin * 2 ** 11 < 2 ** 24
+        x, wt = ri(-2047, 2047, n, cin, h, w), ri(-1, 1, cout, cin, k, k)
+        bias = ri(-1500, 1500, cout)
+        res = ri(-300, 300, n, cout, ho, wo) if use_res else None
+        return x, wt, bias, res
+    x, wt = ri(-3, 3, n, cin, h, w), ri(-3, 3, cout, cin, k, k)
+    if act == "relu6":
+        assert not use_res
+        unit = 2.0 ** -(8 if dtype == torch.bfloat16 else 11)
+        steps = int(round(1.0 / unit))
+        bias = ri(steps, 4 * steps - 1, cout)                               # [1, 4) in units of 2^-8 / 2^-11
+        bias = torch.where(ch % 6 == 0, -2.0 * steps + 0 * bias, bias)      # lower clamp
+        bias = torch.where(ch % 6 == 3, ri(6 * steps - 40, 6 * steps + 40, cout), bias)   # straddles the upper clamp
+        return x * unit, wt, bias * unit, None
+    lo, hi = (260, 1000) if dtype == torch.bfloat16 else (2100, 7000)
+    mag = ri(lo, hi, cout)
+    sign = torch.where(ri(0, 4, cout) == 0, -1.0, 1.0)
+    bias = torch.where(ch % 6 == 5, ri(-3, 3, cout), mag * sign)
+    res = ri(-300, 300, n, cout, ho, wo).to(dtype).float() if use_res else None        # (bf16: the odd integers beyond 256 round to even)
+    return x, wt, bias, res
+
+
+def exact_conv_reference(x, wt, bias, res, *, stride, act, up, dtype, f32_out=False):
+    """(y, pre-add copy) of the conv epilogue as csrc/conv_common.h (epilogue_lds_core) and the direct epilogue of
+    csrc/conv_igemm.hip run it: apply_act, aux = narrow(v), v += res, narrow - every step an explicit float32 operation.  y is the
+    16-bit tensor (float32 if f32_out or dtype is float32), NCHW.  Rejects (AssertionError) a case whose reference does not
+    determine every bit or does not exercise the rounding:
+      * the fp32 conv must equal the fp64 conv exactly, and every |value| stay below 2^24;
+      * (16-bit types) at least 25 % of the values that are narrowed are not representable in the type and at least 10 % are exact
+        ties, at the final narrowing and at the pre-add copy alike."""
+    import torch.nn.functional as F
+    pad = (wt.shape[-1] - 1) // 2
+    with torch.no_grad():
+        v = F.conv2d(x, wt, bias, stride=stride, padding=pad)
+        v64 = F.conv2d(x.double(), wt.double(), bias.double(), stride=stride, padding=pad)
+    assert v.dtype == torch.float32 and torch.equal(v.double(), v64), "the fp32 conv of the case is not exact"
+    bound = float(x.abs().max()) * float(wt.abs().max()) * wt[0].numel() + float(bias.abs().max()) + 301.0
+    assert bound < 2.0 ** 24 * float(min(x[x != 0].abs().min(), 1.0)), "a partial sum of the case can leave the exact integers of fp32"
+    if act == "leaky":
+        v = torch.where(v > 0, v, torch.tensor(0.1, dtype=torch.float32) * v)      # one fp32 multiply, no fma
+    elif act == "relu6":
+        v = v.clamp(0.0, 6.0)
+    else:
+        assert act == "none", act
+    narrow = (lambda t: t) if dtype == torch.float32 else (lambda t: t.to(dtype))
+    pre = v
+    aux = narrow(pre)
+    if res is not None:
+        assert dtype == torch.float32 or torch.equal(res.to(dtype).float(), res)
+        v = v + res                                                                   # one fp32 add
+    if dtype != torch.float32:
+        for name, t in (("output", v), ("pre-add copy", pre)):
+            nonrep, ties = exact_rounding_shares(t, dtype)
+            assert nonrep >= 0.25 and ties >= 0.10, f"{name}: {nonrep:.3f} of the values need rounding, {ties:.3f} are ties"
+    y = v if (f32_out or dtype == torch.float32) else narrow(v)
+    if up:
+        y = y.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)                 # nearest 2x (a copy: before or after narrowing)
+    return y, aux
+
+
+def exact_rounding_shares(t, dtype):
+    """(share of the float32 values in t that dtype cannot represent, share that lie exactly half-way between two neighbours)."""
+    drop = _EXACT_BITS[dtype]
+    low = t.contiguous().view(torch.int32) & ((1 << drop) - 1)
+    return float((low != 0).float().mean()), float((low == (1 << (drop - 1))).float().mean())
+
+
+def exact_conv(shape, seed, dtype, up=False, f32_out=False):
+    """exact_conv_case + exact_conv_reference, computed once per process: (x, w, bias, res, y_ref, aux_ref).  Do not modify them."""
+    key = (tuple(shape), seed, dtype, bool(up), bool(f32_out))
+    if key not in _EXACT_CACHE:
+        x, wt, bias, res = exact_conv_case(shape, seed, dtype)
+        y, aux = exact_conv_reference(x, wt, bias, res, stride=shape[6], act=shape[7], up=up, dtype=dtype, f32_out=f32_out)
+        _EXACT_CACHE[key] = (x, wt, bias, res, y, aux)
+    return _EXACT_CACHE[key]

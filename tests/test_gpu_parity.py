@@ -5,6 +5,14 @@ Tolerances (stated once, used below):
   * pools / SPP / pack: exact (max and rounding are order-free).
   * conv (bf16 in, fp32 accumulate): against an fp32 conv of the SAME bf16-rounded operands,
     |err| <= 2e-3 * sqrt(K)-scaled bound -> we use rtol 1e-2 on the bf16-rounded output (1 bf16 ulp = 2^-8).
+    That tolerance is wider than one rounding, so it cannot tell round-to-nearest-even from truncation, nor where the epilogue
+    rounds.  tests/test_conv_exact_gpu.py closes that: on small-integer operands every product and partial sum is exact in fp32, the
+    output has ONE right value and the comparison is torch.equal - for every non-decode instance of the gather kernel (each reached
+    by a recipe that tests/test_conv_exact_cpu.py checks against yolo_conv2d_pick), the 20x20-tile, halo and streaming kernels, split-K,
+    the fp16 tables and the fp32 kernel.  It pins summation coverage (every product reaches the sum), the rounding mode (a quarter
+    and more of each output needs rounding, a tenth and more are exact ties) and the rounding points (activation, pre-add copy,
+    fp32 residual add, one narrowing).  It cannot pin the rounding of non-integer operands, non-finite or subnormal values: those
+    stay with the tests below and in test_fp16_gpu.py.
   * decode: fp32 vs torch.  Standalone kernel (yolo_decode_fwd: expf + IEEE division, the decode of precision = "fp32"):
     rtol 2e-6 / atol 1e-5 for |logit| up to 30, <= 2 ulp on values straddling the NMS thresholds.  Head-conv epilogue (the bf16
     path: v_exp_f32 on r * log2 e + v_rcp_f32): w / h relative error <= (3 + |r|) * 2^-23, sigmoid absolute error <= 2^-22
@@ -89,7 +97,7 @@ def test_conv_kernel(case):
     res = torch.randn(n, cout, ho, wo, generator=g) if use_res else None
     # views with channel offsets on every tensor to exercise the concat plumbing
     in_ct, in_co = cin + 16, 8
-    xin = torch.zeros(n, h, w, in_ct, dtype=torch.bfloat16, device=DEV)
+    xin = torch.full((n, h, w, in_ct), float("nan"), dtype=torch.bfloat16, device=DEV)      # NaN next to the view: a read past cin shows
     xin[..., in_co:in_co + cin] = _nhwc(x)
     oh, ow = (2 * ho, 2 * wo) if up else (ho, wo)
     out_ct = (K.roundup(cout, 8) + 8)
@@ -2514,7 +2522,7 @@ def test_t20_conv_kernel(case):
     bias = torch.randn(cout, generator=g) * 0.1
     res = torch.randn(n, cout, h, w, generator=g) if use_res else None
     in_ct, in_co = cin + 16, 8
-    xin = torch.zeros(n, h, w, in_ct, dtype=torch.bfloat16, device=DEV)
+    xin = torch.full((n, h, w, in_ct), float("nan"), dtype=torch.bfloat16, device=DEV)      # NaN next to the view: a read past cin shows
     xin[..., in_co:in_co + cin] = _nhwc(x)
     out_ct, out_co = cout + 8, 8
     rin = _nhwc(res) if use_res else None
@@ -2617,7 +2625,7 @@ def test_t20_stride2_conv_kernel(case):
     bias = torch.randn(cout, generator=g) * 0.1
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     in_ct, in_co = cin + 16, 8
-    xin = torch.zeros(n, h, w, in_ct, dtype=torch.bfloat16, device=DEV)
+    xin = torch.full((n, h, w, in_ct), float("nan"), dtype=torch.bfloat16, device=DEV)      # NaN next to the view: a read past cin shows
     xin[..., in_co:in_co + cin] = _nhwc(x)
     out_ct, out_co = cout + 8, 8
     wp, bp, kpad, cout_pad = K.pack_conv_weight(wt, bias, cin)
