@@ -20,8 +20,11 @@
 // A bit without a name below is tested nowhere.  Of the named ones, the recipes of tests/_exact_cases.py launch the gather-kernel
 // instances behind knob 0 (variants 0, 3, 5, 7, 8, 9, 10, 11) and behind kCdNoLdsEpilogue, kCdNoLoaderWaves, kCd256x256EightWaves,
 // kCdMfma32x32, kCdFourWaves, kCdLoadersTwoStages, kCd64x64TwoStages and kCdStreamFirstForm, and compare them bit for bit
-// (tests/test_conv_exact_gpu.py); kFamT20Always / kFamT20Never, kFamStreamAlways / kFamStreamNever and the form bits of knobs 3 and 4
-// have their cases in tests/test_gpu_parity.py.  The ablation bits give wrong results by design and have no test.
+// (tests/test_conv_exact_gpu.py); kFamT20Always / kFamT20Never and kFamStreamAlways / kFamStreamNever have their cases there and in
+// tests/test_gpu_parity.py.  The form bits of knobs 3 and 4 (kRuGeneric64, kRuT20Always, kRuT20Never, kMbStripForm) select the fused
+// kernels of the chained bit-exact cases (tests/_exact_cases.py, tests/test_fused_exact_gpu.py); kMbStripForm also runs, with the
+// shipped rules of knob 3, on the real activation scales in tests/test_gpu_parity.py.  The ablation bits give wrong results by
+// design and have no test.
 #pragma once
 
 struct Tuning {

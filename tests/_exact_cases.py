@@ -6,7 +6,22 @@ output view: "v8" puts every view at an 8-channel offset inside a wider buffer (
 output at a 4-channel offset (only the direct epilogue can).  Rules every forced shape keeps, so that no kernel reads outside what the
 host checks describe: cin % 64 == 0 and cout > 64 wherever knob 0 is >= 0, cout a multiple of 256 for the 256-cout-wide tiles and of
 128 for the 128-wide ones under a forced variant; a ragged cout (255, 100, 40, 24, 16) appears only where the shipped rule itself
-hands it to the instance.  Every shape has a partial last pixel tile and at least two K steps."""
+hands it to the instance.  Every shape has a partial last pixel tile and at least two K steps.
+
+The second half holds the chained cases of the kernels that fuse several layers into one launch (tests/test_fused_exact_cpu.py runs
+their references' guards and sensitivity checks, tests/test_fused_exact_gpu.py launches them).  Forced-shape rules there:
+  * fused residual units: every map passes yolo_resunit_supported (>= 80x80 pixels, 16x16 tiles covering >= 85 %).  The form bits of
+    knob 3 only choose AMONG kernels that compute any supported unit: kRuT20Always drops the tile-count and cover conditions of
+    resunit_t20_applies (a speed rule), kRuT20Never / kRuGeneric64 fall back to the generic 16x16-tile kernel.  No bit lifts a host
+    check.  The library has no query that names the kernel a unit takes (the pick mode is reachable through yolo_conv2d_pick only), so
+    the cases rely on the knob; the default-rule case is checked against yolo_resunit_form.
+  * inverted residuals: knob 4 bit kMbStripForm ASKS for the row-strip form; launch_strip (csrc/conv_mbconv.hip) declines a block it
+    cannot hold and the tile form runs instead, silently.  strip_takes() below repeats its conditions, and every "strip" case must
+    pass it: at stride 1 the strip form holds at most 128 padded hidden channels, at stride 2 its LDS rings end at 128 as well - so the
+    144-hidden blocks of test_fused_inverted_residual never reach it, and the strip row "hidden not a multiple of 32" is a block of its
+    own (24-80-24).  The wide form's tiling follows from the shape alone (yolo_mbwide_launch): stride 2 -> 7x7; stride 1 -> 13x13 when
+    cin <= 96, cout <= 128 and there are >= 192 tiles of 13x13, else 7x7.
+  * the stem takes stem2_kernel for 3 input channels and stem_kernel otherwise; conv + pool has one kernel per (cin, cout) pair."""
 import os
 import re
 
@@ -127,3 +142,121 @@ FAMILY_CASES = [
 
 def case_id(shape):
     return "n%d_%dx%d_c%d-%d_k%d_s%d_%s_r%d_a%d_u%d_f%d" % tuple(int(v) if not isinstance(v, str) else v for v in shape)
+
+
+# ---- chained cases of the fused multi-conv kernels ------------------------------------------------------------------------------------
+RU_GENERIC64, RU_T20_ALWAYS, RU_T20_NEVER = 32, 64, 128       # kRu* form bits (knob 3)
+MB_STRIP = 128                                                 # kMbStripForm (knob 4)
+
+
+def _u(kernel, c, knob3, n, h, w, act, tile, seed):
+    return dict(kernel=kernel, c=c, knob3=knob3, shape=(n, h, w, c, act), tile=tile, seed=seed)
+
+
+# 94x100 is the smallest map yolo_resunit_supported accepts with partial 16x16 tiles in both directions (6x7 tiles, last row of 14,
+# last column of 4) and a partial last row of 20x20 / 8x20 tiles (14 / 6 rows); its width is five whole tiles of 20, so the
+# 20-pixel-wide kernels get 94x101 as well (a last tile column of ONE pixel).  n = 7 gives the persistent kernel 294 tiles, more than
+# the chip has CUs: its loop and prefetch run.  Every case runs with and without the pre-add copy.
+# Achieved shares of the references (LeakyReLU, C = 64 / 128 / 256): 21-32 % negative before the first activation, 39-51 % before the
+# second; 50-56 % of the intermediate beyond 256, 13-18 % of it needs rounding (13-16 % ties); 91-96 % of the outputs and of the
+# pre-add copy need rounding, 3.1-5.8 % are ties.  ReLU6: intermediate 25-28 % at 0, 17-21 % at 6, 26-39 % need rounding; second
+# activation 17-24 % at 0, 27-29 % at 6; 36-40 % of the outputs need rounding, 8.5-10 % are ties.
+UNIT_CASES = [
+    _u("resunit64_persistent", 64, 0, 7, 94, 100, "leaky", (16, 16), 101),
+    _u("resunit_generic16_c64", 64, RU_GENERIC64, 2, 94, 100, "leaky", (16, 16), 102),
+    _u("resunit64_t20", 64, RU_T20_ALWAYS, 2, 94, 100, "leaky", (20, 20), 102),
+    _u("resunit_generic16_c128", 128, RU_T20_NEVER, 2, 94, 100, "leaky", (16, 16), 103),
+    _u("resunit_t20w_c128", 128, RU_T20_ALWAYS, 2, 94, 100, "leaky", (20, 20), 103),
+    _u("resunit_generic16_c256", 256, RU_T20_NEVER, 2, 94, 100, "leaky", (16, 16), 104),
+    _u("resunit_t20w_c256", 256, RU_T20_ALWAYS, 2, 94, 100, "leaky", (8, 20), 104),
+    _u("resunit64_t20_w101", 64, RU_T20_ALWAYS, 2, 94, 101, "leaky", (20, 20), 105),
+    _u("resunit_t20w_c128_w101", 128, RU_T20_ALWAYS, 2, 94, 101, "leaky", (20, 20), 106),
+    _u("resunit_t20w_c256_w101", 256, RU_T20_ALWAYS, 2, 94, 101, "leaky", (8, 20), 107),
+    _u("resunit_generic16_c128_relu6", 128, RU_T20_NEVER, 2, 94, 100, "relu6", (16, 16), 108),
+    _u("resunit64_t20_relu6", 64, RU_T20_ALWAYS, 2, 94, 100, "relu6", (20, 20), 109),
+]
+
+# (kernel, (n, cin, h, w, act), output tile, seed).  stem2_kernel walks tiles of 8x16 outputs, stem_kernel of 16x16.  Achieved shares
+# (LeakyReLU): 23-28 % / 44-54 % negative before the two activations, 11-16 % of the intermediate need rounding (11-15 % ties),
+# 91-92 % of the outputs do, 5-9 % are ties (the 2x2 image has 64 outputs: its seed is one whose reference clears the 2 % of ties).
+# ReLU6: intermediate 25 % at 0, 17 % at 6, 38 % need rounding; output 22 % / 19 % at the clamps, 42 % need rounding, 14 % ties.
+STEM_CASES = [
+    ("stem2", (1, 3, 2, 2, "leaky"), (8, 16), 203),
+    ("stem2", (1, 3, 33, 17, "leaky"), (8, 16), 202),
+    ("stem2", (2, 3, 70, 106, "leaky"), (8, 16), 203),
+    ("stem_one_role", (2, 1, 37, 50, "leaky"), (16, 16), 204),
+    ("stem2", (1, 3, 33, 17, "relu6"), (8, 16), 205),
+]
+
+# (form, (n, h, w, cin, hidden, cout, stride), output tile).  Every block of test_fused_inverted_residual with at most about 100 000
+# input pixels x channels per image - all but 4x104x104, 12x52x52, 3x104x104, 2x61x83 and 2x57x70, which are larger, and 70x26x26 and
+# 20x28x28, whose 70 and 20 images only repeat a tiling the table has; 13x50x45 is larger too and stays, no smaller block selects the
+# 13x13 tiling -, plus 24-80-24 (see the header) and 5x57x61 24-144-24: 320 tiles of 8x8 on 256 workgroups (the tile form's
+# persistent loop).  Achieved shares: expand output 25-28 % at 0, 16-22 % at 6, 33-45 % need rounding (10-14 % ties);
+# depthwise output 47-61 % at 0, 26-41 % at 6, 6-11 % need rounding (without expand conv: 25 % / 19-20 % at the clamps, 30-37 % need
+# rounding); block output 88-96 % need rounding, 2.7-8.4 % ties.
+MBCONV_CASES = [
+    ("tile", (2, 26, 30, 32, 32, 16, 1), (8, 8)),        # no expand conv
+    ("tile", (2, 40, 36, 16, 96, 24, 2), (4, 8)),        # stride 2, cout not a multiple of 16
+    ("tile", (1, 23, 19, 24, 144, 24, 1), (8, 8)),       # residual, hidden not a multiple of 32
+    ("tile", (3, 33, 41, 24, 144, 32, 2), (4, 8)),
+    ("tile", (2, 16, 24, 32, 192, 32, 1), (4, 8)),       # residual, the half tile of the 192-hidden blocks
+    ("tile", (1, 52, 52, 32, 192, 64, 2), (4, 8)),
+    ("tile", (3, 30, 26, 32, 32, 32, 1), (8, 8)),        # residual without expand conv
+    ("tile", (2, 24, 40, 16, 64, 16, 1), (8, 8)),
+    ("tile", (5, 52, 52, 32, 192, 32, 1), (4, 8)),       # residual, 455 half tiles
+    ("tile", (5, 57, 61, 24, 144, 24, 1), (8, 8)),       # more tiles than workgroups
+    ("strip", (2, 26, 30, 32, 32, 16, 1), (8, 26)),      # no expand conv, two column segments
+    ("strip", (2, 40, 36, 16, 96, 24, 2), (8, 26)),      # stride 2, cout not a multiple of 16
+    ("strip", (3, 30, 26, 32, 32, 32, 1), (8, 26)),      # residual without expand conv
+    ("strip", (2, 24, 40, 16, 64, 16, 1), (8, 26)),      # residual, two column segments
+    ("strip", (2, 21, 31, 24, 80, 24, 1), (8, 26)),      # residual, hidden not a multiple of 32, cout not a multiple of 16
+    ("strip", (1, 52, 52, 32, 128, 64, 2), (8, 26)),     # the widest stride-2 block the strip form holds
+    ("wide13", (13, 50, 45, 96, 192, 96, 1), (13, 13)),  # partial tiles at both edges, residual
+    ("wide7", (2, 26, 26, 64, 128, 96, 1), (7, 7)),
+    ("wide7", (3, 13, 13, 160, 320, 160, 1), (7, 7)),    # five K steps, residual
+    ("wide7", (2, 13, 13, 160, 192, 320, 1), (7, 7)),    # 20 cout tiles: the only block with cout > 160
+    ("wide7", (2, 26, 26, 96, 192, 160, 2), (7, 7)),     # stride 2
+    ("wide7", (1, 27, 23, 64, 192, 24, 2), (7, 7)),      # stride 2, odd sizes, cout not a multiple of 16
+]
+MBCONV_SEED = 301
+
+
+def strip_takes(cin, hidden, cout, stride):
+    """launch_strip's conditions (csrc/conv_mbconv.hip, MbStrip<S>, strip_lds_bytes): does the row-strip form hold the block?
+    A copy BY HAND - the library has no query for it - of MbStrip's constants (25 output columns per segment, NE = 384, NDW = 512,
+    kXStride = 96, five x-ring rows), launch_strip's conditions and strip_lds_bytes' sum.  Whoever changes one of those in the C++
+    changes it here: if the two drift apart, a "strip" case can run the tile form and nothing will show it."""
+    expand = hidden != cin
+    ce, cop = (hidden + 31) // 32 * 32, (cout + 15) // 16 * 16
+    iw = 25 * stride + 3
+    iwf = (iw + 15) // 16
+    iws, iwe = iwf * 16, 40 if stride == 1 else (iw + 7) // 8 * 8
+    re_, rne, ne, ndw = 4 if stride == 1 else 5, 6 if stride == 1 else 8, 384, 512
+    npx = (3 * iw * 4 + ne - 1) // ne
+    if cin % 8 or cin > 32 or 3 * iw * (cin // 8) > npx * ne or cop > 64 or ((ce // 2) * 7 if stride == 1 else ce // 4) > ndw:
+        return False
+    dstride = ce * 2
+    while dstride % 256 not in (96, 160):
+        dstride += 16
+    estride = ce * 2 + (8 if expand else 0)
+    lds = (5 * iws * 96 if expand else 0) + (re_ if expand else rne) * iwe * estride + 2 * 32 * dstride + (ce * 96 if expand else 0) + \
+        cop * dstride + (ce + cop) * 4 + (3 * iwf * (ce // 16) * 4 if expand else 0)
+    return lds <= 160 * 1024
+
+
+def wide_tiling(n, h, w, cin, cout, stride):
+    """yolo_mbwide_launch's choice (csrc/conv_mbwide.hip) up to its LDS condition, which every 13x13 case of the table meets.
+    A copy by hand as well (no query names the tiling): keep it in step with the C++ rule, LDS condition included if a 13x13 case
+    near that limit is ever added."""
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    t13 = n * ((ho + 12) // 13) * ((wo + 12) // 13)
+    return "wide13" if stride == 1 and cin <= 96 and (cout + 15) // 16 * 16 <= 128 and t13 >= 192 else "wide7"
+
+
+# conv3x3 + MaxPool2d(2, 2) (csrc/conv_small.hip): every (cin, cout) pair with the pool, at odd sizes - the pool takes the floor, the
+# last odd row / column is computed and dropped -, and every pair without (each (cin, cout, pool) is a template instantiation of its
+# own); n, h, w, cin, cout, pool
+POOL_CASES = [(2, 26, 38, 16, 32, True), (1, 21, 19, 16, 64, True), (1, 21, 19, 32, 32, True), (2, 26, 38, 32, 64, True),
+              (1, 21, 19, 16, 32, False), (2, 26, 38, 16, 64, False), (1, 21, 19, 32, 32, False), (1, 21, 19, 32, 64, False)]
+POOL_SEED = 6

@@ -233,3 +233,230 @@ def exact_conv(shape, seed, dtype, up=False, f32_out=False):
         y, aux = exact_conv_reference(x, wt, bias, res, stride=shape[6], act=shape[7], up=up, dtype=dtype, f32_out=f32_out)
         _EXACT_CACHE[key] = (x, wt, bias, res, y, aux)
     return _EXACT_CACHE[key]
+
+
+# ---- chained exact cases: the fused multi-conv kernels ----------------------------------------------------------------------------
+# The fused kernels narrow an intermediate map to bf16 and feed it to a second conv, so the intermediate must again consist of values
+# whose products and partial sums are exact in fp32 in any order.  Two constructions (case generators below):
+#   * LeakyReLU: x = 10 * small integer, integer w1, b1 = 10 * integer: every pre-activation is 10 k, and the fp32 product 0.1f * 10 k
+#     rounds to exactly k (0.1f is off by 1.5e-8 relative, below the smallest half-ulp 3e-8): the intermediate is all integers, and
+#     past 512 bf16 must round them.  The second conv has w2 in {-1, 0, 1}.  unit = 1.
+#   * ReLU6: everything in units of 2^-8 - x = {-3..3} / 16, integer weights, biases k / 256; the clamp keeps the intermediates in
+#     [0, 6], where multiples of 2^-8 from 1 on need rounding.  unit = 2^-8.
+_CHAIN_CACHE = {}
+_BF16 = torch.bfloat16
+
+
+def _apply_act(v, act):
+    if act == "leaky":
+        return torch.where(v > 0, v, torch.tensor(0.1, dtype=torch.float32) * v)      # one fp32 multiply, no fma
+    if act == "relu6":
+        return v.clamp(0.0, 6.0)
+    assert act == "none", act
+    return v
+
+
+def _zero_pad(a, pad, border=None, neighbours=False):
+    """a [n, c, h, w] with an explicit frame of `pad` pixels: zeros - or, for the sensitivity checks, `border` [c] (what a kernel would
+    hold there had it computed the producing conv on zero-padded input) / the first and last rows of the neighbouring images."""
+    import torch.nn.functional as F
+    ap = F.pad(a, (pad, pad, pad, pad))
+    if border is not None:
+        ap = border.view(1, -1, 1, 1).expand_as(ap).clone()
+        ap[:, :, pad:-pad, pad:-pad] = a
+    if neighbours:
+        assert a.shape[0] >= 2 and pad == 1
+        ap[:-1, :, -1, 1:-1] = a[1:, :, 0, :]        # below the last row: the next image's first row
+        ap[1:, :, 0, 1:-1] = a[:-1, :, -1, :]        # above the first row: the previous image's last row
+    return ap
+
+
+def exact_chain_reference(x, stages, res=None, *, unit, fault=None, fault_stage=None, tile=(16, 16)):
+    """(y bf16, pre-add copy bf16, stats) of a chain of convs as the fused kernels run it: every stage is conv + bias in fp32,
+    activation, and - except after the last - one round-to-nearest-even narrowing to bf16; the last stage ends like
+    exact_conv_reference: pre-add copy narrowed from the activation's value, one fp32 add of the residual, one narrowing.
+    stages: (w [co, ci/groups, k, k], bias [co], stride, groups, act) each; the map a stage reads is zero-padded by (k - 1) / 2.
+    unit: the power of two every operand is a multiple of.
+
+    Without `fault` the case is REJECTED (AssertionError) unless it determines every bit and exercises the rounding:
+      * every stage's operands are multiples of unit, its fp32 conv equals its fp64 conv, and max(conv(|a|, |w|) + |bias| + |res|) stays
+        below 2^24 * unit; a LeakyReLU intermediate is all integers;
+      * >= 15 % of the pre-activations of a LeakyReLU stage are negative; >= 2 % of a ReLU6 stage's values sit at each clamp;
+      * >= 1 % of every narrowed intermediate needs rounding;
+      * at the final narrowing and at the pre-add copy >= 25 % need rounding and >= 2 % are exact ties.
+    stats: {name: share} of all of these, for the comments beside the case tables.
+
+    fault (sensitivity checks of tests/test_fused_exact_cpu.py, no guards): what a subtly wrong kernel would compute instead -
+      "drop_tap_row" / "drop_tap_col"  the 3x3 stage `fault_stage` loses its tap below / right of the centre on the last row / column
+                                       of every tile of tile[0] x tile[1] outputs
+      "trunc_mid" / "wide_mid"         the intermediate stage `fault_stage` reads is narrowed by truncation / not narrowed
+      "aux_after_add"                  the pre-add copy is taken after the residual add
+      "halo_neighbour"                 the padding rows of stage `fault_stage`'s input hold the neighbouring images' rows
+      "pad_act_bias"                   ... hold act(bias) of the producing stage instead of zero
+    fault_stage defaults to the last 3x3 stage."""
+    import torch.nn.functional as F
+    assert fault in (None, "drop_tap_row", "drop_tap_col", "trunc_mid", "wide_mid", "aux_after_add", "halo_neighbour", "pad_act_bias")
+    guard = fault is None
+    stats, bad = {}, []
+    if fault_stage is None:
+        fault_stage = max(i for i, st in enumerate(stages) if st[0].shape[-1] == 3)
+    a = x
+    assert torch.equal(a.to(_BF16).float(), a), "x is not representable in bf16"
+    with torch.no_grad():
+        for i, (wt, bias, stride, groups, act) in enumerate(stages):
+            last = i == len(stages) - 1
+            k = wt.shape[-1]
+            pad = (k - 1) // 2
+            here = fault is not None and i == fault_stage
+            border = None
+            if here and fault == "pad_act_bias":
+                border = _apply_act(stages[i - 1][1], stages[i - 1][4]).to(_BF16).float()
+            ap = _zero_pad(a, pad, border, here and fault == "halo_neighbour") if pad else a
+            v = F.conv2d(ap, wt, bias, stride=stride, groups=groups)
+            if guard:
+                for t in (ap, wt, bias):
+                    assert torch.equal((t / unit).round() * unit, t), f"stage {i}: an operand is no multiple of the unit"
+                v64 = F.conv2d(ap.double(), wt.double(), bias.double(), stride=stride, groups=groups)
+                assert v.dtype == torch.float32 and torch.equal(v.double(), v64), f"stage {i}: the fp32 conv is not exact"
+                bound = F.conv2d(ap.abs().double(), wt.abs().double(), bias.abs().double(), stride=stride, groups=groups)
+                if last and res is not None:
+                    bound = bound + res.abs().double()
+                assert float(bound.max()) < 2.0 ** 24 * unit, f"stage {i}: a partial sum can leave the exact range of fp32"
+            if here and fault in ("drop_tap_row", "drop_tap_col"):
+                assert k == 3
+                one = torch.zeros_like(wt)
+                ky, kx = (2, 1) if fault == "drop_tap_row" else (1, 2)
+                one[:, :, ky, kx] = wt[:, :, ky, kx]
+                lost = F.conv2d(ap, one, None, stride=stride, groups=groups)
+                rows, cols = torch.arange(v.shape[2]), torch.arange(v.shape[3])
+                edge = (rows % tile[0] == tile[0] - 1).view(-1, 1).expand(-1, len(cols)) if fault == "drop_tap_row" else \
+                    (cols % tile[1] == tile[1] - 1).view(1, -1).expand(len(rows), -1)
+                v = v - lost * edge.float()
+            if guard and act == "leaky":
+                stats[f"s{i}_negative"] = float((v < 0).float().mean())
+                if stats[f"s{i}_negative"] < 0.15:
+                    bad.append(f"stage {i}: too few pre-activations are negative")
+            v = _apply_act(v, act)
+            if guard and act == "relu6":
+                stats[f"s{i}_at0"], stats[f"s{i}_at6"] = float((v == 0).float().mean()), float((v == 6).float().mean())
+                if min(stats[f"s{i}_at0"], stats[f"s{i}_at6"]) < 0.02:
+                    bad.append(f"stage {i}: too few values at a clamp")
+            if last:
+                break
+            if guard:
+                if act == "leaky":
+                    assert torch.equal(v, v.round()), f"stage {i}: the LeakyReLU intermediate is not all integers"
+                nonrep, ties = exact_rounding_shares(v, _BF16)
+                stats[f"s{i}_nonrep"], stats[f"s{i}_ties"] = nonrep, ties
+                stats[f"s{i}_beyond256"] = float((v.abs() >= 256).float().mean())
+                if nonrep < 0.01:
+                    bad.append(f"stage {i}: too little of the intermediate needs rounding")
+            nxt = fault is not None and i + 1 == fault_stage
+            if nxt and fault == "trunc_mid":
+                a = (v.contiguous().view(torch.int32) & -65536).view(torch.float32)
+            elif nxt and fault == "wide_mid":
+                a = v
+            else:
+                a = v.to(_BF16).float()
+        pre = v
+        if res is not None:
+            assert torch.equal(res.to(_BF16).float(), res)
+            v = v + res                                                                # one fp32 add
+        if guard:
+            for name, t in (("out", v), ("aux", pre)):
+                nonrep, ties = exact_rounding_shares(t, _BF16)
+                stats[f"{name}_nonrep"], stats[f"{name}_ties"] = nonrep, ties
+                if nonrep < 0.25 or ties < 0.02:
+                    bad.append(f"{name}: too few values need rounding or are ties")
+            assert not bad, f"the case does not exercise the rounding: {bad}; shares {stats}"
+        aux = (v if fault == "aux_after_add" else pre).to(_BF16)
+    return v.to(_BF16), aux, stats
+
+
+def _ri(g):
+    return lambda lo, hi, *size: torch.randint(lo, hi + 1, size, generator=g).float()
+
+
+def _relu6_bias(ri, c, spread, period=4, lo=256):
+    """Bias [c] in units of 2^-8 for a ReLU6 stage whose conv sum has about `spread` (in units of 1) standard deviation: one channel in
+    `period` sits well below 0, one straddles 6, the others lie inside [lo / 256, 5)."""
+    ch = torch.arange(c)
+    b = ri(lo, 5 * 256 - 1, c)
+    b = torch.where(ch % period == 1, ri(-int(256 * (2 + spread)), -256, c), b)
+    b = torch.where(ch % period == period - 1, ri(6 * 256 - 60, 6 * 256 + int(256 * spread), c), b)
+    return b / 256.0
+
+
+def exact_unit_case(shape, seed):
+    """(x, stages, res, unit) of a fused residual unit, shape = (n, h, w, c, act): 1x1 c -> c/2, 3x3 c/2 -> c, + x."""
+    n, h, w, c, act = shape
+    g = torch.Generator().manual_seed(seed)
+    ri = _ri(g)
+    m = c // 2
+    if act == "leaky":
+        x = 10.0 * ri(-2, 2, n, c, h, w)
+        w1 = ri(-3, 3, m, c, 1, 1)
+        # the sum has a standard deviation of about 28 sqrt(c); the bias moves every second channel's values towards and past 512
+        b1 = 10.0 * torch.where(torch.arange(m) % 2 == 0, ri(30, 75, m), ri(-20, 20, m))
+        w2, b2 = ri(-1, 1, c, m, 3, 3), ri(-400, 400, c)
+        return x, [(w1, b1, 1, 1, act), (w2, b2, 1, 1, act)], x, 1.0
+    assert act == "relu6"
+    x = ri(-3, 3, n, c, h, w) / 16.0
+    w1 = ri(-2, 2, m, c, 1, 1)
+    b1 = _relu6_bias(ri, m, 0.18 * c ** 0.5)
+    # (the intermediate is >= 0, about 2 on average: a dense 3x3 over c/2 channels would put every output at a clamp)
+    w2 = ri(-1, 1, c, m, 3, 3) * (torch.rand(c, m, 3, 3, generator=g) < 2.0 / (9 * m)).float()
+    b2 = _relu6_bias(ri, c, 2.0, period=8, lo=640)
+    return x, [(w1, b1, 1, 1, act), (w2, b2, 1, 1, act)], x, 2.0 ** -8
+
+
+def exact_stem_case(shape, seed):
+    """(x float32 NCHW, stages, None, unit) of the fused stem, shape = (n, cin, h, w, act): 3x3 cin -> 32, 3x3 / s2 32 -> 64."""
+    n, cin, h, w, act = shape
+    g = torch.Generator().manual_seed(seed)
+    ri = _ri(g)
+    if act == "leaky":
+        x = 10.0 * ri(-3, 3, n, cin, h, w)
+        w1 = ri(-3, 3, 32, cin, 3, 3) * (3.0 if cin == 1 else 1.0)
+        b1 = 10.0 * torch.where(torch.arange(32) % 2 == 0, ri(35, 75, 32), ri(-10, 10, 32))
+        w2, b2 = ri(-1, 1, 64, 32, 3, 3), ri(-400, 400, 64)
+        return x, [(w1, b1, 1, 1, act), (w2, b2, 2, 1, act)], None, 1.0
+    assert act == "relu6"
+    x = ri(-3, 3, n, cin, h, w) / 16.0
+    w1 = ri(-3, 3, 32, cin, 3, 3)
+    b1 = _relu6_bias(ri, 32, 1.2)
+    w2 = ri(-1, 1, 64, 32, 3, 3) * (torch.rand(64, 32, 3, 3, generator=g) < 2.0 / 288).float()
+    b2 = _relu6_bias(ri, 64, 2.0, period=8, lo=640)
+    return x, [(w1, b1, 1, 1, act), (w2, b2, 2, 1, act)], None, 2.0 ** -8
+
+
+def exact_mbconv_case(shape, seed):
+    """(x, stages, res, unit) of an inverted-residual block, shape = (n, h, w, cin, hidden, cout, stride): [1x1 cin -> hidden, ReLU6,]
+    depthwise 3x3 / stride, ReLU6, 1x1 hidden -> cout [+ x]."""
+    n, h, w, cin, hidden, cout, stride = shape
+    g = torch.Generator().manual_seed(seed)
+    ri = _ri(g)
+    x = ri(-3, 3, n, cin, h, w) / 16.0
+    stages = []
+    if hidden != cin:
+        stages.append((ri(-2, 2, hidden, cin, 1, 1), _relu6_bias(ri, hidden, 0.18 * cin ** 0.5), 1, 1, "relu6"))
+    # without an expand conv the depthwise conv reads x itself (|x| <= 3/16): larger weights and a bias that reaches both clamps
+    wd = ri(-2, 2, hidden, 1, 3, 3) * (1.0 if hidden != cin else 4.0)
+    bd = _relu6_bias(ri, hidden, 3.0 if hidden != cin else 1.0)
+    stages.append((wd, bd, stride, hidden, "relu6"))
+    stages.append((ri(-2, 2, cout, hidden, 1, 1), ri(-3 * 256, 3 * 256, cout) / 256.0, 1, 1, "none"))
+    return x, stages, x if (stride == 1 and cin == cout) else None, 2.0 ** -8
+
+
+_CHAIN_CASES = {"unit": exact_unit_case, "stem": exact_stem_case, "mbconv": exact_mbconv_case}
+
+
+def exact_chain(kind, shape, seed):
+    """An exact chained case and its guarded reference, computed once per process: (x, stages, res, unit, y_ref, aux_ref, stats).
+    Do not modify them."""
+    key = (kind, tuple(shape), seed)
+    if key not in _CHAIN_CACHE:
+        x, stages, res, unit = _CHAIN_CASES[kind](shape, seed)
+        y, aux, stats = exact_chain_reference(x, stages, res, unit=unit)
+        _CHAIN_CACHE[key] = (x, stages, res, unit, y, aux, stats)
+    return _CHAIN_CACHE[key]
