@@ -313,6 +313,31 @@ YOLO_API int yolo_pack_input_nchw_f32_nhwc(const float* x, float* y, int n, int 
 YOLO_API int yolo_pack_conv_weight_f32_f32(const float* w_oihw, int cout, int cin_w, int ksize, int cin, int cout_pad, int kpad,
                                            float* out);
 
+/* ---- fp32 mode, the depthwise encoder families (csrc/efficient_f32.hip): float32 NHWC views in multiples of 4 channels, float32
+ *  arithmetic, expf and an IEEE division in the activations, fmaf chains in a fixed order (no result depends on the grid).
+ *  yolo_dwconv_f32_fwd: depthwise k x k conv (k = 3 or 5, stride 1 or 2) + bias + act (any YOLO_ACT_*) with an explicit leading pad
+ *  and the caller's ho x wo, everything outside the image reads zero - arguments and geometry rule of yolo_dwconv_fwd.  One entry
+ *  point for torch's pad 1 (ksize 3, pad 1, ho = (h - 1) / stride + 1: torchvision's InvertedResidual behind
+ *  models/yolov3_tiny_mobilenet.py:11-34 and the ShuffleNetV2 units behind models/yolov3_tiny_shuffle.py:13-47) and TensorFlow "same"
+ *  (efficientnet_pytorch 0.2.0 Conv2dSamePadding, MBConvBlock._depthwise_conv behind models/yolov3_tiny_efficient.py:22-45:
+ *  pad = pad_total / 2, ho = ceil(h / stride)).  w: f32 [k*k][c] tap-major, bias f32 [c]. */
+YOLO_API int yolo_dwconv_f32_fwd(const float* x, const float* w, const float* bias, float* y, int n, int h, int w_, int c,
+                                 int in_c_total, int in_c_offset, int ho, int wo, int out_c_total, int out_c_offset, int ksize,
+                                 int stride, int pad, int act, yolo_stream_t s);
+/* yolo_se_f32_fwd: squeeze-and-excitation of an MBConvBlock (efficientnet_pytorch 0.2.0 model.py, used through
+ *  models/yolov3_tiny_efficient.py:47-56) exactly as yolo_se_fwd, on float32 views (y may be x); weights as there; workspace:
+ *  yolo_se_workspace_bytes(n, c) bytes with the same layout (the pooled means stay in its first n*c floats).  The partial sums of
+ *  the pooling pass meet in a fixed order: bit-identical from run to run. */
+YOLO_API int yolo_se_f32_fwd(const float* x, float* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int out_c_total,
+                             int out_c_offset, const float* w1, const float* b1, const float* w2, const float* b2, int squeeze,
+                             void* workspace, size_t ws_bytes, yolo_stream_t s);
+/* yolo_channel_shuffle2_f32_fwd: ShuffleNetV2's channel_shuffle(cat(a, b), groups = 2) (torchvision shufflenetv2, used by
+ *  models/yolov3_tiny_shuffle.py:13-47) in the two-slot physical layout of yolo_channel_shuffle2_fwd, on float32 views; c_slot and
+ *  the view of y are multiples of 4 channels; the pad channels of both slots of y are written as zero. */
+YOLO_API int yolo_channel_shuffle2_f32_fwd(const float* a, const float* b, float* y, int n, int h, int w, int half, int c_slot,
+                                           int a_c_total, int a_c_offset, int b_c_total, int b_c_offset, int y_c_total,
+                                           int y_c_offset, yolo_stream_t s);
+
 /* ---- fp16-operand mode (model.precision = "fp16"): the rounding points of the bf16 path with IEEE half instead - fp16 NHWC
  *  activations and packed weights (same bytes and layout as bf16), fp32 accumulation on v_mfma_f32_16x16x32_f16 /
  *  v_mfma_f32_32x32x16_f16, the residual sum formed in fp32 and stored once, fp32 head outputs.  Narrowing: round to nearest even; a
@@ -366,7 +391,10 @@ enum { YOLO_OP_CONV = 1, YOLO_OP_MAXPOOL = 2, YOLO_OP_SPP = 3, YOLO_OP_DWCONV = 
        YOLO_OP_CONV_F16 = 16 /* yolo_conv2d_f16_fwd */, YOLO_OP_MAXPOOL_F16 = 17 /* yolo_maxpool_f16_fwd, fields as MAXPOOL */,
        YOLO_OP_HEAD_DECODE_F16 = 18 /* yolo_head_decode_f16_fwd / yolo_head_decode_filter_f16_fwd, fields as HEAD_DECODE */,
        YOLO_OP_CONV_T20_F16 = 19 /* yolo_conv3x3_t20_f16_fwd with force = 1 (the list's builder asked yolo_conv3x3_t20_f16_supported),
-                                    fields as CONV_F16 */ };
+                                    fields as CONV_F16 */,
+       YOLO_OP_DWCONV_F32 = 20 /* yolo_dwconv_f32_fwd, fields as DWCONV; conv.ksize / conv.pad always the real ones (3 / 1 for the
+                                  torch-style layers): there is no ksize 0 form */,
+       YOLO_OP_SE_F32 = 21 /* yolo_se_f32_fwd, fields as SE */, YOLO_OP_SHUFFLE_F32 = 22 /* yolo_channel_shuffle2_f32_fwd, fields as SHUFFLE */ };
 typedef struct YoloOp {
   int32_t kind, _pad;
   const void* x; const void* w; const float* bias; const void* residual; void* y; void* y_aux;

@@ -18,6 +18,7 @@ OP_CONV, OP_MAXPOOL, OP_SPP, OP_DWCONV, OP_CONV1_NCHW, OP_RESUNIT, OP_STEM, OP_H
 OP_MBCONV, OP_CONV_POOL, OP_SHUFFLE, OP_CONV_F32, OP_MAXPOOL_F32, OP_SE = 10, 11, 12, 13, 14, 15
 OP_CONV_F16, OP_MAXPOOL_F16, OP_HEAD_DECODE_F16 = 16, 17, 18          # the fp16-operand mode
 OP_CONV_T20_F16 = 19                                                  # ... its large 3x3 layers on the 20x20-tile kernels
+OP_DWCONV_F32, OP_SE_F32, OP_SHUFFLE_F32 = 20, 21, 22                 # the fp32 mode's depthwise / squeeze-excite / channel-shuffle layers
 
 
 class YoloConvDesc(C.Structure):
@@ -115,6 +116,9 @@ SIGNATURES = {
     "yolo_maxpool_f32_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 14 + [C.c_void_p]),
     "yolo_pack_input_nchw_f32_nhwc": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "yolo_pack_conv_weight_f32_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "yolo_dwconv_f32_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.c_void_p]),
+    "yolo_se_f32_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 8 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_channel_shuffle2_f32_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 11 + [C.c_void_p]),
     "yolo_conv2d_f16_fwd": (C.c_int, [C.c_void_p] * 6 + [C.POINTER(YoloConvDesc), C.c_void_p]),
     "yolo_conv3x3_t20_f16_supported": (C.c_int, [C.POINTER(YoloConvDesc), C.c_int, C.c_int]),
     "yolo_conv3x3_t20_f16_fwd": (C.c_int, [C.c_void_p] * 6 + [C.POINTER(YoloConvDesc), C.c_int, C.c_void_p]),

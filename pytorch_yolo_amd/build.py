@@ -31,6 +31,7 @@ SOURCES = {
     "conv1x1_stream.hip": [],
     "pointwise.hip": [],
     "efficient.hip": [],
+    "efficient_f32.hip": ["-ffp-contract=off"],
     "preprocess.hip": ["-ffp-contract=off"],
     "nms.hip": ["-ffp-contract=off"],
 }

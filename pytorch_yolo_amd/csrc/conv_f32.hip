@@ -252,7 +252,11 @@ extern "C" int yolo_conv2d_f32_fwd(const float* x, const float* w_packed, const 
                "conv_f32: bad output view (cout %d, offset %d, total %d)", d.cout, d.out_c_offset, d.out_c_total);
   YOLO_REQUIRE(d.kpad % F_BK == 0 && d.kpad >= d.ksize * d.ksize * d.cin, "conv_f32: kpad %d must be a multiple of 32 covering K", d.kpad);
   YOLO_REQUIRE(d.cout_pad % F_BN == 0 && d.cout_pad >= d.cout, "conv_f32: cout_pad %d", d.cout_pad);
-  YOLO_REQUIRE(d.ho == (d.h + 2 * d.pad - d.ksize) / d.stride + 1 && d.wo == (d.w + 2 * d.pad - d.ksize) / d.stride + 1,
+  const int ho_std = (d.h + 2 * d.pad - d.ksize) / d.stride + 1, wo_std = (d.w + 2 * d.pad - d.ksize) / d.stride + 1;
+  // one more row / column than the symmetric-pad size = one more zero below / right of the image (TensorFlow "same" padding): the
+  // rule of yolo_conv2d_fwd; the kernel bounds-checks every tap
+  YOLO_REQUIRE((d.ho == ho_std || (d.ho == ho_std + 1 && (d.ho - 1) * d.stride - d.pad < d.h)) &&
+                   (d.wo == wo_std || (d.wo == wo_std + 1 && (d.wo - 1) * d.stride - d.pad < d.w)),
                "conv_f32: output size %dx%d inconsistent with input %dx%d k%d s%d p%d", d.ho, d.wo, d.h, d.w, d.ksize, d.stride, d.pad);
   if (residual) YOLO_REQUIRE(d.res_c_total % 4 == 0 && d.res_c_offset % 4 == 0 && !d.upsample2x, "conv_f32: bad residual view");
   if (y_preadd) YOLO_REQUIRE(d.aux_c_total % 4 == 0 && d.aux_c_offset % 4 == 0, "conv_f32: bad aux view");

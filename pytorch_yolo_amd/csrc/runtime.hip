@@ -107,6 +107,19 @@ extern "C" int yolo_run_ops(const YoloOp* ops, int n_ops, yolo_stream_t s) {
         rc = yolo_maxpool_f32_fwd((const float*)o.x, (float*)o.y, d.n, d.h, d.w, d.cin, d.in_c_total, d.in_c_offset, d.ho, d.wo,
                                   d.out_c_total, d.out_c_offset, d.ksize, d.stride, d.pad, d.upsample2x /* dilation */, s);
         break;
+      case YOLO_OP_DWCONV_F32:
+        rc = yolo_dwconv_f32_fwd((const float*)o.x, (const float*)o.w, o.bias, (float*)o.y, d.n, d.h, d.w, d.cin, d.in_c_total,
+                                 d.in_c_offset, d.ho, d.wo, d.out_c_total, d.out_c_offset, d.ksize, d.stride, d.pad, d.act, s);
+        break;
+      case YOLO_OP_SE_F32:
+        rc = yolo_se_f32_fwd((const float*)o.x, (float*)o.y, d.n, d.h, d.w, d.cin, d.in_c_total, d.in_c_offset, d.out_c_total,
+                             d.out_c_offset, (const float*)o.w, o.bias, (const float*)o.w_pre, o.bias_pre, o.kpad_pre, o.workspace,
+                             o.ws_bytes, s);
+        break;
+      case YOLO_OP_SHUFFLE_F32:
+        rc = yolo_channel_shuffle2_f32_fwd((const float*)o.x, (const float*)o.residual, (float*)o.y, d.n, d.h, d.w, d.cout, d.cin,
+                                           d.in_c_total, d.in_c_offset, d.res_c_total, d.res_c_offset, d.out_c_total, d.out_c_offset, s);
+        break;
       case YOLO_OP_CONV_F16:
         rc = yolo_conv2d_f16_fwd(o.x, o.w, o.bias, o.residual, o.y, o.y_aux, &d, s);
         break;

@@ -2,9 +2,9 @@
 accounting over such an array.
 
 One emitter per launch kind (``EMITTERS``), each returning the op(s) of one launch; ``build_ops`` is the loop over the records
-for every precision (fp32: the same conv emitter with the fp32 packing and op kind, max pools instead of the SPP kernel, no
-kernel for the depthwise / SE / shuffle layers; fp16: the fp16 packing and op kinds, the SPP kernel itself - it orders 16-bit
-patterns -, no kernel for those three layer kinds either; its large 3x3 layers go to the 20x20-tile kernels)."""
+for every precision (fp32: the same emitters with the fp32 packing and op kinds, max pools instead of the SPP kernel; fp16: the
+fp16 packing and op kinds, the SPP kernel itself - it orders 16-bit patterns -, no kernel for the depthwise / SE / shuffle layers;
+its large 3x3 layers go to the 20x20-tile kernels)."""
 from __future__ import annotations
 
 import os
@@ -14,7 +14,7 @@ import torch
 from . import diag
 from . import kernels as K
 from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, DT_BF16, DT_F16, DT_F32, OP_SE, OP_CONV, OP_CONV1_NCHW, OP_CONV_F16, OP_CONV_T20_F16,
-                   OP_CONV_F32, OP_DWCONV, OP_CONV1_POOL, OP_CONV_POOL, OP_HEAD_DECODE_F16, OP_MAXPOOL_F16, OP_MAXPOOL_F32, OP_MBCONV,
+                   OP_CONV_F32, OP_DWCONV, OP_DWCONV_F32, OP_SE_F32, OP_SHUFFLE_F32, OP_CONV1_POOL, OP_CONV_POOL, OP_HEAD_DECODE_F16, OP_MAXPOOL_F16, OP_MAXPOOL_F32, OP_MBCONV,
                    OP_SHUFFLE, OP_HEAD_DECODE, OP_MAXPOOL, OP_RESUNIT, OP_SPP, OP_STEM, YoloOp)
 
 _ACT = {"leaky": ACT_LEAKY01, "relu6": ACT_RELU6, "relu": ACT_RELU, "none": ACT_NONE, "swish": ACT_SWISH}
@@ -156,13 +156,15 @@ def _emit_dwconv(plan, L):
     nd, x, y = L.node, L.src, L.dst
     w, b = nd.attrs["weight"]
     kk = w.shape[2] * w.shape[3]
-    op = _op(OP_DWCONV, x=_ptr(x), y=_ptr(y))
+    op = _op(OP_DWCONV_F32 if plan.f32 else OP_DWCONV, x=_ptr(x), y=_ptr(y))
     op.w, op.bias = _keep(plan, w.detach().float().reshape(x.c, kk).t().contiguous(), b.detach().float().contiguous())
     d = op.conv
     _in_view(d, x)
     _out_view(d, y)
     d.stride, d.act = nd.attrs["stride"], _ACT[nd.attrs["act"]]
     d.ksize, d.pad = nd.attrs.get("ksize", 0), nd.attrs.get("pad", 0)      # ksize 0: the 3x3 / pad 1 strip kernel
+    if plan.f32:                                                           # one fp32 kernel: the torch-style layers are k 3 / pad 1
+        d.ksize, d.pad = nd.attrs.get("ksize", 3), nd.attrs.get("pad", 1)
     return [op]
 
 
@@ -171,7 +173,7 @@ def _emit_se(plan, L):
     sq = nd.attrs["w1"].shape[0]
     f = lambda t: t.detach().float()
     ws_bytes = K.se_workspace_bytes(x.n, x.c) // 4 * 4
-    op = _op(OP_SE, x=_ptr(x), y=_ptr(y), kpad_pre=sq, ws_bytes=ws_bytes)
+    op = _op(OP_SE_F32 if plan.f32 else OP_SE, x=_ptr(x), y=_ptr(y), kpad_pre=sq, ws_bytes=ws_bytes)
     op.w, op.w_pre, op.bias, op.bias_pre, op.workspace = _keep(plan, f(nd.attrs["w1"]).reshape(sq, x.c).contiguous(),
                                f(nd.attrs["w2"]).reshape(x.c, sq).t().contiguous(),    # [sq][c]
                                f(nd.attrs["b1"]).contiguous(), f(nd.attrs["b2"]).contiguous(),
@@ -184,7 +186,7 @@ def _emit_se(plan, L):
 def _emit_shuffle(plan, L):
     nd, y = L.node, L.dst
     a_, b_ = nd.srcs
-    op = _op(OP_SHUFFLE, x=_ptr(a_), residual=_ptr(b_), y=_ptr(y))
+    op = _op(OP_SHUFFLE_F32 if plan.f32 else OP_SHUFFLE, x=_ptr(a_), residual=_ptr(b_), y=_ptr(y))
     d = op.conv
     _in_view(d, a_)                                                         # cin = physical channels per slot
     d.res_c_total, d.res_c_offset = b_.buf.c_total, b_.c_offset
@@ -234,9 +236,9 @@ def build_ops(plan):
     plan.rows_total = row
     ops, op_launches = [], []
     for L in plan.launches:
-        if (plan.f32 or plan.f16) and L.kind in ("dwconv", "shuffle", "se"):
-            raise NotImplementedError(f"precision='{plan.precision}' covers the Darknet families (YOLOv3-SPP / -tiny / YOLOv3 / Lite); "
-                                      f"no {plan.precision} kernel for '{L.kind}' layers")
+        if plan.f16 and L.kind in ("dwconv", "shuffle", "se"):
+            raise NotImplementedError(f"precision='fp16' covers the Darknet families (YOLOv3-SPP / -tiny / YOLOv3 / Lite); "
+                                      f"no fp16 kernel for '{L.kind}' layers (precision='fp32' and 'bf16' run them)")
         assert not (L.reads_nchw and ops)               # feed() patches op 0's x with the caller's batch
         for op in EMITTERS[L.kind](plan, L):
             ops.append(op); op_launches.append(L)
@@ -281,6 +283,8 @@ def conv_flops(op_array, n_ops: int, c_in: int) -> float:
             total += 2.0 * d.n * d.h * d.w * (d.cout * d.cin) * 10
         elif op.kind == OP_DWCONV:
             total += 2.0 * d.n * d.ho * d.wo * d.cin * 9
+        elif op.kind == OP_DWCONV_F32:                   # (always carries the real kernel size)
+            total += 2.0 * d.n * d.ho * d.wo * d.cin * d.ksize * d.ksize
         elif op.kind == OP_MBCONV:                       # expand at the input size, depthwise + projection at the output size
             hid = op.kpad_pre
             total += (2.0 * d.n * d.h * d.w * d.cin * hid if op.w_pre else 0.0) + 2.0 * d.n * d.ho * d.wo * hid * (9 + d.cout)
@@ -316,12 +320,12 @@ def algorithmic_bytes(op_array, n_ops: int, c_in: int, detect: bool = False) -> 
             total += m_in * d.cout * 2 * (3 if op.y_aux else 2)
         elif op.kind == OP_MBCONV:
             total += m_in * d.cin * 2 + m_out * d.cout * 2
-        elif op.kind in (OP_MAXPOOL, OP_DWCONV, OP_MAXPOOL_F32, OP_MAXPOOL_F16):
-            total += (m_in + m_out) * d.cin * (4 if op.kind == OP_MAXPOOL_F32 else 2)
-        elif op.kind == OP_SE:
-            total += 3.0 * m_in * d.cin * 2                                      # pooled once, read again for the rescale, written
+        elif op.kind in (OP_MAXPOOL, OP_DWCONV, OP_MAXPOOL_F32, OP_MAXPOOL_F16, OP_DWCONV_F32):
+            total += (m_in + m_out) * d.cin * (4 if op.kind in (OP_MAXPOOL_F32, OP_DWCONV_F32) else 2)
+        elif op.kind in (OP_SE, OP_SE_F32):
+            total += 3.0 * m_in * d.cin * (4 if op.kind == OP_SE_F32 else 2)     # pooled once, read again for the rescale, written
         elif op.kind == OP_SPP:
             total += m_in * d.cin * 2 * 4                                        # reads c, writes the three pooled copies
-        elif op.kind == OP_SHUFFLE:
-            total += 2.0 * m_in * d.cin * 2
+        elif op.kind in (OP_SHUFFLE, OP_SHUFFLE_F32):
+            total += 2.0 * m_in * d.cin * (4 if op.kind == OP_SHUFFLE_F32 else 2)
     return total

@@ -199,6 +199,39 @@ def maxpool_f32(x, y, *, n, h, w, c, in_view, out_view, ksize, stride, pad, dila
     return y
 
 
+def _need_f32(what, *tensors):
+    _need_cuda(*tensors)
+    for t in tensors:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise RuntimeError(f"{what}: every tensor must be contiguous float32")
+
+
+def dwconv_f32(x, wkc, bias, y, *, n, h, w, c, in_view, out_view, ho, wo, ksize, stride, pad, act):
+    """fp32 mode depthwise k x k (3 or 5) conv with an explicit leading pad (yolo_dwconv_f32_fwd); wkc: f32 [k*k][c]; torch's
+    3x3 / pad 1 is ksize=3, pad=1."""
+    _need_f32("dwconv_f32", x, wkc, bias, y)
+    check(load().yolo_dwconv_f32_fwd(_ptr(x), _ptr(wkc), _ptr(bias), _ptr(y), n, h, w, c, in_view[0], in_view[1], ho, wo, out_view[0],
+                                     out_view[1], ksize, stride, pad, act, stream_ptr()), "dwconv_f32")
+    return y
+
+
+def se_f32(x, y, w1, b1, w2, b2, workspace, *, n, h, w, c, in_view, out_view):
+    """fp32 mode squeeze-and-excitation (yolo_se_f32_fwd): tensors and workspace (se_workspace_bytes) as ``se``, all float32."""
+    _need_f32("se_f32", x, y, w1, b1, w2, b2, workspace)
+    check(load().yolo_se_f32_fwd(_ptr(x), _ptr(y), n, h, w, c, in_view[0], in_view[1], out_view[0], out_view[1], _ptr(w1), _ptr(b1),
+                                 _ptr(w2), _ptr(b2), w1.shape[0], _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                 stream_ptr()), "se_f32")
+    return y
+
+
+def shuffle2_f32(a, b, y, *, n, h, w, half, c_slot, a_view, b_view, y_view):
+    """fp32 mode channel_shuffle(cat(a, b), 2) in the two-slot layout (yolo_channel_shuffle2_f32_fwd); views = (c_total, c_offset)."""
+    _need_f32("shuffle2_f32", a, b, y)
+    check(load().yolo_channel_shuffle2_f32_fwd(_ptr(a), _ptr(b), _ptr(y), n, h, w, half, c_slot, a_view[0], a_view[1], b_view[0],
+                                               b_view[1], y_view[0], y_view[1], stream_ptr()), "shuffle2_f32")
+    return y
+
+
 def pack_input(x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """f32 NCHW -> bf16 NHWC (channels zero-padded to out.shape[-1])."""
     _need_cuda(x, out)
