@@ -1,6 +1,6 @@
 """Diagnostics of the plan build, all opt-in by env variable and none of them part of the product path:
 
-* ``YOLO_REDZONE=<bytes>``: guarded allocations (``GuardedAlloc``: Plan's allocator);
+* ``YOLO_REDZONE=<bytes>``: guarded allocations (``GuardedAlloc``: Plan's allocator), ``YOLO_REDZONE_BYTE`` the poison byte;
 * ``YOLO_SHRINK_OPS="i,j,..."``: launches that process one image (timing only, results wrong);
 * ``YOLO_DEPTH_FIRST="a-b:S,..."``: launches [a, b) as S depth-first passes over image sub-batches (bit-equal results).
 
@@ -19,9 +19,11 @@ DEPTH_FIRST_DEFAULT = ""
 
 class GuardedAlloc:
     """Plan's allocator.  YOLO_REDZONE=<bytes>: every activation buffer and every packed weight / bias of the plan sits in the
-    middle of a larger allocation whose margins are filled with REDZONE_BYTE (0x7f7f... = a large finite bf16 / f32 pattern that
-    max pools, MFMAs and decodes would carry into the results).  ``redzone_report()`` then tells whether a launch wrote outside
-    its buffer; results that change against a plain plan show reads outside (VERDICT r3 item 2;
+    middle of a larger allocation whose margins are filled with the poison byte: REDZONE_BYTE (0x7f7f... = a large finite bf16 /
+    f32 pattern that max pools, MFMAs and decodes would carry into the results) unless YOLO_REDZONE_BYTE names another, such as
+    0xFF (NaN in bf16 / f16 / f32: it survives the multiplication by a zero-padded weight that makes 0x7f7f vanish, where a max or
+    a compare may drop it); the plan keeps the byte its first guarded allocation was made with.  ``redzone_report()`` then tells
+    whether a launch wrote outside its buffer; results that change against a plain plan show reads outside (VERDICT r3 item 2;
     tests/test_gpu_parity.py::test_launch_lists_stay_inside_their_buffers).  Expects ``device``, ``_keep`` and ``_redzones``
     (lists) on the instance."""
     REDZONE_BYTE = 0x7F
@@ -29,10 +31,20 @@ class GuardedAlloc:
     def _redzone(self) -> int:
         return int(os.environ.get("YOLO_REDZONE", "0")) // 256 * 256
 
+    def redzone_byte(self) -> int:
+        """The poison byte of this plan's margins: YOLO_REDZONE_BYTE ("0xFF", "255", ...) when the first guarded allocation was made,
+        REDZONE_BYTE without it."""
+        if getattr(self, "_redzone_byte", None) is None:
+            byte = int(os.environ.get("YOLO_REDZONE_BYTE", "") or str(self.REDZONE_BYTE), 0)
+            if not 0 <= byte <= 255:
+                raise RuntimeError(f"YOLO_REDZONE_BYTE={byte}: not a byte")
+            self._redzone_byte = byte
+        return self._redzone_byte
+
     def _guarded(self, nbytes: int):
         """(raw uint8 allocation with poisoned margins, byte offset of the payload)."""
         rz = self._redzone()
-        raw = torch.full((nbytes + 2 * rz,), self.REDZONE_BYTE, dtype=torch.uint8, device=self.device)
+        raw = torch.full((nbytes + 2 * rz,), self.redzone_byte(), dtype=torch.uint8, device=self.device)
         self._redzones.append((raw, rz, nbytes))
         return raw, rz
 
@@ -62,12 +74,13 @@ class GuardedAlloc:
         return t
 
     def redzone_report(self):
-        """Number of margin bytes that no longer hold REDZONE_BYTE, per guarded allocation: [(index, payload bytes, below, above)]
+        """Number of margin bytes that no longer hold the poison byte, per guarded allocation: [(index, payload bytes, below, above)]
         for the damaged ones (empty list: every launch stayed inside its buffers)."""
         bad = []
+        byte = self.redzone_byte()
         for i, (raw, rz, nbytes) in enumerate(self._redzones):
-            lo = int((raw[:rz] != self.REDZONE_BYTE).sum())
-            hi = int((raw[rz + nbytes:] != self.REDZONE_BYTE).sum())
+            lo = int((raw[:rz] != byte).sum())
+            hi = int((raw[rz + nbytes:] != byte).sum())
             if lo or hi:
                 bad.append((i, nbytes, lo, hi))
         return bad

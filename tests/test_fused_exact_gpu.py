@@ -13,7 +13,11 @@ and the real activation scales - tests/test_gpu_parity.py keeps those.
 Views as in test_conv_exact_gpu.py::run_exact: x sits at an 8-channel offset in a wider buffer whose other channels hold NaN, y and the
 pre-add copy sit at an offset among -77 values that must survive.  The forms are selected through yolo_set_tuning (knobs 3 and 4) and
 restored in finally; the library cannot print which fused kernel a unit or block takes, so the forms rest on the knobs and on the
-rules tests/test_fused_exact_cpu.py repeats (see the header of tests/_exact_cases.py)."""
+rules tests/test_fused_exact_cpu.py repeats (see the header of tests/_exact_cases.py).
+
+Along the pixel direction every operand (x - the unit's residual too -, y, the pre-add copy, the float32 NCHW batch of the stem, every
+packed weight and bias) sits between the poisoned margins of tests/_guard.py, and every case runs once per poison (0xFF, 0x7F): a
+read outside an operand shows in the comparison, a write in Guard.assert_intact() after it."""
 import contextlib
 
 import pytest
@@ -21,6 +25,7 @@ import torch
 import torch.nn.functional as F
 
 import _exact_cases as E
+import _guard as G
 from helpers import exact_chain, exact_conv
 from test_conv_exact_gpu import DEV, _assert_equal, _nhwc
 from test_fused_exact_cpu import MB_IDS, POOL_IDS, STEM_IDS, UNIT_IDS
@@ -44,10 +49,11 @@ def _act_code(act):
     return {"leaky": ACT_LEAKY01, "relu6": ACT_RELU6}[act]
 
 
-def _view_in(x, margin=8):
-    """x NCHW -> NHWC bf16 on the device at channel offset `margin` of a buffer 2 * margin wider, NaN elsewhere."""
+def _view_in(x, g, margin=8):
+    """x NCHW -> NHWC bf16 on the device at channel offset `margin` of a buffer 2 * margin wider, NaN elsewhere, allocated by the
+    Guard `g`."""
     n, c, h, w = x.shape
-    buf = torch.full((n, h, w, c + 2 * margin), float("nan"), dtype=BF16, device=DEV)
+    buf = g.alloc("x", (n, h, w, c + 2 * margin), BF16, float("nan"))
     buf[..., margin:margin + c] = _nhwc(x, BF16)
     return buf
 
@@ -67,22 +73,24 @@ def test_fused_residual_unit_exact(u, use_aux):
     x, stages, res, unit, y_ref, aux_ref, _ = exact_chain("unit", u["shape"], u["seed"])
     (w1, b1, _, _, _), (w2, b2, _, _, _) = stages
     assert K.resunit_supported(c, h, w)
-    xin = _view_in(x)
     w1p, b1p, kpad1, cpad1 = K.pack_conv_weight(w1, b1, c)
     w2p, b2p, kpad2, cpad2 = K.pack_conv_weight(w2, b2, c // 2)
     assert torch.equal(w1p.float()[:c // 2, :c], w1.reshape(c // 2, c)) and torch.equal(b1p[:c // 2], b1)
     d = K.conv_desc(n=n, h=h, w=w, cin=c // 2, in_c_total=c + 16, in_c_offset=8, cout=c, out_c_total=c + 16, out_c_offset=8, ksize=3, stride=1,
                     act=_act_code(act), kpad=kpad2, cout_pad=cpad2, aux=(c + 16, 8) if use_aux else (0, 0))
-    dev = [t.to(DEV) for t in (w1p, b1p, w2p, b2p)]
     with knob(3, u["knob3"]):
-        for run in range(2):
-            y = torch.full((n, h, w, c + 16), -77.0, dtype=BF16, device=DEV)
-            aux = torch.full((n, h, w, c + 16), -77.0, dtype=BF16, device=DEV) if use_aux else None
+        for run, poison in enumerate(G.POISONS):
+            g = G.Guard(poison, DEV)
+            xin = _view_in(x, g)
+            dev = [g.like(name, t) for name, t in (("w1", w1p), ("b1", b1p), ("w2", w2p), ("b2", b2p))]
+            y = g.alloc("y", (n, h, w, c + 16), BF16, -77.0)
+            aux = g.alloc("pre-add copy", (n, h, w, c + 16), BF16, -77.0) if use_aux else None
             K.resunit(xin, dev[0], dev[1], dev[2], dev[3], y, d, kpad1, cpad1, y_preadd=aux)
             torch.cuda.synchronize()
             _check_view(y, 8, c, y_ref, f"y (launch {run})")
             if use_aux:
                 _check_view(aux, 8, c, aux_ref, f"pre-add copy (launch {run})")
+            g.assert_intact()
 
 
 @pytest.mark.parametrize("kernel,shape,tile,seed", E.STEM_CASES, ids=STEM_IDS)
@@ -98,13 +106,15 @@ def test_fused_stem_exact(kernel, shape, tile, seed):
     assert y_ref.shape == (n, 64, ho, wo)
     d = K.conv_desc(n=n, h=h, w=w, cin=32, in_c_total=32, in_c_offset=0, cout=64, out_c_total=80, out_c_offset=8, ksize=3, stride=2,
                     act=_act_code(act), kpad=kpad2, cout_pad=cpad2)
-    xd = x.contiguous().to(DEV)
-    dev = [t.to(DEV) for t in (w1p, b1p, w2p, b2p)]
-    for run in range(2):
-        y = torch.full((n, ho, wo, 80), -77.0, dtype=BF16, device=DEV)
+    for run, poison in enumerate(G.POISONS):
+        g = G.Guard(poison, DEV)
+        xd = g.like("x (float32 NCHW)", x.contiguous())
+        dev = [g.like(name, t) for name, t in (("w1", w1p), ("b1", b1p), ("w2", w2p), ("b2", b2p))]
+        y = g.alloc("y", (n, ho, wo, 80), BF16, -77.0)
         K.stem(xd, cin, dev[0], dev[1], kpad1, dev[2], dev[3], y, d)
         torch.cuda.synchronize()
         _check_view(y, 8, 64, y_ref, f"y (launch {run})")
+        g.assert_intact()
 
 
 @pytest.mark.parametrize("form,shape,tile", E.MBCONV_CASES, ids=MB_IDS)
@@ -121,14 +131,18 @@ def test_fused_inverted_residual_exact(form, shape, tile):
     (wd, bd, _, _, _), (wp, bp, _, _, _) = stages[-2:]
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
     assert y_ref.shape == (n, cout, ho, wo)
-    xin = _view_in(x)
-    y = torch.full((n, ho, wo, cout + 8), -77.0, dtype=BF16, device=DEV)
-    packed = tuple(None if t is None else t.to(DEV) for t in K.pack_mbconv(we, be, wd, bd, wp, bp, stride=stride))
-    with knob(4, E.MB_STRIP if form == "strip" else 0):
-        K.mbconv(xin, packed, y, n=n, h=h, w=w, cin=cin, hidden=hidden, cout=cout, in_view=(cin + 16, 8), out_view=(cout + 8, 4),
-                 stride=stride, has_res=res is not None)
-        torch.cuda.synchronize()
-    _check_view(y, 4, cout, y_ref, "y")
+    host = K.pack_mbconv(we, be, wd, bd, wp, bp, stride=stride)
+    for poison in G.POISONS:
+        g = G.Guard(poison, DEV)
+        xin = _view_in(x, g)
+        y = g.alloc("y", (n, ho, wo, cout + 8), BF16, -77.0)
+        packed = tuple(None if t is None else g.like(name, t) for name, t in zip(("w expand", "b expand", "w depthwise", "b depthwise", "w project", "b project"), host))
+        with knob(4, E.MB_STRIP if form == "strip" else 0):
+            K.mbconv(xin, packed, y, n=n, h=h, w=w, cin=cin, hidden=hidden, cout=cout, in_view=(cin + 16, 8), out_view=(cout + 8, 4),
+                     stride=stride, has_res=res is not None)
+            torch.cuda.synchronize()
+        _check_view(y, 4, cout, y_ref, "y")
+        g.assert_intact()
 
 
 @pytest.mark.parametrize("case", E.POOL_CASES, ids=POOL_IDS)
@@ -144,7 +158,10 @@ def test_small_cin_conv_with_maxpool_exact(case):
     wp, bp, kpad, cpad = K.pack_conv_weight(wt, bias, cin)
     d = K.conv_desc(n=n, h=h, w=w, cin=cin, in_c_total=cin + 16, in_c_offset=8, cout=cout, out_c_total=cout + 16, out_c_offset=8, ksize=3, stride=1,
                     act=_act_code("leaky"), kpad=kpad, cout_pad=cpad)
-    y = torch.full((n, ho, wo, cout + 16), -77.0, dtype=BF16, device=DEV)
-    K.conv3x3_pool(_view_in(x), wp.to(DEV), bp.to(DEV), y, d, pool=pool)
-    torch.cuda.synchronize()
-    _check_view(y, 8, cout, y_ref, "y")
+    for poison in G.POISONS:
+        g = G.Guard(poison, DEV)
+        y = g.alloc("y", (n, ho, wo, cout + 16), BF16, -77.0)
+        K.conv3x3_pool(_view_in(x, g), g.like("packed weights", wp), g.like("bias", bp), y, d, pool=pool)
+        torch.cuda.synchronize()
+        _check_view(y, 8, cout, y_ref, "y")
+        g.assert_intact()

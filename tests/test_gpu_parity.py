@@ -2324,16 +2324,71 @@ def test_pack_detections_and_events():
 
 # ------------------------------------------------------------------------------------------------
 # memory-safety audit of the launch lists
-def _guarded(shape, dtype, rz=65536, fill=0x7F):
-    """A tensor in the middle of a larger allocation whose margins hold ``fill``; returns (tensor, raw bytes, rz)."""
-    numel = int(np.prod(shape))
-    nbytes = numel * torch.empty((), dtype=dtype).element_size()
-    raw = torch.full((nbytes + 2 * rz,), fill, dtype=torch.uint8, device=DEV)
-    return raw[rz:rz + nbytes].view(dtype).view(shape), raw, rz
+_LIST_POISONS = (0x7F, 0xFF)      # tests/_guard.py: 3.4e38 as bf16 / f32 (a max or a compare carries it), NaN (it survives a zero weight)
 
 
-def _margins_intact(raw, rz, fill=0x7F):
-    return bool((raw[:rz] == fill).all()) and bool((raw[-rz:] == fill).all())
+def _audit_launch_list(model, x_plain, precision, monkeypatch, conf, tag):
+    """forward + decode + NMS of ``model``'s launch list for the batch ``x_plain`` [bs, 3, h, w] once on a plain plan and once per
+    poison on a guarded one: every activation buffer, packed weight and bias of the plan (engine.Plan, YOLO_REDZONE with
+    YOLO_REDZONE_BYTE) and the call's own buffers - the input batch, io, p of every head, the NMS outputs dets / idx / count and the
+    NMS workspace (tests/_guard.py: margins of 64 KiB or one image plane) - sit inside larger allocations whose margins hold the
+    poison byte.  Then
+      * writes: every margin still holds the poison - compared bytewise, so the int32 buffers and the byte workspace count too;
+      * reads: io, p and the detections are bit-equal to those of the plain plan - a kernel that picked up margin bytes (a max pool
+        window, a halo pixel, a weight row past the matrix) would carry 3.4e38 / inf / NaN into them.
+    ``conf``: the NMS threshold; None takes half the best score of the plain run (uncalibrated synthetic heads score low).  Returns
+    the plain plan."""
+    import _guard as G
+    from pytorch_yolo_amd import engine, kernels as K
+    from pytorch_yolo_amd.utils.utils import MAX_PER_CLASS, MIN_WH, nms_capacity
+    bs, _, h, w = x_plain.shape
+
+    def run(poison, conf):
+        if poison is None:
+            monkeypatch.delenv("YOLO_REDZONE", raising=False)
+        else:
+            monkeypatch.setenv("YOLO_REDZONE", "65536")
+            monkeypatch.setenv("YOLO_REDZONE_BYTE", hex(poison))
+        a = G.Plain(DEV) if poison is None else G.Guard(poison, DEV)
+        rec = engine.Recorder(bs, 3, h, w)
+        model._trace(rec, rec.input)
+        plan = engine.Plan(rec, torch.device(DEV), model.n_class, max(h, w), precision)
+        no, rows = model.n_class + 5, plan.rows_total
+        cap = nms_capacity(rows, model.n_class)
+        x = a.like("x", x_plain)
+        io = a.alloc("io", (bs, rows, no), torch.float32, plane=rows * no)
+        ps = tuple(a.alloc(f"p[{k}]", (bs, hd["na"], hd["sym"].h, hd["sym"].w, no), torch.float32) for k, hd in enumerate(plan.heads))
+        dets = a.alloc("dets", (bs, cap, 7), torch.float32, plane=cap * 7)
+        idx = a.alloc("idx", (bs, cap), torch.int32, plane=cap)
+        cnt = a.alloc("count", (bs,), torch.int32)
+        ws = a.alloc("nms workspace", (K.nms_workspace_bytes(bs, rows, model.n_class),), torch.uint8)
+        with torch.no_grad():
+            plan._launch(x, io, ps)
+            if conf is None:
+                score = io[..., 4] * io[..., 5:].max(-1).values
+                score = torch.where((io[..., 2] > MIN_WH) & (io[..., 3] > MIN_WH) & torch.isfinite(score), score, torch.zeros_like(score))
+                conf = float(score.max()) * 0.5
+            K.nms_merge(io, conf, C.NMS_FULL["nms_thres"], dets, idx, cnt, ws, min_wh=MIN_WH, max_per_class=MAX_PER_CLASS)
+        torch.cuda.synchronize()
+        return plan, a, io, ps, dets, idx, cnt, conf
+
+    plan_p, _, io_p, ps_p, dets_p, idx_p, cnt_p, conf = run(None, conf)
+    assert plan_p._redzones == [] and bool(torch.isfinite(io_p).all()), tag
+    assert int(cnt_p.sum()) > 0, f"{tag}: the NMS leg is vacuous"
+    for poison in _LIST_POISONS:
+        what = f"{tag}, poison {poison:#04x}"
+        plan_g, guard, io_g, ps_g, dets_g, idx_g, cnt_g, _ = run(poison, conf)
+        assert plan_g.redzone_byte() == poison and len(plan_g._redzones) >= plan_g.n_ops, f"{what}: the plan's buffers were not guarded"
+        assert all(bool((raw[:rz] == poison).all()) for raw, rz, _ in plan_g._redzones[:4]), f"{what}: the plan's margins do not hold the poison"
+        assert plan_g.redzone_report() == [], f"{what}: a launch wrote outside a plan buffer: {plan_g.redzone_report()}"
+        guard.assert_intact()                       # x, io, p..., dets, idx, count, nms workspace: bytewise
+        assert torch.equal(io_g, io_p), f"{what}: io differs between the guarded and the plain plan: a kernel reads outside its buffers"
+        assert all(torch.equal(a, b) for a, b in zip(ps_g, ps_p)), what
+        assert torch.equal(cnt_g, cnt_p), what
+        for b in range(bs):
+            assert torch.equal(dets_g[b, :cnt_p[b]], dets_p[b, :cnt_p[b]]) and torch.equal(idx_g[b, :cnt_p[b]], idx_p[b, :cnt_p[b]]), what
+        del plan_g, guard, io_g, ps_g, dets_g, idx_g, cnt_g
+    return plan_p
 
 
 @pytest.mark.parametrize("name", ["tiny_416x32", "mobile_416x64", "spp_640x32", "tiny_416x32_fp32"])
@@ -2341,15 +2396,16 @@ def test_launch_lists_stay_inside_their_buffers(name, monkeypatch):
     """Dynamic bounds audit of the BASELINE launch lists at the bench shapes (the tiny-416 x 32 list is the one whose HIP-graph
     replay ended in a GPU memory access fault in round 3).  Every activation buffer, packed weight and bias of the plan
     (engine.Plan, YOLO_REDZONE), the input batch, io, the NMS outputs and the NMS workspace sit inside larger allocations whose
-    64 KB margins are poisoned with 0x7f bytes (3.4e38 as bf16 / f32).  After forward + decode + NMS:
+    margins (64 KB and more) are poisoned - once with 0x7f bytes (3.4e38 as bf16 / f32), once with 0xff bytes (NaN).  After forward
+    + decode + NMS (_audit_launch_list):
       * writes: every margin still holds the poison;
       * reads: io and the detections are bit-equal to those of a plain plan - a kernel that picked up margin bytes (a max pool
         window, a halo pixel, a weight row past the matrix) would carry 3.4e38 / inf / NaN into them.
     The static side of the audit (what every launch may touch by the C ABI's contract against the planner's allocations) is
-    tests/test_host_cpu.py::test_every_launch_stays_inside_the_plans_allocations."""
-    from pytorch_yolo_amd import YOLOv3TinyMobile, engine, kernels as K
+    tests/test_host_cpu.py::test_every_launch_stays_inside_the_plans_allocations; the modes and families these four lists do not
+    reach are test_small_launch_lists_stay_inside_their_buffers."""
+    from pytorch_yolo_amd import YOLOv3TinyMobile
     from pytorch_yolo_amd.utils.synthetic import synth_state_dict
-    from pytorch_yolo_amd.utils.utils import MAX_PER_CLASS, MIN_WH, nms_capacity
     fp32 = name.endswith("_fp32")
     if name.startswith("tiny"):
         model, sd, _ = build_case(C.FULL_CASES["tiny_416"])
@@ -2363,43 +2419,35 @@ def test_launch_lists_stay_inside_their_buffers(name, monkeypatch):
         bs, hw = 32, 640
     model = model.to(DEV)
     x_plain = _seeded_batch(bs, hw).to(DEV)
+    # (the MobileNetV2 model's uncalibrated synthetic heads score low: a threshold its survivors clear, so that the NMS kernels run)
+    _audit_launch_list(model, x_plain, "fp32" if fp32 else "bf16", monkeypatch, 0.002 if name.startswith("mobile") else C.NMS_FULL["conf_thres"], name)
 
-    def run(guard):
-        if guard:
-            monkeypatch.setenv("YOLO_REDZONE", "65536")
-        else:
-            monkeypatch.delenv("YOLO_REDZONE", raising=False)
-        rec = engine.Recorder(bs, 3, hw, hw)
-        model._trace(rec, rec.input)
-        plan = engine.Plan(rec, torch.device(DEV), model.n_class, hw, "fp32" if fp32 else "bf16")
-        no, cap = model.n_class + 5, nms_capacity(plan.rows_total, model.n_class)
-        shapes = [((bs, 3, hw, hw), torch.float32), ((bs, plan.rows_total, no), torch.float32), ((bs, cap, 7), torch.float32),
-                  ((bs, cap), torch.int32), ((bs,), torch.int32), ((K.nms_workspace_bytes(bs, plan.rows_total, model.n_class),), torch.uint8)]
-        shapes += [((bs, hd["na"], hd["sym"].h, hd["sym"].w, no), torch.float32) for hd in plan.heads]
-        ts = [_guarded(sh, dt) if guard else (torch.empty(sh, dtype=dt, device=DEV), None, 0) for sh, dt in shapes]
-        x, io, dets, idx, cnt, ws = (t[0] for t in ts[:6])
-        ps = tuple(t[0] for t in ts[6:])
-        x.copy_(x_plain)
-        with torch.no_grad():
-            plan._launch(x, io, ps)
-            # (the MobileNetV2 model's uncalibrated synthetic heads score low: a threshold its survivors clear, so that the NMS kernels run)
-            K.nms_merge(io, 0.002 if name.startswith("mobile") else C.NMS_FULL["conf_thres"], C.NMS_FULL["nms_thres"], dets, idx, cnt, ws,
-                        min_wh=MIN_WH, max_per_class=MAX_PER_CLASS)
-        torch.cuda.synchronize()
-        return plan, ts, io, ps, dets, cnt
 
-    plan_g, ts_g, io_g, ps_g, dets_g, cnt_g = run(True)
-    assert len(plan_g._redzones) >= plan_g.n_ops, "the plan's buffers were not guarded"
-    assert plan_g.redzone_report() == [], f"a launch wrote outside a plan buffer: {plan_g.redzone_report()}"
-    for i, (_, raw, rz) in enumerate(ts_g):
-        assert _margins_intact(raw, rz), f"a launch wrote outside call buffer {i} (x, io, dets, idx, count, nms workspace, p...)"
-    plan_p, _, io_p, ps_p, dets_p, cnt_p = run(False)
-    assert torch.equal(io_g, io_p), "io differs between the guarded and the plain plan: a kernel reads outside its buffers"
-    assert all(torch.equal(a, b) for a, b in zip(ps_g, ps_p))
-    assert torch.equal(cnt_g, cnt_p) and int(cnt_p.sum()) > 0
-    for b in range(bs):
-        assert torch.equal(dets_g[b, :cnt_p[b]], dets_p[b, :cnt_p[b]])
-    assert bool(torch.isfinite(io_p).all())
+def _plan_case_names():
+    from _guard_plan_cases import PLAN_CASES
+    return list(PLAN_CASES)
+
+
+@pytest.mark.parametrize("name", _plan_case_names())
+def test_small_launch_lists_stay_inside_their_buffers(name, monkeypatch):
+    """The audit of test_launch_lists_stay_inside_their_buffers for the modes and families that have no bench shape
+    (tests/_guard_plan_cases.py): the fp16 mode of SPP, tiny and YOLOv3 with the 20x20-tile kernels (both of them, at the smallest
+    three-image input that reaches them) and without (YOLO_FP16_T20=0), the fp32 mode of the four encoder families (the float32
+    depthwise, squeeze-excite and shuffle kernels), the bf16 lists of EfficientNet, ShuffleNetV2, SqueezeNet, YOLOv3 and Lite - three
+    images of unequal sides, both poisons.  The op kinds of the list are asserted first (the CPU suite pins them too)."""
+    from _guard_plan_cases import PLAN_CASES, build_model, plan_kinds
+    from pytorch_yolo_amd.utils.synthetic import synth_images, synth_state_dict
+    family, kw, precision, env, (bs, h, w), kinds, t20_strides = PLAN_CASES[name]
+    monkeypatch.delenv("YOLO_FP16_T20", raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    model = build_model(family, kw)
+    model.load_state_dict(synth_state_dict(model.state_dict(), 1234, n_class=kw["n_class"]))
+    model = model.to(DEV)
+    x = synth_images(bs, h, w, 7).to(DEV)
+    plan = _audit_launch_list(model, x, precision, monkeypatch, None, name)
+    got, strides = plan_kinds(plan)
+    assert got == set(kinds) and strides == set(t20_strides), (sorted(got), sorted(strides))
 
 
 # ------------------------------------------------------------------------------------------------
