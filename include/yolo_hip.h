@@ -259,6 +259,27 @@ YOLO_API int yolo_nms_merge(float* pred, int bs, int rows, int nc, float conf_th
                    int max_per_class, int mutate_conf, float* out_dets, int32_t* out_idx,
                    int32_t* out_count, int cap, void* workspace, size_t workspace_bytes, yolo_stream_t s);
 
+/* ---- the other suppression styles of the same function (utils/utils.py:240: nms_style = 'OR' (default) | 'AND' | 'MERGE' | 'SOFT').
+ *  The reference hard-codes 'MERGE'; yolo_nms_styled takes the style as an argument and yolo_nms_merge is
+ *  yolo_nms_styled(..., YOLO_NMS_MERGE, s).  Shared by all styles, unchanged: conf product and filters (:212-218), xywh2xyxy (:231),
+ *  the sort by conf (:237), the per-class loop over ascending class ids (:241), a class of ONE row is kept as it is (:244-246, the
+ *  length before the cap), only the first max_per_class rows of a class take part (:247-250), the final order (:291).  Per class:
+ *    YOLO_NMS_MERGE (:266-275)  the head's box becomes the conf-weighted mean of the rows with iou > nms_thres, which leave with it.
+ *    YOLO_NMS_OR    (:253-259)  greedy hard NMS: emit the head, keep the rows with iou < nms_thres (iou == nms_thres is removed).
+ *    YOLO_NMS_AND   (:260-265)  as OR, but the head is emitted only if its largest iou with the remaining rows is > 0.5 (a
+ *                               constant of the reference, not nms_thres); the last remaining row of a class is never emitted, so
+ *                               an image may lose every row (out_count 0).
+ *    YOLO_NMS_SOFT  (:277-287)  nothing is removed: row j is emitted with conf_j * prod_{i<j} exp(-iou(i,j)^2 / 0.5) (factors in
+ *                               ascending i, one fp32 multiply each; rows are not re-sorted inside the loop); the final order uses
+ *                               the decayed conf; class_conf (column 5) is untouched.  expf is the one step that is not bit-defined.
+ *  In OR, AND and SOFT the box columns of an output row are the input row's corners, unchanged, and out_idx is that row.
+ *  nms_thres >= 1 is refused for MERGE only (its loop would not terminate).  An unknown style returns YOLO_E_ARG.
+ *  The one-call pipeline step (YoloPipeStep / yolo_pipeline_step) has no style field and stays MERGE-only. */
+enum { YOLO_NMS_MERGE = 0, YOLO_NMS_OR = 1, YOLO_NMS_AND = 2, YOLO_NMS_SOFT = 3 };
+YOLO_API int yolo_nms_styled(float* pred, int bs, int rows, int nc, float conf_thres, float nms_thres, float min_wh,
+                   int max_per_class, int mutate_conf, float* out_dets, int32_t* out_idx,
+                   int32_t* out_count, int cap, void* workspace, size_t workspace_bytes, int style, yolo_stream_t s);
+
 /* ---- the compact form of the same post-process (round 4): detect() = non_max_suppression(forward(x)[0]) without ever writing io.
  *  The head convs filter their own decoded rows in their epilogue (yolo_head_decode_filter_fwd: the row filter of utils.py:212-218,
  *  operation for operation what yolo_nms_merge's first kernel does on a materialised io) and leave, in the workspace, ONE sort key
@@ -275,6 +296,10 @@ YOLO_API int yolo_head_decode_filter_fwd(const void* x, const void* w_packed, co
 YOLO_API int yolo_nms_merge_compact(void* workspace, size_t workspace_bytes, int bs, int rows, int nc, float nms_thres,
                                     int max_per_class, float* out_dets, int32_t* out_idx, int32_t* out_count, int cap,
                                     yolo_stream_t s);
+/* ... with the style of yolo_nms_styled (yolo_nms_merge_compact = YOLO_NMS_MERGE); the head epilogues' row filter is style-independent */
+YOLO_API int yolo_nms_styled_compact(void* workspace, size_t workspace_bytes, int bs, int rows, int nc, float nms_thres,
+                                     int max_per_class, float* out_dets, int32_t* out_idx, int32_t* out_count, int cap,
+                                     int style, yolo_stream_t s);
 
 /* ---- scale_coords (utils/utils.py:296-303): map kept boxes from the network-input frame back to each original
  *  image: dets [bs,cap,row_floats] (columns 0..3 = x1,y1,x2,y2) in place; params_dev: device f32 [bs][4] =

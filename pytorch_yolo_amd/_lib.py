@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("YOLO_HIP_LIB") or os.path.join(_HERE, "csrc", "libyol
 ABI_VERSION = 2          # include/yolo_hip.h, yolo_abi_version
 ACT_NONE, ACT_LEAKY01, ACT_RELU6, ACT_RELU, ACT_SWISH = 0, 1, 2, 3, 4
 DT_BF16, DT_F32, DT_F16 = 0, 1, 2
+NMS_MERGE, NMS_OR, NMS_AND, NMS_SOFT = 0, 1, 2, 3                    # YOLO_NMS_*: the reference's nms_style names (utils/utils.py:240)
+NMS_STYLES = {"MERGE": NMS_MERGE, "OR": NMS_OR, "AND": NMS_AND, "SOFT": NMS_SOFT}
 OP_CONV, OP_MAXPOOL, OP_SPP, OP_DWCONV, OP_CONV1_NCHW, OP_RESUNIT, OP_STEM, OP_HEAD_DECODE, OP_CONV1_POOL = 1, 2, 3, 4, 5, 6, 7, 8, 9
 OP_MBCONV, OP_CONV_POOL, OP_SHUFFLE, OP_CONV_F32, OP_MAXPOOL_F32, OP_SE = 10, 11, 12, 13, 14, 15
 OP_CONV_F16, OP_MAXPOOL_F16, OP_HEAD_DECODE_F16 = 16, 17, 18          # the fp16-operand mode
@@ -104,11 +106,15 @@ SIGNATURES = {
     "yolo_nms_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "yolo_nms_merge": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_float] * 3 + [C.c_int] * 2 +
                        [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_nms_styled": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_float] * 3 + [C.c_int] * 2 +
+                        [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "yolo_nms_compact_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
     "yolo_head_decode_filter_fwd": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YoloConvDesc), C.c_void_p, C.c_int, C.c_int, C.c_float,
                                               C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "yolo_nms_merge_compact": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_int] * 3 + [C.c_float, C.c_int] + [C.c_void_p] * 3 +
                                [C.c_int, C.c_void_p]),
+    "yolo_nms_styled_compact": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_int] * 3 + [C.c_float, C.c_int] + [C.c_void_p] * 3 +
+                                [C.c_int, C.c_int, C.c_void_p]),
     "yolo_scale_coords": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "yolo_letterbox_u8_fwd": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_double] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p] +
                               [C.c_int] * 4 + [C.c_float, C.c_void_p]),
@@ -168,6 +174,13 @@ def load():
             raise RuntimeError(f"libyolo_hip.so: struct {st.__name__} is {lib.yolo_abi_sizeof(which)} bytes in the library, {C.sizeof(st)} in the binding")
     _lib = lib
     return lib
+
+
+def nms_style_id(nms_style) -> int:
+    """The YOLO_NMS_* value of a reference style name (case-sensitive, like the reference's string compare)."""
+    if not isinstance(nms_style, str) or nms_style not in NMS_STYLES:
+        raise ValueError(f"nms_style must be one of 'MERGE', 'OR', 'AND', 'SOFT' (reference utils/utils.py:240), not {nms_style!r}")
+    return NMS_STYLES[nms_style]
 
 
 def check(rc: int, what: str = "") -> None:

@@ -15,6 +15,11 @@
 //   nms_merge  : one 1024-thread workgroup per image: bitonic sort of the keys (LDS up to 8192 keys,
 //                global workspace beyond), class segments, one wave per class runs the sequential
 //                MERGE over its first max_per_class rows with ballot masks, final sort by conf.
+//                The per-class loop is the kernel's template parameter: one instantiation per suppression style of the
+//                reference (YOLO_NMS_MERGE :266-275, _OR :253-259, _AND :260-265, _SOFT :277-287); everything around it - filter,
+//                key sort, class segments, work queue, final order - is the same code for all four.  The decisions of OR and
+//                AND (iou < nms_thres, max iou > 0.5) are single fp32 comparisons of the same IoU sequence as MERGE's; SOFT's
+//                decay conf *= expf(-(iou * iou) / 0.5f) is exact up to expf (<= 1 ulp).
 #include "nms_common.h"
 
 namespace {
@@ -227,8 +232,13 @@ struct MergeArgs {
   float nms_thres;
 };
 
+// The sort buffer is ONE array shared by the four instantiations below, not a static of each: block_sort_lds is compiled out of
+// line, and only while every caller hands it the same array does the compiler know the address (and its 16-byte alignment:
+// ds_read_b128 / ds_write_b128 instead of pairs of 64-bit accesses) inside it.
+__shared__ __attribute__((aligned(16))) u64 s_keys[kLdsKeys];
+
+template <int STYLE>
 __global__ __launch_bounds__(kMergeThreads) void nms_merge_kernel(const MergeArgs a) {
-  __shared__ __attribute__((aligned(16))) u64 s_keys[kLdsKeys];
   __shared__ int s_seg_start[kMaxClasses];
   __shared__ int s_seg_len[kMaxClasses];
   __shared__ int s_nout, s_nlist, s_next;
@@ -335,79 +345,165 @@ __global__ __launch_bounds__(kMergeThreads) void nms_merge_kernel(const MergeArg
 
     u64 alive0 = (m >= 64) ? ~0ull : ((1ull << m) - 1ull);
     u64 alive1 = (m > 64) ? ((m - 64 >= 64) ? ~0ull : ((1ull << (m - 64)) - 1ull)) : 0ull;
-    while (alive0 | alive1) {
-      const int p = alive0 ? __builtin_ctzll(alive0) : 64 + __builtin_ctzll(alive1);
-      const int pl = p & 63;
-      const bool phi = p >= 64;
-      const bool last = (__builtin_popcountll(alive0) + __builtin_popcountll(alive1)) == 1;
-      const float px1 = readlane_f(phi ? bx[1][0] : bx[0][0], pl), py1 = readlane_f(phi ? bx[1][1] : bx[0][1], pl);
-      const float px2 = readlane_f(phi ? bx[1][2] : bx[0][2], pl), py2 = readlane_f(phi ? bx[1][3] : bx[0][3], pl);
-      const float pconf = readlane_f(phi ? ws[1] : ws[0], pl);
-      float mx1 = px1, my1 = py1, mx2 = px2, my2 = py2;
-      u64 h0 = 0, h1 = 0;
-      if (last) {                                                        // :268-270 kept as is
-        if (!phi) h0 = 1ull << pl; else h1 = 1ull << pl;
-      } else {
-        const float area1 = (px2 - px1) * (py2 - py1) + 1e-16f;          // :91,:93
-        bool hit[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const bool live = ((h ? alive1 : alive0) >> lane) & 1ull;
-          hit[h] = false;
-          if (live) {                                                    // bbox_iou, utils.py:85-96
-            const float iw = fminf(px2, bx[h][2]) - fmaxf(px1, bx[h][0]);
-            const float ih = fminf(py2, bx[h][3]) - fmaxf(py1, bx[h][1]);
-            const float inter = fmaxf(iw, 0.f) * fmaxf(ih, 0.f);
-            const float uni = (area1 + area[h]) - inter;
-            hit[h] = __fdiv_rn(inter, uni) > a.nms_thres;                // :271
-          }
-        }
-        h0 = __ballot(hit[0]);
-        h1 = __ballot(hit[1]);
-        // weighted mixture box (:272-274), sequential fp32 in candidate order (products rounded once, as the
-        // reference's `weights * boxes` does before the sum)
-        float wsum = 0.f, ax1 = 0.f, ay1 = 0.f, ax2 = 0.f, ay2 = 0.f;
-        u64 w0 = h0, w1 = h1;
-        while (w0) {
-          const int g = __builtin_ctzll(w0);
-          w0 &= w0 - 1;
-          wsum = wsum + readlane_f(ws[0], g);
-          ax1 = ax1 + readlane_f(wp[0][0], g);
-          ay1 = ay1 + readlane_f(wp[0][1], g);
-          ax2 = ax2 + readlane_f(wp[0][2], g);
-          ay2 = ay2 + readlane_f(wp[0][3], g);
-        }
-        while (w1) {
-          const int g = __builtin_ctzll(w1);
-          w1 &= w1 - 1;
-          wsum = wsum + readlane_f(ws[1], g);
-          ax1 = ax1 + readlane_f(wp[1][0], g);
-          ay1 = ay1 + readlane_f(wp[1][1], g);
-          ax2 = ax2 + readlane_f(wp[1][2], g);
-          ay2 = ay2 + readlane_f(wp[1][3], g);
-        }
-        mx1 = __fdiv_rn(ax1, wsum);
-        my1 = __fdiv_rn(ay1, wsum);
-        mx2 = __fdiv_rn(ax2, wsum);
-        my2 = __fdiv_rn(ay2, wsum);
-        if ((h0 | h1) == 0) {  // pivot does not overlap itself (the reference would spin forever): drop it
-          if (!phi) h0 = 1ull << pl; else h1 = 1ull << pl;
-        }
-      }
-      // the lane that owns the pivot emits the row
+    // the pivot's IoU against my candidate h (bbox_iou, utils.py:85-96): the instruction sequence of the MERGE loop below
+    auto iou_with = [&](float px1, float py1, float px2, float py2, float area1, int h) {
+      const float iw = fminf(px2, bx[h][2]) - fmaxf(px1, bx[h][0]);
+      const float ih = fminf(py2, bx[h][3]) - fmaxf(py1, bx[h][1]);
+      const float inter = fmaxf(iw, 0.f) * fmaxf(ih, 0.f);
+      const float uni = (area1 + area[h]) - inter;
+      return __fdiv_rn(inter, uni);
+    };
+    // the lane that owns candidate (pl, phi) emits it with its own corners (OR / AND / SOFT leave the box alone)
+    auto emit_own = [&](int pl, bool phi, float conf) {
       if (lane == pl) {
         const int slot = atomicAdd(&s_nout, 1);
         if (slot < a.stage_cap) {
           float* o = stage + (long)slot * 8;
-          o[0] = mx1; o[1] = my1; o[2] = mx2; o[3] = my2;
-          o[4] = pconf;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] = phi ? bx[1][e] : bx[0][e];
+          o[4] = conf;
           o[5] = phi ? my_cconf[1] : my_cconf[0];
           o[6] = (float)c;
           o[7] = __int_as_float(phi ? my_row[1] : my_row[0]);
         }
       }
-      alive0 &= ~h0;
-      alive1 &= ~h1;
+    };
+    if constexpr (STYLE == YOLO_NMS_MERGE) {
+      while (alive0 | alive1) {
+        const int p = alive0 ? __builtin_ctzll(alive0) : 64 + __builtin_ctzll(alive1);
+        const int pl = p & 63;
+        const bool phi = p >= 64;
+        const bool last = (__builtin_popcountll(alive0) + __builtin_popcountll(alive1)) == 1;
+        const float px1 = readlane_f(phi ? bx[1][0] : bx[0][0], pl), py1 = readlane_f(phi ? bx[1][1] : bx[0][1], pl);
+        const float px2 = readlane_f(phi ? bx[1][2] : bx[0][2], pl), py2 = readlane_f(phi ? bx[1][3] : bx[0][3], pl);
+        const float pconf = readlane_f(phi ? ws[1] : ws[0], pl);
+        float mx1 = px1, my1 = py1, mx2 = px2, my2 = py2;
+        u64 h0 = 0, h1 = 0;
+        if (last) {                                                        // :268-270 kept as is
+          if (!phi) h0 = 1ull << pl; else h1 = 1ull << pl;
+        } else {
+          const float area1 = (px2 - px1) * (py2 - py1) + 1e-16f;          // :91,:93
+          bool hit[2];
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const bool live = ((h ? alive1 : alive0) >> lane) & 1ull;
+            hit[h] = false;
+            if (live) {                                                    // bbox_iou, utils.py:85-96
+              const float iw = fminf(px2, bx[h][2]) - fmaxf(px1, bx[h][0]);
+              const float ih = fminf(py2, bx[h][3]) - fmaxf(py1, bx[h][1]);
+              const float inter = fmaxf(iw, 0.f) * fmaxf(ih, 0.f);
+              const float uni = (area1 + area[h]) - inter;
+              hit[h] = __fdiv_rn(inter, uni) > a.nms_thres;                // :271
+            }
+          }
+          h0 = __ballot(hit[0]);
+          h1 = __ballot(hit[1]);
+          // weighted mixture box (:272-274), sequential fp32 in candidate order (products rounded once, as the
+          // reference's `weights * boxes` does before the sum)
+          float wsum = 0.f, ax1 = 0.f, ay1 = 0.f, ax2 = 0.f, ay2 = 0.f;
+          u64 w0 = h0, w1 = h1;
+          while (w0) {
+            const int g = __builtin_ctzll(w0);
+            w0 &= w0 - 1;
+            wsum = wsum + readlane_f(ws[0], g);
+            ax1 = ax1 + readlane_f(wp[0][0], g);
+            ay1 = ay1 + readlane_f(wp[0][1], g);
+            ax2 = ax2 + readlane_f(wp[0][2], g);
+            ay2 = ay2 + readlane_f(wp[0][3], g);
+          }
+          while (w1) {
+            const int g = __builtin_ctzll(w1);
+            w1 &= w1 - 1;
+            wsum = wsum + readlane_f(ws[1], g);
+            ax1 = ax1 + readlane_f(wp[1][0], g);
+            ay1 = ay1 + readlane_f(wp[1][1], g);
+            ax2 = ax2 + readlane_f(wp[1][2], g);
+            ay2 = ay2 + readlane_f(wp[1][3], g);
+          }
+          mx1 = __fdiv_rn(ax1, wsum);
+          my1 = __fdiv_rn(ay1, wsum);
+          mx2 = __fdiv_rn(ax2, wsum);
+          my2 = __fdiv_rn(ay2, wsum);
+          if ((h0 | h1) == 0) {  // pivot does not overlap itself (the reference would spin forever): drop it
+            if (!phi) h0 = 1ull << pl; else h1 = 1ull << pl;
+          }
+        }
+        // the lane that owns the pivot emits the row
+        if (lane == pl) {
+          const int slot = atomicAdd(&s_nout, 1);
+          if (slot < a.stage_cap) {
+            float* o = stage + (long)slot * 8;
+            o[0] = mx1; o[1] = my1; o[2] = mx2; o[3] = my2;
+            o[4] = pconf;
+            o[5] = phi ? my_cconf[1] : my_cconf[0];
+            o[6] = (float)c;
+            o[7] = __int_as_float(phi ? my_row[1] : my_row[0]);
+          }
+        }
+        alive0 &= ~h0;
+        alive1 &= ~h1;
+      }
+    } else if constexpr (STYLE == YOLO_NMS_OR || STYLE == YOLO_NMS_AND) {
+      // OR (:253-259): emit the head, keep the rows with iou < nms_thres (strict: iou == nms_thres is removed).
+      // AND (:260-265): the same removal, but the head is emitted only if max(iou) > 0.5 (the reference's constant, not
+      // nms_thres; a NaN iou makes torch's max NaN and the comparison false), and the last remaining row of a class with
+      // n > 1 is never emitted; n == 1 (the length BEFORE the cap) is kept as is (:244-246).
+      while (alive0 | alive1) {
+        const int p = alive0 ? __builtin_ctzll(alive0) : 64 + __builtin_ctzll(alive1);
+        const int pl = p & 63;
+        const bool phi = p >= 64;
+        const bool last = (__builtin_popcountll(alive0) + __builtin_popcountll(alive1)) == 1;
+        u64 h0 = phi ? 0ull : 1ull << pl, h1 = phi ? 1ull << pl : 0ull;     // the head leaves in every case
+        bool emit = STYLE == YOLO_NMS_OR || seg_n == 1;
+        if (!last) {
+          const float px1 = readlane_f(phi ? bx[1][0] : bx[0][0], pl), py1 = readlane_f(phi ? bx[1][1] : bx[0][1], pl);
+          const float px2 = readlane_f(phi ? bx[1][2] : bx[0][2], pl), py2 = readlane_f(phi ? bx[1][3] : bx[0][3], pl);
+          const float area1 = (px2 - px1) * (py2 - py1) + 1e-16f;          // :91,:93
+          bool hit[2], big[2], bad[2];
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const bool live = (((h ? alive1 : alive0) >> lane) & 1ull) && !(lane == pl && phi == (h == 1));
+            hit[h] = big[h] = bad[h] = false;
+            if (live) {
+              const float iou = iou_with(px1, py1, px2, py2, area1, h);
+              hit[h] = !(iou < a.nms_thres);                               // :259 / :265
+              big[h] = iou > 0.5f;                                         // :263
+              bad[h] = iou != iou;
+            }
+          }
+          h0 |= __ballot(hit[0]);
+          h1 |= __ballot(hit[1]);
+          if constexpr (STYLE == YOLO_NMS_AND)
+            emit = (__ballot(big[0]) | __ballot(big[1])) != 0 && (__ballot(bad[0]) | __ballot(bad[1])) == 0;
+          else
+            emit = true;
+        }
+        if (emit) emit_own(pl, phi, phi ? ws[1] : ws[0]);
+        alive0 &= ~h0;
+        alive1 &= ~h1;
+      }
+    } else {
+      // SOFT (:277-287): nothing is removed and nothing re-sorted; candidate i is emitted with its current conf, then every
+      // later candidate's conf is multiplied by exp(-iou^2 / 0.5): factors applied in ascending i, one fp32 multiply each
+      static_assert(STYLE == YOLO_NMS_SOFT, "unknown NMS style");
+      float cf[2] = {ws[0], ws[1]};
+      for (int i = 0; i < m; ++i) {
+        const int pl = i & 63;
+        const bool phi = i >= 64;
+        emit_own(pl, phi, phi ? cf[1] : cf[0]);
+        if (i == m - 1) break;                                             // :280-282
+        const float px1 = readlane_f(phi ? bx[1][0] : bx[0][0], pl), py1 = readlane_f(phi ? bx[1][1] : bx[0][1], pl);
+        const float px2 = readlane_f(phi ? bx[1][2] : bx[0][2], pl), py2 = readlane_f(phi ? bx[1][3] : bx[0][3], pl);
+        const float area1 = (px2 - px1) * (py2 - py1) + 1e-16f;            // :91,:93
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int q = lane + 64 * h;
+          if (q > i && q < m) {
+            const float iou = iou_with(px1, py1, px2, py2, area1, h);
+            cf[h] = cf[h] * expf(-(iou * iou) / 0.5f);                     // :287
+          }
+        }
+      }
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -490,19 +586,21 @@ extern "C" size_t yolo_nms_compact_workspace_bytes(int bs, int rows, int nc) {
   return carve(nullptr, bs, rows, nc, true).bytes;
 }
 
-static int nms_check(int bs, int rows, int nc, float nms_thres, int max_per_class, int cap) {
+static int nms_check(int bs, int rows, int nc, float nms_thres, int max_per_class, int cap, int style) {
+  YOLO_REQUIRE(style == YOLO_NMS_MERGE || style == YOLO_NMS_OR || style == YOLO_NMS_AND || style == YOLO_NMS_SOFT,
+               "nms: unknown style %d (YOLO_NMS_MERGE 0, _OR 1, _AND 2, _SOFT 3)", style);
   YOLO_REQUIRE(bs > 0 && rows > 0 && nc > 0 && cap > 0, "nms: bad sizes");
   YOLO_REQUIRE(nc <= kMaxClasses, "nms: n_class %d > %d unsupported", nc, kMaxClasses);
   YOLO_REQUIRE(rows < (1 << 20), "nms: rows %d >= 2^20 unsupported", rows);
   YOLO_REQUIRE(max_per_class >= 1 && max_per_class <= kMaxPerClassCap, "nms: max_per_class %d not in [1,%d]", max_per_class,
                kMaxPerClassCap);
-  YOLO_REQUIRE(nms_thres < 1.f, "nms: nms_thres must be < 1 (the reference never terminates otherwise)");
+  YOLO_REQUIRE(style != YOLO_NMS_MERGE || nms_thres < 1.f, "nms: nms_thres must be < 1 (the reference never terminates otherwise)");
   return 0;
 }
 
 static int launch_merge(const float* rows_base, int row_floats, int cc_index, const Workspace& w, int bs, int rows, int nc,
                         float nms_thres, int max_per_class, float* out_dets, int32_t* out_idx, int32_t* out_count, int cap,
-                        hipStream_t st) {
+                        int style, hipStream_t st) {
   MergeArgs a;
   a.pred = rows_base;
   a.keys = w.keys;
@@ -521,15 +619,21 @@ static int launch_merge(const float* rows_base, int row_floats, int cc_index, co
   a.cc_index = cc_index;
   a.row_keys = w.row_keys;
   a.nms_thres = nms_thres;
-  hipLaunchKernelGGL(nms_merge_kernel, dim3((unsigned)bs), dim3(kMergeThreads), 0, st, a);
+  const dim3 grid((unsigned)bs), block(kMergeThreads);
+  switch (style) {                                    // (nms_check has refused every other value)
+    case YOLO_NMS_OR: hipLaunchKernelGGL(nms_merge_kernel<YOLO_NMS_OR>, grid, block, 0, st, a); break;
+    case YOLO_NMS_AND: hipLaunchKernelGGL(nms_merge_kernel<YOLO_NMS_AND>, grid, block, 0, st, a); break;
+    case YOLO_NMS_SOFT: hipLaunchKernelGGL(nms_merge_kernel<YOLO_NMS_SOFT>, grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL(nms_merge_kernel<YOLO_NMS_MERGE>, grid, block, 0, st, a); break;
+  }
   return yolo_check_launch("yolo_nms_merge(merge)");
 }
 
-extern "C" int yolo_nms_merge(float* pred, int bs, int rows, int nc, float conf_thres, float nms_thres, float min_wh,
-                              int max_per_class, int mutate_conf, float* out_dets, int32_t* out_idx, int32_t* out_count,
-                              int cap, void* workspace, size_t workspace_bytes, yolo_stream_t s) {
+extern "C" int yolo_nms_styled(float* pred, int bs, int rows, int nc, float conf_thres, float nms_thres, float min_wh,
+                               int max_per_class, int mutate_conf, float* out_dets, int32_t* out_idx, int32_t* out_count,
+                               int cap, void* workspace, size_t workspace_bytes, int style, yolo_stream_t s) {
   YOLO_REQUIRE(pred && out_dets && out_idx && out_count && workspace, "nms: null pointer");
-  if (int rc = nms_check(bs, rows, nc, nms_thres, max_per_class, cap)) return rc;
+  if (int rc = nms_check(bs, rows, nc, nms_thres, max_per_class, cap, style)) return rc;
   const int no = nc + 5;
   const size_t tile_bytes = (size_t)kFilterRows * no * 4;
   YOLO_REQUIRE(tile_bytes <= 64 * 1024, "nms: row of %d floats too wide", no);
@@ -544,21 +648,34 @@ extern "C" int yolo_nms_merge(float* pred, int bs, int rows, int nc, float conf_
   hipLaunchKernelGGL(nms_filter_kernel, fgrid, dim3(256), tile_bytes, st, pred, rows, no, conf_thres, min_wh, mutate_conf,
                      w.keys, w.key_pitch, w.counts);
   if (int rc = yolo_check_launch("yolo_nms_merge(filter)")) return rc;
-  return launch_merge(pred, no, -1, w, bs, rows, nc, nms_thres, max_per_class, out_dets, out_idx, out_count, cap, st);
+  return launch_merge(pred, no, -1, w, bs, rows, nc, nms_thres, max_per_class, out_dets, out_idx, out_count, cap, style, st);
+}
+extern "C" int yolo_nms_merge(float* pred, int bs, int rows, int nc, float conf_thres, float nms_thres, float min_wh,
+                              int max_per_class, int mutate_conf, float* out_dets, int32_t* out_idx, int32_t* out_count,
+                              int cap, void* workspace, size_t workspace_bytes, yolo_stream_t s) {
+  return yolo_nms_styled(pred, bs, rows, nc, conf_thres, nms_thres, min_wh, max_per_class, mutate_conf, out_dets, out_idx, out_count,
+                         cap, workspace, workspace_bytes, YOLO_NMS_MERGE, s);
 }
 
 // ---- the compact form (include/yolo_hip.h): the head convs' epilogues filter their own rows (yolo_head_decode_filter_fwd appends keys
 // and writes the survivors' records), so io is never written and never read back: head launches -> merge
-extern "C" int yolo_nms_merge_compact(void* workspace, size_t workspace_bytes, int bs, int rows, int nc, float nms_thres,
-                                      int max_per_class, float* out_dets, int32_t* out_idx, int32_t* out_count, int cap,
-                                      yolo_stream_t s) {
+extern "C" int yolo_nms_styled_compact(void* workspace, size_t workspace_bytes, int bs, int rows, int nc, float nms_thres,
+                                       int max_per_class, float* out_dets, int32_t* out_idx, int32_t* out_count, int cap,
+                                       int style, yolo_stream_t s) {
   YOLO_REQUIRE(workspace && out_dets && out_idx && out_count, "nms_merge_compact: null pointer");
-  if (int rc = nms_check(bs, rows, nc, nms_thres, max_per_class, cap)) return rc;
+  if (int rc = nms_check(bs, rows, nc, nms_thres, max_per_class, cap, style)) return rc;
   if (workspace_bytes < yolo_nms_compact_workspace_bytes(bs, rows, nc))
     return yolo_set_error(YOLO_E_WORKSPACE, "nms_compact: workspace %zu < %zu bytes", workspace_bytes,
                           yolo_nms_compact_workspace_bytes(bs, rows, nc));
   const Workspace w = carve(workspace, bs, rows, nc, true);
-  return launch_merge(w.rec, kRecFloats, 4, w, bs, rows, nc, nms_thres, max_per_class, out_dets, out_idx, out_count, cap, (hipStream_t)s);
+  return launch_merge(w.rec, kRecFloats, 4, w, bs, rows, nc, nms_thres, max_per_class, out_dets, out_idx, out_count, cap, style,
+                      (hipStream_t)s);
+}
+extern "C" int yolo_nms_merge_compact(void* workspace, size_t workspace_bytes, int bs, int rows, int nc, float nms_thres,
+                                      int max_per_class, float* out_dets, int32_t* out_idx, int32_t* out_count, int cap,
+                                      yolo_stream_t s) {
+  return yolo_nms_styled_compact(workspace, workspace_bytes, bs, rows, nc, nms_thres, max_per_class, out_dets, out_idx, out_count, cap,
+                                 YOLO_NMS_MERGE, s);
 }
 
 

@@ -205,21 +205,24 @@ class Plan(GuardedAlloc, _Runs):
                 K.decode(hd["sym"].buf.tensor, hd["anchors"], self.n_class, hd["stride"], io, hd["row"], p)
 
     def launch_detect(self, x, io, ps, nms_out, conf_thres, nms_thres, timing=None, join=True, after_nms=None, whole_batch=False,
-                      wait_for=None, compact=False, cu_partition=False):
-        """forward + decode + MERGE-NMS into caller-provided buffers; no host sync (``cu_partition`` / ``whole_batch`` / ``join`` are
+                      wait_for=None, compact=False, cu_partition=False, nms_style="MERGE"):
+        """forward + decode + NMS (``nms_style``: utils.non_max_suppression) into caller-provided buffers; no host sync (``cu_partition`` / ``whole_batch`` / ``join`` are
         the StreamedPlan's: one list on the current stream has nothing to partition).  ``compact=True``: the compact NMS form
         (``io`` is not written and may be None; include/yolo_hip.h yolo_head_decode_filter_fwd) where the plan allows it.
         nms_out = (dets [bs,cap,7] f32, idx [bs,cap] i32, count [bs] i32).  ``timing``: one (start, end)
         event pair per stream, recorded around the conv launch list.  ``after_nms(i, lo, hi)`` is called in
         the context of stream i right after the NMS launch of images [lo, hi) (see distributed.PipelinedGather)."""
+        from ._lib import nms_style_id
         from .utils.utils import MAX_PER_CLASS, MIN_WH, nms_launch
+        style = nms_style_id(nms_style)
         if compact and self.compact_ok:
             ws = self.compact_workspace()
             self._launch(x, None, ps, timing=timing[0] if timing else None, compact=(ws, conf_thres, MIN_WH))
-            K.nms_merge_compact(ws, x.shape[0], self.rows_total, self.n_class, nms_thres, *nms_out, max_per_class=MAX_PER_CLASS)
+            K.nms_styled_compact(ws, x.shape[0], self.rows_total, self.n_class, nms_thres, *nms_out, style=style,
+                                 max_per_class=MAX_PER_CLASS)
         else:
             self._launch(x, io, ps, timing=timing[0] if timing else None)
-            nms_launch(io, conf_thres, nms_thres, nms_out, slot=0)
+            nms_launch(io, conf_thres, nms_thres, nms_out, slot=0, nms_style=nms_style)
         if after_nms is not None:
             after_nms(0, 0, x.shape[0])
 
@@ -414,8 +417,10 @@ class StreamedPlan(_Runs):
         return len(self.streams)
 
     def launch_detect(self, x, io, ps, nms_out, conf_thres, nms_thres, timing=None, join=True, after_nms=None, whole_batch=False,
-                      wait_for=None, cu_partition=False, compact=False):
-        """``compact=True``: the compact NMS form - the heads filter their own rows, ``io`` is neither written nor read and may be
+                      wait_for=None, cu_partition=False, compact=False, nms_style="MERGE"):
+        """``nms_style``: the suppression style of either NMS form (utils.non_max_suppression).
+
+        ``compact=True``: the compact NMS form - the heads filter their own rows, ``io`` is neither written nor read and may be
         None (include/yolo_hip.h yolo_head_decode_filter_fwd; +1.7 % on SPP-640 x 32 from the io store alone) - where the plans allow it.
 
         ``wait_for``: an event every pipeline of this call waits for before its first launch (pipelined calls do not wait for
@@ -440,7 +445,9 @@ class StreamedPlan(_Runs):
         work nor for this one: successive calls then form S free-running pipelines (in-order per stream, so
         buffer reuse is safe) — the caller synchronises before reading results, and before a joined call on the same plan
         (the pipelines run on their own, CU-partitioned streams: ``pipe_streams``)."""
+        from ._lib import nms_style_id
         from .utils.utils import MAX_PER_CLASS, MIN_WH, nms_launch
+        style = nms_style_id(nms_style)
         cur = torch.cuda.current_stream()
         whole = whole_batch and not join
         if whole:
@@ -490,10 +497,10 @@ class StreamedPlan(_Runs):
                 if side_nms:
                     nst.wait_event(self._heads_done[i])
                 if cmp_ is not None:
-                    K.nms_merge_compact(cmp_[0], hi - lo, pl.rows_total, pl.n_class, nms_thres, *(t[lo:hi] for t in nms_out),
-                                        max_per_class=MAX_PER_CLASS)
+                    K.nms_styled_compact(cmp_[0], hi - lo, pl.rows_total, pl.n_class, nms_thres, *(t[lo:hi] for t in nms_out),
+                                         style=style, max_per_class=MAX_PER_CLASS)
                 else:
-                    nms_launch(io[lo:hi], conf_thres, nms_thres, tuple(t[lo:hi] for t in nms_out), slot=i)
+                    nms_launch(io[lo:hi], conf_thres, nms_thres, tuple(t[lo:hi] for t in nms_out), slot=i, nms_style=nms_style)
                 if after_nms is not None:
                     after_nms(i, lo, hi)
                 if side_nms:

@@ -14,7 +14,7 @@ from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU6, DT_BF16, DT_F16, DT_F32, Yo
                    check, load)
 
 __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pick", "stem", "resunit", "resunit_supported", "resunit_form", "maxpool", "spp", "dwconv3x3", "dwconv", "se", "se_workspace_bytes", "mbconv", "mbconv_supported", "mbconv_form", "pack_mbconv", "conv3x3_pool", "conv3x3_pool_supported", "conv2d_splitk", "conv2d_splitk_plan", "decode", "head_decode", "head_decode_supported",
-           "nms_merge", "pack_conv_weight", "roundup", "run_ops"]
+           "nms_merge", "nms_styled", "nms_styled_compact", "pack_conv_weight", "roundup", "run_ops"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -495,6 +495,24 @@ def nms_merge(pred, conf_thres, nms_thres, out_dets, out_idx, out_count, workspa
                                 stream_ptr()), "nms_merge")
 
 
+def nms_styled(pred, conf_thres, nms_thres, out_dets, out_idx, out_count, workspace, *, style=_lib.NMS_MERGE, min_wh=2.0,
+               max_per_class=100, mutate_conf=False):
+    """``nms_merge`` with the suppression style as an argument (yolo_nms_styled; ``style`` = a _lib.NMS_* value)."""
+    _need_cuda(pred, out_dets, out_idx, out_count, workspace)
+    if pred.dtype != torch.float32 or pred.dim() != 3 or not pred.is_contiguous():
+        raise RuntimeError("nms: prediction must be contiguous float32 [bs, rows, 5+nc]")
+    bs, rows, no = pred.shape
+    cap = out_dets.shape[1]
+    if tuple(out_dets.shape) != (bs, cap, 7) or tuple(out_idx.shape) != (bs, cap) or out_count.numel() != bs:
+        raise RuntimeError("nms: output shape mismatch")
+    if out_dets.dtype != torch.float32 or out_idx.dtype != torch.int32 or out_count.dtype != torch.int32:
+        raise RuntimeError("nms: output dtype mismatch")
+    check(load().yolo_nms_styled(_ptr(pred), bs, rows, no - 5, float(conf_thres), float(nms_thres), float(min_wh),
+                                 int(max_per_class), int(bool(mutate_conf)), _ptr(out_dets), _ptr(out_idx),
+                                 _ptr(out_count), cap, _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                 int(style), stream_ptr()), "nms_styled")
+
+
 def nms_compact_workspace_bytes(bs, rows, nc) -> int:
     return int(load().yolo_nms_compact_workspace_bytes(bs, rows, nc))
 
@@ -521,6 +539,19 @@ def nms_merge_compact(workspace, bs, rows, nc, nms_thres, out_dets, out_idx, out
     check(load().yolo_nms_merge_compact(_ptr(workspace), workspace.numel() * workspace.element_size(), bs, rows, nc, float(nms_thres),
                                         int(max_per_class), _ptr(out_dets), _ptr(out_idx), _ptr(out_count), cap, stream_ptr()),
           "nms_merge_compact")
+
+
+def nms_styled_compact(workspace, bs, rows, nc, nms_thres, out_dets, out_idx, out_count, *, style=_lib.NMS_MERGE, max_per_class=100):
+    """``nms_merge_compact`` with the suppression style as an argument (yolo_nms_styled_compact; ``style`` = a _lib.NMS_* value)."""
+    _need_cuda(workspace, out_dets, out_idx, out_count)
+    cap = out_dets.shape[1]
+    if tuple(out_dets.shape) != (bs, cap, 7) or tuple(out_idx.shape) != (bs, cap) or out_count.numel() != bs:
+        raise RuntimeError("nms: output shape mismatch")
+    if out_dets.dtype != torch.float32 or out_idx.dtype != torch.int32 or out_count.dtype != torch.int32:
+        raise RuntimeError("nms: output dtype mismatch")
+    check(load().yolo_nms_styled_compact(_ptr(workspace), workspace.numel() * workspace.element_size(), bs, rows, nc, float(nms_thres),
+                                         int(max_per_class), _ptr(out_dets), _ptr(out_idx), _ptr(out_count), cap, int(style),
+                                         stream_ptr()), "nms_styled_compact")
 
 
 def cu_masked_stream(cu_bits, device):

@@ -236,7 +236,7 @@ class YOLOBase(nn.Module):
                 return plan.run_graph(x)
             return plan.run(x)
 
-    def detect_stream(self, batches, conf_thres=0.5, nms_thres=0.5, depth=None):
+    def detect_stream(self, batches, conf_thres=0.5, nms_thres=0.5, depth=None, nms_style="MERGE"):
         """``detect()`` over a stream of equally shaped batches with the GPU kept busy: a generator that yields, in order, the
         reference-style ``list[Tensor[n,7] | None]`` of every batch - batch k's list after batch k+depth-1 has been launched.
         ``depth`` = batches in flight (their output buffers form a ring): default S = the plan's pipelines (2) for models whose
@@ -244,8 +244,14 @@ class YOLOBase(nn.Module):
         and with only S in flight a pipeline idles while the host hands out one batch and launches the next).  Successive batches alternate between the pipelines (``launch_detect(whole_batch=True)``):
         no host sync per batch except the count read-back of the batch being handed out, which by then has left the GPU.  The
         pipelines share the chip (no CU partition: ``launch_detect(cu_partition=...)`` says why).
-        SPP-640 x 32: ~6,000 images/s against ~4,700 for back-to-back ``detect()`` calls (bench.py)."""
+        SPP-640 x 32: ~6,000 images/s against ~4,700 for back-to-back ``detect()`` calls (bench.py).
+        ``nms_style`` (utils.non_max_suppression): the one-call pipeline step is MERGE-only, so another style launches every batch
+        through ``launch_detect`` (the compact NMS form where the plan allows it) and has a ring of its own."""
+        from .._lib import nms_style_id
         from ..utils.utils import nms_capacity, split_detections
+        nms_style_id(nms_style)                                  # (an unknown style raises here, before anything is launched)
+        merge = nms_style == "MERGE"
+        ring_key = (lambda d: d) if merge else (lambda d: (d, nms_style))     # ring pool: MERGE rings under their depth, as before
         if self.training:
             raise NotImplementedError("detect_stream() is an inference call: .eval() first")
         ring, pending, plan, shape, dev = [], [], None, None, None
@@ -266,7 +272,7 @@ class YOLOBase(nn.Module):
                     # the ring (output buffers, pinned count buffers, events, prebuilt pipeline steps) of the last generator that
                     # finished on this plan is taken over: building one costs more than 40 YOLOv3-tiny batches take
                     pool = plan.__dict__.setdefault("_stream_rings", {})
-                    ring = pool.pop(depth, None) or []
+                    ring = pool.pop(ring_key(depth), None) or []          # (a MERGE ring holds pipeline steps: never handed to another style)
                     for item in ring:
                         if item[4] is not None:
                             item[4].step.conf_thres, item[4].step.nms_thres = float(conf_thres), float(nms_thres)
@@ -277,7 +283,7 @@ class YOLOBase(nn.Module):
                                    torch.empty((shape[0],), dtype=torch.int32, device=x.device))
                             # one FFI call per batch where the plan allows it (engine.FastStep: yolo_pipeline_step), in the compact NMS
                             # form: the heads filter their own rows, io is never written (include/yolo_hip.h)
-                            fast = plan.fast_pipeline(slot, None, out, conf_thres, nms_thres) if hasattr(plan, "fast_pipeline") else None
+                            fast = plan.fast_pipeline(slot, None, out, conf_thres, nms_thres) if merge and hasattr(plan, "fast_pipeline") else None
                             io, ps = (None, ()) if fast is not None else plan.new_outputs(want_p=False)
                             ring.append((io, ps, out, torch.cuda.Event(), fast))
                 elif tuple(x.shape) != shape or x.device != dev:
@@ -296,7 +302,7 @@ class YOLOBase(nn.Module):
                     ready = torch.cuda.Event()
                     ready.record()                               # x was produced on the caller's stream: the pipeline waits for it
                     plan.launch_detect(x, io, ps, out, conf_thres, nms_thres, join=False, whole_batch=True, wait_for=ready, compact=True,
-                                       after_nms=lambda i, lo, hi, done=done: done.record(torch.cuda.current_stream()))
+                                       nms_style=nms_style, after_nms=lambda i, lo, hi, done=done: done.record(torch.cuda.current_stream()))
             while pending:
                 yield self._collect(pending.pop(0))
         finally:
@@ -304,7 +310,7 @@ class YOLOBase(nn.Module):
                 torch.cuda.synchronize(dev)
                 pending.clear()
             if plan is not None and ring and len(ring) == depth:
-                plan.__dict__.setdefault("_stream_rings", {})[depth] = ring      # drained: the next generator on this plan reuses it
+                plan.__dict__.setdefault("_stream_rings", {})[ring_key(depth)] = ring      # drained: the next generator on this plan reuses it
 
     @staticmethod
     def _collect(item):
@@ -315,16 +321,19 @@ class YOLOBase(nn.Module):
         done.synchronize()
         return split_detections(*out)
 
-    def detect(self, x, conf_thres=0.5, nms_thres=0.5):
+    def detect(self, x, conf_thres=0.5, nms_thres=0.5, nms_style="MERGE"):
         """The composition inside reference test_model (utils/utils.py:374-378):
-        ``non_max_suppression(model(x)[0], conf_thres, nms_thres)``."""
+        ``non_max_suppression(model(x)[0], conf_thres, nms_thres)``.  ``nms_style`` (utils.non_max_suppression): 'MERGE' takes the
+        one-call pipeline step where the plan has one; that step is MERGE-only, so the other styles take the per-launch path."""
+        from .._lib import nms_style_id
         from ..utils.utils import nms_capacity, split_detections
+        nms_style_id(nms_style)
         if self.training:
             raise NotImplementedError("detect() is an inference call: .eval() first")
         x = x.float().contiguous()
         plan = self.plan_for(x)
         with torch.cuda.device(x.device):
-            fast = plan.detect_step(conf_thres, nms_thres) if hasattr(plan, "detect_step") else None
+            fast = plan.detect_step(conf_thres, nms_thres) if nms_style == "MERGE" and hasattr(plan, "detect_step") else None
             if fast is not None:                             # one whole-batch launch list + NMS behind ONE FFI call (engine.FastStep)
                 fast.launch(x)
                 return fast.collect()
@@ -333,5 +342,5 @@ class YOLOBase(nn.Module):
             out = (torch.empty((bs, cap, 7), dtype=torch.float32, device=x.device),
                    torch.empty((bs, cap), dtype=torch.int32, device=x.device),
                    torch.empty((bs,), dtype=torch.int32, device=x.device))
-            plan.launch_detect(x, io, ps, out, conf_thres, nms_thres, compact=True)     # (compact NMS form where the plan allows it)
+            plan.launch_detect(x, io, ps, out, conf_thres, nms_thres, compact=True, nms_style=nms_style)     # (compact NMS form where the plan allows it)
             return split_detections(*out)

@@ -1,13 +1,15 @@
 """Host mirror of the post-process part of reference utils/utils.py.
 
 ``non_max_suppression`` keeps the reference signature and return value
-(utils.py:200-206,293) and runs the batched MERGE-NMS kernels (csrc/nms.hip).
+(utils.py:200-206,293) and runs the batched NMS kernels (csrc/nms.hip) in one of the
+reference's four styles (``nms_style=``: 'MERGE', which the reference hard-codes, 'OR', 'AND', 'SOFT').
 """
 from __future__ import annotations
 
 import torch
 
 from .. import kernels as K
+from .._lib import nms_style_id
 
 MIN_WH = 2.0               # reference utils.py:207
 MAX_PER_CLASS = 100        # reference utils.py:247-250
@@ -37,9 +39,10 @@ def nms_capacity(rows: int, nc: int) -> int:
 
 
 def nms_raw(prediction: torch.Tensor, conf_thres: float, nms_thres: float, inplace_conf: bool = False,
-            out=None):
+            out=None, nms_style: str = "MERGE"):
     """Launch only (no host sync).  Returns (dets [bs,cap,7], idx [bs,cap], count [bs]) device tensors;
     rows beyond count[b] are unspecified.  ``out`` lets a caller pass static buffers (graph capture)."""
+    style = nms_style_id(nms_style)
     if prediction.dim() != 3:
         raise RuntimeError("prediction must be [bs, rows, 5+nc]")
     if not prediction.is_cuda:
@@ -57,19 +60,20 @@ def nms_raw(prediction: torch.Tensor, conf_thres: float, nms_thres: float, inpla
                torch.empty((bs, cap), dtype=torch.int32, device=dev),
                torch.empty((bs,), dtype=torch.int32, device=dev))
     with torch.cuda.device(prediction.device):          # the library launches on the current device's stream
-        K.nms_merge(prediction, conf_thres, nms_thres, out[0], out[1], out[2], _workspace(prediction.device, bs, rows, nc),
-                    min_wh=MIN_WH, max_per_class=MAX_PER_CLASS, mutate_conf=inplace_conf)
+        K.nms_styled(prediction, conf_thres, nms_thres, out[0], out[1], out[2], _workspace(prediction.device, bs, rows, nc),
+                     style=style, min_wh=MIN_WH, max_per_class=MAX_PER_CLASS, mutate_conf=inplace_conf)
     return out
 
 
-def nms_launch(prediction, conf_thres, nms_thres, out, slot=0, inplace_conf=False):
+def nms_launch(prediction, conf_thres, nms_thres, out, slot=0, inplace_conf=False, nms_style="MERGE"):
     """Launch the NMS kernels on the current stream into ``out`` = (dets, idx, count); the workspace is private to the
     current stream (``slot`` is kept for callers of the old signature and ignored)."""
+    style = nms_style_id(nms_style)
     bs, rows, no = prediction.shape
     with torch.cuda.device(prediction.device):
-        K.nms_merge(prediction, conf_thres, nms_thres, out[0], out[1], out[2],
-                    _workspace(prediction.device, bs, rows, no - 5), min_wh=MIN_WH, max_per_class=MAX_PER_CLASS,
-                    mutate_conf=inplace_conf)
+        K.nms_styled(prediction, conf_thres, nms_thres, out[0], out[1], out[2],
+                     _workspace(prediction.device, bs, rows, no - 5), style=style, min_wh=MIN_WH, max_per_class=MAX_PER_CLASS,
+                     mutate_conf=inplace_conf)
     return out
 
 
@@ -99,8 +103,15 @@ def split_detections(dets, idx, count, with_indices=False):
     return out, [next(parts) if n else None for n in counts]
 
 
-def non_max_suppression(prediction, conf_thres=0.5, nms_thres=0.5, inplace_conf=False, with_indices=False):
-    """Drop-in for reference ``non_max_suppression`` (utils.py:200-293, 'MERGE' style).
+def non_max_suppression(prediction, conf_thres=0.5, nms_thres=0.5, inplace_conf=False, with_indices=False, nms_style="MERGE"):
+    """Drop-in for reference ``non_max_suppression`` (utils.py:200-293).
+
+    ``nms_style`` is the reference's one-word switch (utils.py:240; names as there, case-sensitive): 'MERGE' (what the reference
+    ships with: conf-weighted mean boxes, :266-275), 'OR' (greedy hard NMS, :253-259; a row with iou == nms_thres is removed),
+    'AND' (:260-265: a head is kept only if it overlaps a remaining row by more than 0.5; lone rows of a class with several rows
+    are erased) and 'SOFT' (:277-287: nothing is removed, conf decays by exp(-iou^2 / 0.5) per earlier row).  In 'OR', 'AND' and
+    'SOFT' the boxes are the input rows' corners, unchanged.  'SOFT' conf values carry the rounding of expf (<= 4e-5 relative
+    over a class's chain of up to 99 factors); everything else is bit-defined.  Anything else raises ``ValueError``.
 
     Returns a list (len bs) of ``Tensor[n,7]`` = (x1, y1, x2, y2, conf, class_conf, class) sorted by
     conf descending, or ``None`` for an image with no detections.
@@ -112,7 +123,7 @@ def non_max_suppression(prediction, conf_thres=0.5, nms_thres=0.5, inplace_conf=
     The reference's unstable argsort (:237,:291) is replaced by a total order
     (conf desc, then class, then input row) — identical whenever conf values are distinct.
     """
-    return split_detections(*nms_raw(prediction, conf_thres, nms_thres, inplace_conf), with_indices=with_indices)
+    return split_detections(*nms_raw(prediction, conf_thres, nms_thres, inplace_conf, nms_style=nms_style), with_indices=with_indices)
 
 
 def xywh2xyxy(x):
@@ -179,11 +190,11 @@ def _dict_from_results(data, targets, imgs_path, orig_shapes, cur_shape):
     return data
 
 
-def predict_dataset(model, batches, conf_thresh=0.1, nms_thresh=0.1):
+def predict_dataset(model, batches, conf_thresh=0.1, nms_thresh=0.1, nms_style="MERGE"):
     """The loop of the reference's ``test_model`` (utils.py:357-378) up to its prediction dictionary: for every
     ``(imgs, targets, imgs_path, shapes)`` batch (the reference dataset's collate format; ``targets`` is ignored):
     forward, NMS, back-projection.  The COCO scoring that follows in the reference (``coco_helper`` + pycocotools,
-    utils.py:380-393) is outside this path and not installed here."""
+    utils.py:380-393) is outside this path and not installed here.  ``nms_style``: see ``non_max_suppression``."""
     was_training = model.training
     model.eval()
     data = {}
@@ -191,7 +202,7 @@ def predict_dataset(model, batches, conf_thresh=0.1, nms_thresh=0.1):
         for imgs, _targets, imgs_path, shapes in batches:
             imgs = imgs.to(next(model.parameters()).device)
             with torch.no_grad():
-                det = model.detect(imgs, conf_thresh, nms_thresh)
+                det = model.detect(imgs, conf_thresh, nms_thresh, nms_style=nms_style)
             _dict_from_results(data, det, imgs_path, shapes, tuple(imgs.shape[-2:]))
     finally:
         if was_training:
