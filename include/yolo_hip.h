@@ -301,6 +301,37 @@ YOLO_API int yolo_nms_styled_compact(void* workspace, size_t workspace_bytes, in
                                      int max_per_class, float* out_dets, int32_t* out_idx, int32_t* out_count, int cap,
                                      int style, yolo_stream_t s);
 
+/* ---- compute_loss / build_targets / wh_iou (utils/utils.py:99-197) on the raw head tensors p of `io, p = model(x)`: FORWARD VALUE
+ *  ONLY - nothing here forms a gradient (csrc/loss.hip).
+ *  Geometry, all HOST arrays: na / ny / nx [nl] per YOLO layer (nl <= 4, na <= 8) and anchor_vec = the layers' anchor_vec values
+ *  exactly as the Python layer holds them (anchors / stride, yolo_layer.py:109; never recomputed here), (w, h) pairs, layers back to
+ *  back: 2 * sum(na) floats.  n_grids of layer l is (nx[l], ny[l]) (yolo_layer.py:111).
+ *  targets: device f32 [nt, 6] = image, class, x, y, w, h (x..h normalised to the image); nt == 0 is legal (targets may be NULL).
+ *  p: HOST array of nl device pointers, p[l] = f32 [bs, na, ny, nx, 5 + nc] contiguous.
+ *  Target assignment per (layer, target), every step one IEEE fp32 operation in the reference's order: gwh = wh * n_grids (:169),
+ *  wh_iou against each anchor (:116-121), the FIRST maximum (:172), kept iff iou > iou_thresh (:177), b / class / gi / gj by
+ *  truncation (:181-183), txy = gxy - floor(gxy) (:187), twh = logf(gwh / anchor) (:190).  A kept target with image outside [0, bs),
+ *  class outside [0, nc), gi outside [0, nx), gj outside [0, ny) or a NaN among them - the reference raises an IndexError there - is
+ *  NOT assigned; its record is flagged and it is counted in status[0].
+ *  workspace (yolo_loss_workspace_bytes; caller-owned, nothing in it needs initialising) starts with the records:
+ *    int32 [nl][max(nt, 1)][12] = valid, b, a, gj, gi, class, txy[2], twh[2] (float bits), flagged, 0 - slot order is target order;
+ *  the tconf map (one byte per row of every layer, cleared by every call), the float64 partial sums of the objectness pass and four
+ *  float64 terms per record follow.
+ *  yolo_build_targets_fwd: the map and the records (for callers who want the assignment).
+ *  yolo_loss_fwd: the same, then the loss (:137-155).  gains: HOST f32 [4] = k * h['xy_loss'], k * h['wh_loss'], k * h['cls_loss'],
+ *  k * h['conf_loss'] with k = bs (:136).  class_weight: device f32 [nc] or NULL (CrossEntropyLoss(weight=), :130; ignored for
+ *  nc == 1, where the class term is BCEWithLogits against the class INDEX, :152).  out: device f32 [5] = lxy, lwh, lconf, lcls, loss
+ *  (:157).  status: device int32 [1 + nl] = flagged targets, then the kept targets of each layer.
+ *  No atomics: terms in fp32, sums in float64 in an order fixed by the shapes - bit-identical from run to run. */
+YOLO_API size_t yolo_loss_workspace_bytes(int nl, const int32_t* na, const int32_t* ny, const int32_t* nx, int bs, int nt);
+YOLO_API int yolo_build_targets_fwd(const float* targets, int nt, int nl, const int32_t* na, const int32_t* ny, const int32_t* nx,
+                                    const float* anchor_vec, int bs, int nc, float iou_thresh, void* workspace,
+                                    size_t workspace_bytes, yolo_stream_t s);
+YOLO_API int yolo_loss_fwd(const float* const* p, const float* targets, int nt, int nl, const int32_t* na, const int32_t* ny,
+                           const int32_t* nx, const float* anchor_vec, int bs, int nc, float iou_thresh, const float* gains,
+                           const float* class_weight, void* workspace, size_t workspace_bytes, float* out, int32_t* status,
+                           yolo_stream_t s);
+
 /* ---- scale_coords (utils/utils.py:296-303): map kept boxes from the network-input frame back to each original
  *  image: dets [bs,cap,row_floats] (columns 0..3 = x1,y1,x2,y2) in place; params_dev: device f32 [bs][4] =
  *  {pad_x, pad_y, gain, n_rows}; do_round = the `.round()` of the caller at utils.py:313. */

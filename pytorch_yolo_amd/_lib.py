@@ -115,6 +115,12 @@ SIGNATURES = {
                                [C.c_int, C.c_void_p]),
     "yolo_nms_styled_compact": (C.c_int, [C.c_void_p, C.c_size_t] + [C.c_int] * 3 + [C.c_float, C.c_int] + [C.c_void_p] * 3 +
                                 [C.c_int, C.c_int, C.c_void_p]),
+    "yolo_loss_workspace_bytes": (C.c_size_t, [C.c_int] + [C.POINTER(C.c_int32)] * 3 + [C.c_int] * 2),
+    "yolo_build_targets_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int32)] * 3 + [C.POINTER(C.c_float), C.c_int, C.c_int,
+                                         C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "yolo_loss_fwd": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int32)] * 3 +
+                      [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t,
+                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "yolo_scale_coords": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "yolo_letterbox_u8_fwd": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_double] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p] +
                               [C.c_int] * 4 + [C.c_float, C.c_void_p]),

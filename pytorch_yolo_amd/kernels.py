@@ -14,7 +14,7 @@ from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU6, DT_BF16, DT_F16, DT_F32, Yo
                    check, load)
 
 __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pick", "stem", "resunit", "resunit_supported", "resunit_form", "maxpool", "spp", "dwconv3x3", "dwconv", "se", "se_workspace_bytes", "mbconv", "mbconv_supported", "mbconv_form", "pack_mbconv", "conv3x3_pool", "conv3x3_pool_supported", "conv2d_splitk", "conv2d_splitk_plan", "decode", "head_decode", "head_decode_supported",
-           "nms_merge", "nms_styled", "nms_styled_compact", "pack_conv_weight", "roundup", "run_ops"]
+           "nms_merge", "nms_styled", "nms_styled_compact", "loss_workspace_bytes", "build_targets_fwd", "loss_fwd", "LOSS_REC_WORDS", "pack_conv_weight", "roundup", "run_ops"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -511,6 +511,65 @@ def nms_styled(pred, conf_thres, nms_thres, out_dets, out_idx, out_count, worksp
                                  int(max_per_class), int(bool(mutate_conf)), _ptr(out_dets), _ptr(out_idx),
                                  _ptr(out_count), cap, _ptr(workspace), workspace.numel() * workspace.element_size(),
                                  int(style), stream_ptr()), "nms_styled")
+
+
+LOSS_REC_WORDS = 12     # int32 words of one record of yolo_build_targets_fwd: valid, b, a, gj, gi, class, txy[2], twh[2], flagged, 0
+
+
+def _loss_geometry(geom, anchor_vec):
+    """ctypes arrays of (na, ny, nx) per layer and of the layers' anchor_vec (w, h) pairs back to back."""
+    nl = len(geom)
+    arr = lambda k: (C.c_int32 * max(nl, 1))(*[int(g[k]) for g in geom])
+    flat = [float(v) for layer in anchor_vec for pair in layer for v in pair]
+    return nl, arr(0), arr(1), arr(2), (C.c_float * max(len(flat), 1))(*flat)
+
+
+def loss_workspace_bytes(geom, bs, nt) -> int:
+    """Bytes of the workspace of build_targets_fwd / loss_fwd; ``geom`` = [(na, ny, nx)] per YOLO layer."""
+    nl, na, ny, nx, _ = _loss_geometry(geom, [])
+    n = int(load().yolo_loss_workspace_bytes(nl, na, ny, nx, int(bs), int(nt)))
+    if n == 0:
+        check(-1, "loss_workspace_bytes")
+    return n
+
+
+def _loss_targets(targets):
+    if targets.dim() != 2 or targets.shape[1] != 6 or targets.dtype != torch.float32 or not targets.is_contiguous():
+        raise RuntimeError("loss: targets must be a contiguous float32 [nt, 6] tensor (image, class, x, y, w, h)")
+    return targets.shape[0]
+
+
+def build_targets_fwd(targets, geom, anchor_vec, bs, nc, iou_thresh, workspace):
+    """Target assignment of reference build_targets (yolo_build_targets_fwd): fills the tconf map and the records at the start of
+    ``workspace`` (int32 [nl, max(nt, 1), LOSS_REC_WORDS])."""
+    _need_cuda(targets, workspace)
+    nt = _loss_targets(targets)
+    nl, na, ny, nx, av = _loss_geometry(geom, anchor_vec)
+    check(load().yolo_build_targets_fwd(_ptr(targets) if nt else None, nt, nl, na, ny, nx, av, int(bs), int(nc), float(iou_thresh),
+                                        _ptr(workspace), workspace.numel() * workspace.element_size(), stream_ptr()), "build_targets")
+
+
+def loss_fwd(p, targets, geom, anchor_vec, nc, iou_thresh, gains, class_weight, workspace, out, status):
+    """compute_loss forward (yolo_loss_fwd): ``p`` = the raw head tensors [bs, na, ny, nx, 5 + nc] (contiguous float32), ``gains`` =
+    (k xy_loss, k wh_loss, k cls_loss, k conf_loss); writes out f32 [5] and status int32 [1 + nl]."""
+    _need_cuda(targets, class_weight, workspace, out, status, *p)
+    nt = _loss_targets(targets)
+    if len(geom) != len(p) or not p:
+        raise RuntimeError("loss: one geometry entry per head tensor")
+    bs = p[0].shape[0]
+    for t, (na_l, ny_l, nx_l) in zip(p, geom):
+        if tuple(t.shape) != (bs, na_l, ny_l, nx_l, nc + 5) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"loss: head tensor {tuple(t.shape)} is not contiguous float32 [{bs}, {na_l}, {ny_l}, {nx_l}, {nc + 5}]")
+    if class_weight is not None and (class_weight.dtype != torch.float32 or class_weight.numel() != nc or not class_weight.is_contiguous()):
+        raise RuntimeError(f"loss: class_weight must be contiguous float32 [{nc}]")
+    if out.dtype != torch.float32 or out.numel() != 5 or status.dtype != torch.int32 or status.numel() != 1 + len(p) \
+            or not out.is_contiguous() or not status.is_contiguous():
+        raise RuntimeError("loss: out must be float32 [5] and status int32 [1 + layers]")
+    nl, na, ny, nx, av = _loss_geometry(geom, anchor_vec)
+    ptrs = (C.c_void_p * nl)(*[t.data_ptr() for t in p])
+    check(load().yolo_loss_fwd(ptrs, _ptr(targets) if nt else None, nt, nl, na, ny, nx, av, bs, int(nc), float(iou_thresh),
+                               (C.c_float * 4)(*[float(v) for v in gains]), _ptr(class_weight), _ptr(workspace),
+                               workspace.numel() * workspace.element_size(), _ptr(out), _ptr(status), stream_ptr()), "loss")
 
 
 def nms_compact_workspace_bytes(bs, rows, nc) -> int:

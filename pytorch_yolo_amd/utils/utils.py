@@ -3,9 +3,14 @@
 ``non_max_suppression`` keeps the reference signature and return value
 (utils.py:200-206,293) and runs the batched NMS kernels (csrc/nms.hip) in one of the
 reference's four styles (``nms_style=``: 'MERGE', which the reference hard-codes, 'OR', 'AND', 'SOFT').
+
+``compute_loss`` and ``build_targets`` (utils.py:124-197) run the kernels of csrc/loss.hip on the raw head tensors of an eval-mode
+forward: the reference's validation loss, FORWARD VALUE ONLY (no gradient, no ``grad_fn``).  ``wh_iou``, ``bbox_iou`` and
+``xyxy2xywh`` are the reference's tensor helpers on whatever device their inputs live on.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from .. import kernels as K
@@ -90,7 +95,6 @@ def split_detections(dets, idx, count, with_indices=False):
     if total == 0:
         out = [None] * len(counts)
         return (out, list(out)) if with_indices else out
-    import numpy as np
     rows = np.concatenate([np.arange(b * cap, b * cap + n, dtype=np.int64) for b, n in enumerate(counts) if n])
     rows = torch.from_numpy(rows).to(dets.device, non_blocking=True)
     packed = dets.reshape(-1, dets.shape[2]).index_select(0, rows)
@@ -136,6 +140,45 @@ def xywh2xyxy(x):
     return y
 
 
+def xyxy2xywh(x):
+    """Reference utils.py:29-43: rows (x1, y1, x2, y2) -> rows (x centre, y centre, w, h); a torch tensor or a numpy array [n, 4]."""
+    out = torch.zeros_like(x) if isinstance(x, torch.Tensor) else np.zeros_like(x)
+    for axis in (0, 1):
+        lo, hi = x[:, axis], x[:, axis + 2]
+        out[:, axis] = (lo + hi) / 2
+        out[:, axis + 2] = hi - lo
+    return out
+
+
+def _corner_columns(box, corners):
+    """(x1, y1, x2, y2) of ``box`` ([4] or [4, n]) given as corners or as (x, y, w, h): x -+ w / 2 like xywh2xyxy."""
+    if corners:
+        return box[0], box[1], box[2], box[3]
+    half_w, half_h = box[2] / 2, box[3] / 2
+    return box[0] - half_w, box[1] - half_h, box[0] + half_w, box[1] + half_h
+
+
+def bbox_iou(box1, box2, x1y1x2y2=True):
+    """Reference utils.py:63-96: IoU of one box ``box1`` [4] with every row of ``box2`` [n, 4]; both as corners (default) or as
+    (x, y, w, h).  Operation order as the reference's: area1 carries the + 1e-16, the union is (area1 + area2) - intersection."""
+    ax1, ay1, ax2, ay2 = _corner_columns(box1, x1y1x2y2)
+    bx1, by1, bx2, by2 = _corner_columns(box2.t(), x1y1x2y2)
+    overlap_w = (torch.min(ax2, bx2) - torch.max(ax1, bx1)).clamp(0)
+    overlap_h = (torch.min(ay2, by2) - torch.max(ay1, by1)).clamp(0)
+    inter = overlap_w * overlap_h
+    area1 = (ax2 - ax1) * (ay2 - ay1) + 1e-16
+    return inter / (area1 + (bx2 - bx1) * (by2 - by1) - inter)
+
+
+def wh_iou(box1, box2):
+    """Reference utils.py:99-121: IoU of the (w, h) pair ``box1`` [2] with every row of ``box2`` [n, 2], as boxes sharing a centre -
+    the anchor-to-target measure of build_targets (the assignment kernel of csrc/loss.hip forms it the same way)."""
+    w, h = box1[0], box1[1]
+    others = box2.t()
+    inter = torch.min(w, others[0]) * torch.min(h, others[1])
+    return inter / ((w * h + 1e-16) + others[0] * others[1] - inter)
+
+
 def _scale_params(img1_shape, img0_shape, n_rows):
     """(pad_x, pad_y, gain, n_rows) exactly as the reference computes them in python floats (utils.py:298-300)."""
     gain = max(img1_shape) / max(img0_shape)
@@ -174,6 +217,186 @@ def scale_detections(dets, count, img1_shape, img0_shapes, round_result=True):
     return dets
 
 
+# ---- compute_loss / build_targets (reference utils.py:124-197) on the device: csrc/loss.hip ---------------------------------------
+HYPER_KEYS = ("iou_thresh", "xy_loss", "wh_loss", "cls_loss", "conf_loss")
+_loss_ws_cache = {}
+LOSS_TARGET_STEP = 256       # the cached loss workspace is sized for the target count rounded up to this
+
+
+def _hyper_params(model):
+    h = getattr(model, "hyper_params", None)
+    if h is None or any(k not in h for k in HYPER_KEYS):
+        raise ValueError("compute_loss / build_targets need model.hyper_params with the keys " + ", ".join(HYPER_KEYS)
+                         + f" (reference utils.py:134,162), got {None if h is None else sorted(h)}")
+    return h
+
+
+def _layer_geometry(layer):
+    """(n_anchors, (nx, ny) of n_grids, anchor_vec as nested lists) of a YOLO layer, read from the attributes the reference's
+    build_targets reads (utils.py:169,171,190).  The two tensors are copied to the host once per (tensor, version): a forward at a new
+    input size replaces them (YOLOLayer._sync_grid_attrs), and only then does the next call copy - and synchronise - again."""
+    av, ng = layer.anchor_vec, layer.n_grids
+    if not isinstance(av, torch.Tensor) or not isinstance(ng, torch.Tensor):
+        return None                                       # no forward yet: the reference's attributes are still the int 0
+    cached = layer.__dict__.get("_loss_geometry")
+    if cached is None or cached[0] is not av or cached[1] is not ng or cached[2] != (av._version, ng._version):
+        vec = [[float(w), float(h)] for w, h in av.detach().cpu().tolist()]
+        grids = tuple(ng.detach().cpu().tolist())
+        cached = (av, ng, (av._version, ng._version), (len(vec), grids, vec))
+        layer.__dict__["_loss_geometry"] = cached
+    return cached[3]
+
+
+def _loss_geometry(model, shapes=None):
+    """([(na, ny, nx)], [anchor_vec]) of model.yolo_layers; with ``shapes`` (those of the head tensors) every layer is checked against
+    its tensor."""
+    geom, vecs = [], []
+    layers = list(model.yolo_layers)
+    if shapes is not None and len(shapes) != len(layers):
+        raise RuntimeError(f"compute_loss: {len(shapes)} head tensors for {len(layers)} YOLO layers")
+    for i, layer in enumerate(layers):
+        lg = _layer_geometry(layer)
+        if lg is None:
+            raise RuntimeError(f"YOLO layer {i} has no grid yet (anchor_vec / n_grids are set by a forward): run the model at this input size first")
+        na, (nxf, nyf), vec = lg
+        nx, ny = int(nxf), int(nyf)
+        if shapes is not None:
+            sh = tuple(shapes[i])
+            if len(sh) != 5 or (sh[1], sh[2], sh[3]) != (na, ny, nx) or sh[4] != int(layer.n_classes) + 5:
+                raise RuntimeError(f"YOLO layer {i}: its grid attributes (anchors {na}, n_grids ({nx}, {ny}), classes {int(layer.n_classes)}) do not match "
+                                   f"the head tensor {sh}: run the model forward at this input size before compute_loss")
+        geom.append((na, ny, nx))
+        vecs.append(vec)
+    return geom, vecs
+
+
+def _loss_workspace(device, geom, bs, nt):
+    """Scratch of the loss kernels (records / tconf map / partial sums), cached like the NMS scratch: per (device, shapes, stream), least
+    recently used entry dropped; sized for the target count rounded up to LOSS_TARGET_STEP so that batches with different counts share it."""
+    nt_cap = max(1, -(-nt // LOSS_TARGET_STEP)) * LOSS_TARGET_STEP
+    key = (device, tuple(geom), bs, nt_cap, torch.cuda.current_stream(device).cuda_stream)
+    ws = _loss_ws_cache.pop(key, None)
+    if ws is None:
+        ws = torch.empty(K.loss_workspace_bytes(geom, bs, nt_cap), dtype=torch.uint8, device=device)
+    _loss_ws_cache[key] = ws
+    while len(_loss_ws_cache) > MAX_CACHED_WORKSPACES:
+        old = _loss_ws_cache.pop(next(iter(_loss_ws_cache)))
+        old.record_stream(torch.cuda.current_stream(device))
+    return ws
+
+
+def _device_targets(targets, device):
+    targets = torch.as_tensor(targets)
+    if targets.dim() != 2 or targets.shape[1] != 6:
+        raise RuntimeError(f"targets must be [nt, 6] (image, class, x, y, w, h), got {tuple(targets.shape)}")
+    return targets.to(device=device, dtype=torch.float32).contiguous()
+
+
+def _records(workspace, nl, nt):
+    """The records at the start of a loss workspace as int32 [nl, nt, LOSS_REC_WORDS] (a view)."""
+    return workspace[:nl * nt * K.LOSS_REC_WORDS * 4].view(torch.int32).view(nl, nt, K.LOSS_REC_WORDS)
+
+
+def _out_of_range_message(n):
+    return f"{n} targets outside the batch / grid / class range (the reference raises an IndexError on them)"
+
+
+def build_targets(model, targets, bs=None, workspace=None):
+    """Drop-in for reference ``build_targets`` (utils.py:160-197): ``(txy, twh, tcls, indices)``, per-layer lists with
+    ``indices[i] = (b, a, gj, gi)`` int64, ``tcls[i]`` int64, ``txy[i]`` / ``twh[i]`` float32 [n_i, 2], kept targets in the order of
+    ``targets``.  ``targets`` ([nt, 6]: image, class, x, y, w, h) may live on the host; the result lives on the device of the model's
+    YOLO layers.  Runs the assignment kernel (yolo_build_targets_fwd) and compacts its fixed-slot records with a boolean index:
+    THIS SYNCHRONISES with the device (compute_loss does not go through here).  Ties between anchors go to the first maximum.
+    ``bs`` bounds the image index (default: the largest image index + 1); a kept target outside the batch / grid / class range raises
+    ``RuntimeError``.  ``workspace``: a caller-owned uint8 buffer of ``kernels.loss_workspace_bytes`` bytes."""
+    h = _hyper_params(model)
+    geom, vecs = _loss_geometry(model)
+    device = model.yolo_layers[0].anchor_vec.device
+    if device.type != "cuda":
+        raise RuntimeError("pytorch_yolo_amd.build_targets runs on a ROCm device only (no CPU fallback)")
+    targets = _device_targets(targets, device)
+    nt, nl, nc = targets.shape[0], len(geom), int(model.n_class)
+    if bs is None:
+        bs = max(1, int(targets[:, 0].max()) + 1) if nt else 1
+    i64 = lambda: torch.empty((0,), dtype=torch.int64, device=device)
+    if nt == 0:
+        f2 = lambda: torch.empty((0, 2), dtype=torch.float32, device=device)
+        return [f2() for _ in geom], [f2() for _ in geom], [i64() for _ in geom], [(i64(), i64(), i64(), i64()) for _ in geom]
+    with torch.cuda.device(device):
+        if workspace is None:
+            workspace = _loss_workspace(device, geom, bs, nt)
+        K.build_targets_fwd(targets, geom, vecs, bs, nc, h["iou_thresh"], workspace)
+        rec = _records(workspace, nl, nt)
+        bad = int(rec[:, :, 10].amax(0).sum())
+        if bad:
+            raise RuntimeError("build_targets: " + _out_of_range_message(bad))
+        txy, twh, tcls, indices = [], [], [], []
+        for i in range(nl):
+            r = rec[i][rec[i, :, 0] != 0]
+            cols = r.long()
+            indices.append((cols[:, 1], cols[:, 2], cols[:, 3], cols[:, 4]))
+            tcls.append(cols[:, 5])
+            fl = r[:, 6:10].contiguous().view(torch.float32)
+            txy.append(fl[:, 0:2].clone())
+            twh.append(fl[:, 2:4].clone())
+    return txy, twh, tcls, indices
+
+
+def loss_raw(p, targets, model, class_weight=None, workspace=None, out=None, status=None):
+    """Launch only (no host sync once the layers' geometry is cached): returns ``(out, status, workspace)`` device tensors - out
+    float32 [5] = (lxy, lwh, lconf, lcls, loss), status int32 [1 + layers] = (targets outside the batch / grid / class range, kept
+    targets per layer).  ``workspace`` / ``out`` / ``status`` let a caller pass static buffers (graph capture, guarded tests)."""
+    h = _hyper_params(model)
+    p = list(p)
+    if not p or not all(isinstance(t, torch.Tensor) for t in p):
+        raise RuntimeError("compute_loss: p must be the list of raw head tensors that `io, p = model(x)` returns")
+    if not all(t.is_cuda for t in p):
+        raise RuntimeError("pytorch_yolo_amd.compute_loss runs on a ROCm device only (no CPU fallback)")
+    device = p[0].device
+    p = [t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous() for t in p]
+    geom, vecs = _loss_geometry(model, [t.shape for t in p])
+    targets = _device_targets(targets, device)
+    nc, bs, nt = int(model.n_class), p[0].shape[0], targets.shape[0]
+    if class_weight is not None:
+        class_weight = torch.as_tensor(class_weight).to(device=device, dtype=torch.float32).contiguous()
+    gains = [bs * h["xy_loss"], bs * h["wh_loss"], bs * h["cls_loss"], bs * h["conf_loss"]]       # k = bs, utils.py:135-136
+    with torch.cuda.device(device):
+        if workspace is None:
+            workspace = _loss_workspace(device, geom, bs, nt)
+        if out is None:
+            out = torch.empty((5,), dtype=torch.float32, device=device)
+        if status is None:
+            status = torch.empty((1 + len(p),), dtype=torch.int32, device=device)
+        K.loss_fwd(p, targets, geom, vecs, nc, h["iou_thresh"], gains, class_weight, workspace, out, status)
+    return out, status, workspace
+
+
+def compute_loss(p, targets, model, class_weight=None, check=True):
+    """Drop-in for reference ``compute_loss`` (utils.py:124-157), FORWARD VALUE ONLY: returns ``(loss, items)`` - ``loss`` float32 [1],
+    ``items`` float32 [5] = cat(lxy, lwh, lconf, lcls, loss) - on the device, WITHOUT ``grad_fn``: nothing here can be back-propagated.
+
+    ``p`` is the list of raw head tensors [bs, na, ny, nx, 5 + nc] that ``io, p = model(x)`` returns in eval mode (in the reference the
+    same tensors in training and eval mode), on the device (no CPU fallback); tensors that are not float32 or not contiguous are
+    converted.  ``targets`` [nt, 6] = image, class, x, y, w, h (normalised) may live on the host; ``nt == 0`` is legal.  ``model`` is
+    read for ``hyper_params`` (keys iou_thresh, xy_loss, wh_loss, cls_loss, conf_loss: ``ValueError`` without them), ``n_class`` and,
+    per YOLO layer, ``anchor_vec`` / ``n_grids`` / ``n_classes`` - which must describe ``p`` (``RuntimeError`` otherwise: run the
+    forward at this input size first).  The reference's quirks are kept: k = bs, a duplicate cell is gathered once per target, and
+    with ``n_class == 1`` the class term is BCEWithLogits against the class INDEX.
+
+    Differences from the reference:
+      * a kept target whose image, class or grid cell is out of range (the reference raises an IndexError) is left out and counted:
+        ``check=True`` reads the count - ONE host sync - and raises ``RuntimeError``; ``check=False`` never syncs and returns the loss
+        of the remaining targets (``loss_raw`` also returns the status array);
+      * ties between anchors go to the first maximum (torch.max leaves the choice open);
+      * the sums are float64 in a fixed order: the value is bit-identical from run to run, within 5e-6 relative of the reference's."""
+    out, status, _ = loss_raw(p, targets, model, class_weight)
+    if check:
+        bad = int(status[0])
+        if bad:
+            raise RuntimeError("compute_loss: " + _out_of_range_message(bad))
+    return out[4:5], out
+
+
 def _dict_from_results(data, targets, imgs_path, orig_shapes, cur_shape):
     """Drop-in for the reference's ``_dict_from_results`` (utils.py:306-327): the detections of one batch (the list
     ``non_max_suppression`` returns, rows x1 y1 x2 y2 conf cls_conf cls in the network frame ``cur_shape``) are mapped
@@ -190,21 +413,36 @@ def _dict_from_results(data, targets, imgs_path, orig_shapes, cur_shape):
     return data
 
 
-def predict_dataset(model, batches, conf_thresh=0.1, nms_thresh=0.1, nms_style="MERGE"):
+def predict_dataset(model, batches, conf_thresh=0.1, nms_thresh=0.1, nms_style="MERGE", loss=False):
     """The loop of the reference's ``test_model`` (utils.py:357-378) up to its prediction dictionary: for every
-    ``(imgs, targets, imgs_path, shapes)`` batch (the reference dataset's collate format; ``targets`` is ignored):
-    forward, NMS, back-projection.  The COCO scoring that follows in the reference (``coco_helper`` + pycocotools,
-    utils.py:380-393) is outside this path and not installed here.  ``nms_style``: see ``non_max_suppression``."""
+    ``(imgs, targets, imgs_path, shapes)`` batch (the reference dataset's collate format): forward, NMS, back-projection.
+    The COCO scoring that follows in the reference (``coco_helper`` + pycocotools,
+    utils.py:380-393) is outside this path and not installed here.  ``nms_style``: see ``non_max_suppression``.
+
+    ``loss=False`` ignores ``targets`` and returns the dictionary.  ``loss=True`` takes the two-line path per batch
+    (``io, p = model(imgs)``, ``non_max_suppression(io, ...)``), computes ``compute_loss(p, targets, model)`` (the model needs
+    ``hyper_params``) and returns ``(data, items)``: ``items`` = the batch-size-weighted mean of the five loss items
+    (lxy, lwh, lconf, lcls, loss) as a list of floats."""
     was_training = model.training
     model.eval()
     data = {}
+    acc, seen = None, 0
     try:
-        for imgs, _targets, imgs_path, shapes in batches:
+        for imgs, targets, imgs_path, shapes in batches:
             imgs = imgs.to(next(model.parameters()).device)
             with torch.no_grad():
-                det = model.detect(imgs, conf_thresh, nms_thresh, nms_style=nms_style)
+                if loss:
+                    io, p = model(imgs)
+                    det = non_max_suppression(io, conf_thresh, nms_thresh, nms_style=nms_style)
+                    items = compute_loss(p, targets, model)[1].double() * imgs.shape[0]
+                    acc = items if acc is None else acc + items
+                    seen += imgs.shape[0]
+                else:
+                    det = model.detect(imgs, conf_thresh, nms_thresh, nms_style=nms_style)
             _dict_from_results(data, det, imgs_path, shapes, tuple(imgs.shape[-2:]))
     finally:
         if was_training:
             model.train()
+    if loss:
+        return data, ([float("nan")] * 5 if acc is None else (acc / seen).tolist())
     return data
