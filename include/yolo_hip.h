@@ -134,7 +134,8 @@ YOLO_API int yolo_conv3x3_pool_fwd(const void* x, const void* w_packed, const fl
                                    int pool, yolo_stream_t s);
 
 /* ---- depthwise 3x3 conv + bias + act (MobileNetV2 inverted residual; torchvision, see
- *      models/yolov3_tiny_mobilenet.py:11-34).  w: f32 [9][c] tap-major, bias f32 [c]. */
+ *      models/yolov3_tiny_mobilenet.py:11-34).  w: f32 [9][c] tap-major, bias f32 [c].  act: any YOLO_ACT_*, applied in fp32 to
+ *      the sum before the one narrowing to bf16, with the operations of yolo_dwconv_fwd; a value outside the enum is YOLO_E_ARG. */
 YOLO_API int yolo_dwconv3x3_fwd(const void* x, const float* w, const float* bias, void* y, int n, int h, int w_,
                        int c, int in_c_total, int in_c_offset, int ho, int wo, int out_c_total,
                        int out_c_offset, int stride, int act, yolo_stream_t s);

@@ -203,6 +203,20 @@ __global__ __launch_bounds__(512) void spp_lines_kernel(bf16_t* __restrict__ buf
 }
 
 // ------------------------------------------------------------------------------------------------
+// Activation of both depthwise 3x3 forms: every YOLO_ACT_*, with the operations of efficient.hip's act_f (LeakyReLU as the select
+// this file has always used: the same bits as fmaxf(v, 0.1f * v) on finite values).  `act` is a kernel argument, tested after the
+// last tap.  The stride-1 strip kernel sits at 168 registers, the most that leave three waves per SIMD: the selects stay a
+// sequence of conditional assignments (a chain of early returns compiles to 174), and swish - expf and a division, 174 as well -
+// is a template parameter of the strip form, so that the layers of the shipped models, none of them swish, run the code they ran.
+template <bool SWISH = true>
+__device__ __forceinline__ float dw_act(float v, int act) {
+  if (SWISH && act == YOLO_ACT_SWISH) return v / (1.f + expf(-v));          // x * sigmoid(x)
+  if (act == YOLO_ACT_LEAKY01) v = v > 0.f ? v : 0.1f * v;
+  if (act == YOLO_ACT_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
+  if (act == YOLO_ACT_RELU) v = fmaxf(v, 0.f);
+  return v;
+}
+
 // Depthwise 3x3 (pad 1) + bias + activation, one thread = 8 channels of one output pixel, fp32 math.  (Reference form:
 // yolo_dwconv3x3_fwd launches the strip kernel below; YOLO_DWCONV_DEBUG=1 selects this one.)
 __global__ __launch_bounds__(256) void dwconv3x3_kernel(const bf16_t* __restrict__ x, const float* __restrict__ wt,
@@ -238,12 +252,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const bf16_t* __restrict
   }
   bf16x8 o;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    float v = acc[e];
-    if (act == YOLO_ACT_LEAKY01) v = v > 0.f ? v : 0.1f * v;
-    if (act == YOLO_ACT_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-    o[e] = (bf16_t)v;
-  }
+  for (int e = 0; e < 8; ++e) o[e] = (bf16_t)dw_act(acc[e], act);
   *reinterpret_cast<bf16x8*>(y + ((b * ho + oh) * wo + ow) * out_ct + out_co + g * 8) = o;
 }
 
@@ -410,7 +419,7 @@ extern "C" int yolo_spp_fwd(void* buf, int n, int h, int w, int c, yolo_stream_t
 // Same fp32 operation order as the one-pixel form (bias, then taps row by row), so the results are identical.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-template <int S, int R>
+template <int S, int R, bool SWISH>
 __global__ __launch_bounds__(256) void dwconv3x3_strip_kernel(const bf16_t* __restrict__ x, const float* __restrict__ wt,
                                                               const float* __restrict__ bias, bf16_t* __restrict__ y, int h,
                                                               int w, int c, int in_ct, int in_co, int ho, int wo, int out_ct,
@@ -474,12 +483,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_strip_kernel(const bf16_t* __re
       }
     bf16x8 o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float v = acc[e >> 1][e & 1];
-      if (act == YOLO_ACT_LEAKY01) v = v > 0.f ? v : 0.1f * v;
-      if (act == YOLO_ACT_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-      o[e] = (bf16_t)v;
-    }
+    for (int e = 0; e < 8; ++e) o[e] = (bf16_t)dw_act<SWISH>(acc[e >> 1][e & 1], act);
     *reinterpret_cast<bf16x8*>(y + ((b * ho + oh) * wo + ow) * out_ct + out_co + g * 8) = o;
   }
 }
@@ -489,8 +493,12 @@ static int launch_dw_strip(const bf16_t* x, const float* w, const float* bias, b
                            int in_co, int ho, int wo, int out_ct, int out_co, int act, hipStream_t s) {
   const int strips = (ho + R - 1) / R;
   const long total = (long)n * strips * wo * (c / 8);
-  hipLaunchKernelGGL((dwconv3x3_strip_kernel<S, R>), dim3(blocks_for(total)), dim3(256), 0, s, x, w, bias, y, h, w_, c, in_ct, in_co,
-                     ho, wo, out_ct, out_co, act, strips, total);
+  if (act == YOLO_ACT_SWISH)
+    hipLaunchKernelGGL((dwconv3x3_strip_kernel<S, R, true>), dim3(blocks_for(total)), dim3(256), 0, s, x, w, bias, y, h, w_, c, in_ct,
+                       in_co, ho, wo, out_ct, out_co, act, strips, total);
+  else
+    hipLaunchKernelGGL((dwconv3x3_strip_kernel<S, R, false>), dim3(blocks_for(total)), dim3(256), 0, s, x, w, bias, y, h, w_, c, in_ct,
+                       in_co, ho, wo, out_ct, out_co, act, strips, total);
   return yolo_check_launch("yolo_dwconv3x3_fwd");
 }
 
@@ -504,6 +512,7 @@ extern "C" int yolo_dwconv3x3_fwd(const void* x, const float* w, const float* bi
                                   int stride, int act, yolo_stream_t s) {
   YOLO_REQUIRE(x && w && bias && y && n > 0 && c > 0 && c % 8 == 0, "dwconv: bad arguments");
   YOLO_REQUIRE(stride == 1 || stride == 2, "dwconv: stride %d", stride);
+  YOLO_REQUIRE(act >= YOLO_ACT_NONE && act <= YOLO_ACT_SWISH, "dwconv: activation %d", act);
   YOLO_REQUIRE(ho == (h + 2 - 3) / stride + 1 && wo == (w_ + 2 - 3) / stride + 1, "dwconv: bad output size");
   YOLO_REQUIRE(in_c_total % 8 == 0 && in_c_offset % 8 == 0 && out_c_total % 8 == 0 && out_c_offset % 8 == 0,
                "dwconv: views must be 8-channel aligned");

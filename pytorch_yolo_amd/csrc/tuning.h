@@ -23,8 +23,9 @@
 // (tests/test_conv_exact_gpu.py); kFamT20Always / kFamT20Never and kFamStreamAlways / kFamStreamNever have their cases there and in
 // tests/test_gpu_parity.py.  The form bits of knobs 3 and 4 (kRuGeneric64, kRuT20Always, kRuT20Never, kMbStripForm) select the fused
 // kernels of the chained bit-exact cases (tests/_exact_cases.py, tests/test_fused_exact_gpu.py); kMbStripForm also runs, with the
-// shipped rules of knob 3, on the real activation scales in tests/test_gpu_parity.py.  The ablation bits give wrong results by
-// design and have no test.
+// shipped rules of knob 3, on the real activation scales in tests/test_gpu_parity.py.  kDwOnePixel and kDwFourRows are read when the
+// library loads, so tests/test_pointwise_exact_gpu.py starts one fresh interpreter per value and compares the depthwise 3x3 table
+// of tests/_exact_cases.py bit for bit in each.  The ablation bits give wrong results by design and have no test.
 #pragma once
 
 struct Tuning {
@@ -108,7 +109,7 @@ enum : int {
   kMbwNoWeightDma = 16,            // no weight DMAs after chunk 0
 };
 
-// YOLO_DWCONV_DEBUG (tuning only)
+// YOLO_DWCONV_DEBUG (tuning only): both forms give the bits of the shipped 8-row strips
 enum : int {
   kDwOnePixel = 1,                 // the one-pixel form
   kDwFourRows = 2,                 // strips of 4 rows instead of 8

@@ -260,3 +260,84 @@ def wide_tiling(n, h, w, cin, cout, stride):
 POOL_CASES = [(2, 26, 38, 16, 32, True), (1, 21, 19, 16, 64, True), (1, 21, 19, 32, 32, True), (2, 26, 38, 32, 64, True),
               (1, 21, 19, 16, 32, False), (2, 26, 38, 16, 64, False), (1, 21, 19, 32, 32, False), (1, 21, 19, 32, 64, False)]
 POOL_SEED = 6
+
+
+# ---- first-layer, depthwise and squeeze-excite kernels (tests/test_pointwise_exact_cpu.py / _gpu.py) ----------------------------------
+# A seed stands beside every row whose reference has guards: the smallest one (from the table's base) whose reference passes them
+# for every activation the row runs with.  On the maps of a few pixels (2x2, 1x1: 16 to 128 outputs) the shares are coarse, and a seed
+# is what decides them; on the others the first seed passes.
+
+# yolo_conv1_nchw_f32_fwd / yolo_conv1_pool_nchw_f32_fwd at stride 1 (conv3x3_halo.hip: 16x16 tiles, 3 per workgroup, every halo
+# requested up front): 19x50 is 2 tile rows (the last of 3 rows) and 4 tile columns (a group of 3 and a group of 1, the last of 2
+# columns), on every instantiation - cout {16, 32} x pool x cin_real 3 (the CINR = 3 template) / 1 and 8 (the generic one); a 2x2
+# image; 21x35 for the pooled form (the floor drops the odd row and column).  ((n, cin, h, w, cout, stride, act, pool), seed)
+# Achieved shares of the references: x 59-88 % needs rounding, 12-33 % ties (66-69 % / 21-25 % from 19x50 on); LeakyReLU 46-53 %
+# negative pre-activations, 72-85 % of the outputs need rounding, 8-11 % ties; ReLU6 24-30 % at 0, 17-24 % at 6, 30-37 % need rounding,
+# 10-13 % ties; no activation 64-82 % need rounding, 12-20 % ties.  Truncated x changes 12-59 % of the outputs, un-narrowed x 8-42 %.
+_S1 = [(cout, pool, cin) for cout in (16, 32) for pool in (False, True) for cin in (3, 1, 8)]
+FIRST_S1_CASES = [((2, cin, 19, 50, cout, 1, ("leaky", "relu6", "none")[(i + i // 3) % 3], pool), 400 + i) for i, (cout, pool, cin) in enumerate(_S1)]
+FIRST_S1_CASES += [((2, 3, 2, 2, 32, 1, "leaky", False), 420), ((2, 1, 2, 2, 16, 1, "relu6", False), 421), ((2, 8, 2, 2, 16, 1, "leaky", True), 422),
+                   ((2, 3, 21, 35, 16, 1, "leaky", True), 423), ((2, 8, 21, 35, 32, 1, "relu6", True), 424)]
+# the stride-2 form (conv_small.hip: 16x16 OUTPUT tiles, 5 per workgroup, two halo buffers used alternately): wo = 82 is a full group
+# of five tiles plus a group of one tile of 2 columns; 35x163 / 36x164 are the odd / even right and bottom edges
+FIRST_S2_CASES = [((2, cin, h, w, 32, 2, act, False), 440 + i) for i, (cin, (h, w), act) in enumerate(
+    (cin, hw, act) for cin in (3, 1) for hw in ((35, 163), (36, 164)) for act in ("relu6", "leaky"))]
+FIRST_CASES = FIRST_S1_CASES + FIRST_S2_CASES
+
+
+def first_id(shape):
+    return "n%d_c%d_%dx%d_co%d_s%d_%s_pool%d" % tuple(int(v) if not isinstance(v, str) else v for v in shape)
+
+
+# every activation whose result is determined bit for bit (swish = x / (1 + expf(-x)) is not: it stays with the tolerance tests)
+DW_ACTS = ("none", "leaky", "relu6", "relu")
+
+# yolo_dwconv3x3_fwd (pointwise.hip: strips of 8 output rows per thread, the rows slide through three register slots), each at
+# strides 1 and 2: a one-pixel map; h = 9, a last strip of ONE row, on a one-column map; 17 rows (odd, last strip of one row at
+# stride 1, ho = 9 at stride 2) with three channel groups; 16 rows (even, whole strips); 18 rows (even, ho = 9).  n = 2: the rows
+# outside an image must read zero, never the neighbouring image's rows (NaN cannot sit there, the values decide).  ((n, c, h, w), seed)
+DW3_CASES = [((1, 8, 1, 1), 500), ((2, 8, 9, 1), 601), ((2, 24, 17, 5), 502), ((2, 16, 16, 7), 803), ((2, 24, 18, 6), 504)]
+DW3_ROWS = [(shape, seed, stride) for shape, seed in DW3_CASES for stride in (1, 2)]
+
+
+def dw3_shape(nchw, stride, act):
+    """The exact_dw_case shape of a DW3_CASES row."""
+    return tuple(nchw) + (3, stride, act)
+
+
+# yolo_dwconv_fwd (efficient.hip) and yolo_dwconv_f32_fwd (efficient_f32.hip): k {3, 5} x stride {1, 2} on 6x8, 7x9 and 1x1 maps of two
+# images, in TensorFlow-"same" geometry and with torch's pad k // 2 where that is another one (an even map at stride 2: leading pad
+# k // 2 - 1 against k // 2); c = 8 and 24 (bf16) / 12 (float32).  (k, stride, h, w, geometry)
+def _dw_geometries():
+    from helpers import dw_geometry
+    out = []
+    for k in (3, 5):
+        for stride in (1, 2):
+            for h, w in ((6, 8), (7, 9), (1, 1)):
+                out.append((k, stride, h, w, "same"))
+                if dw_geometry(h, w, k, stride, "torch") != dw_geometry(h, w, k, stride, "same"):
+                    out.append((k, stride, h, w, "torch"))
+    return out
+
+
+DW_SEED, DW_F32_SEED = 520, 560
+# (k, stride, h, w, geometry, c) -> seed, where DW_SEED itself does not pass the guards for every activation
+DW_SEEDS = {r: 620 for r in ((3, 1, 7, 9, "same", 8), (3, 1, 1, 1, "same", 8), (3, 2, 7, 9, "same", 8), (3, 2, 1, 1, "same", 8),
+                             (5, 1, 1, 1, "same", 8), (5, 1, 1, 1, "same", 24), (5, 2, 1, 1, "same", 8), (5, 2, 1, 1, "same", 24))}
+
+
+def dw_rows():
+    """[(k, stride, h, w, geometry, c, seed)] of the bf16 table."""
+    return [g + (c, DW_SEEDS.get(g + (c,), DW_SEED)) for g in _dw_geometries() for c in (8, 24)]
+
+
+def dw_f32_rows():
+    return [g + (12, DW_F32_SEED) for g in _dw_geometries()]
+
+
+# yolo_se_fwd / yolo_se_f32_fwd, (n, h, w, c, sq): c / 8 (bf16) and c / 4 (float32) chunks of 1, 2, 4, 8, 16, 33 and 144 reach every
+# channel-group width of the pooling pass (1..32) and several groups with a partial last one; 42x50 is cut into 8 pixel ranges, 23x23
+# into 2 (a range keeps >= 256 pixels), the others are one range; 5x3 and 3x3 are smaller than one stripe of 256 / cgb pixels.
+SE_CASES = [(1, 42, 50, 8, 1), (1, 23, 23, 16, 4), (2, 5, 3, 32, 48), (2, 9, 7, 64, 64), (3, 4, 4, 128, 4), (2, 7, 9, 264, 48), (1, 3, 3, 1152, 64)]
+SE_F32_CASES = [(n, h, w, c // 2, sq) for n, h, w, c, sq in SE_CASES]
+SE_SEED = 600

@@ -460,3 +460,235 @@ def exact_chain(kind, shape, seed):
         y, aux, stats = exact_chain_reference(x, stages, res, unit=unit)
         _CHAIN_CACHE[key] = (x, stages, res, unit, y, aux, stats)
     return _CHAIN_CACHE[key]
+
+
+# ---- first-layer, depthwise and squeeze-excite cases (tests/test_pointwise_exact_cpu.py / _gpu.py) ---------------------------------
+# The first-layer kernels narrow the caller's float32 pixels to bf16 themselves, so their x is NOT representable: ten per cent zeros,
+# else +-(512..1023) / 1024 - in [0.5, 1) bf16 keeps multiples of 2^-8, so three values in four need rounding and one in four is an exact
+# tie -, and after round-to-nearest-even everything is a multiple of 2^-8 again: the chain reference takes over from there.
+# The depthwise kernels read bf16 (small integers, or multiples of 1/16 for ReLU6) or float32 (integers of eleven significant bits
+# times {-1, 0, 1}); squeeze-and-excitation reads integers whose partial sums are exact however the pooling pass splits them.
+_POINT_CACHE = {}
+
+
+def _act_any(v, act):
+    """_apply_act plus ReLU (one fmaxf)."""
+    return v.clamp(min=0.0) if act == "relu" else _apply_act(v, act)
+
+
+def _truncate_bf16(t):
+    return (t.contiguous().view(torch.int32) & -65536).view(torch.float32)
+
+
+def exact_first_layer_case(shape, seed):
+    """(x float32 NCHW as the caller holds it, w, bias) for shape = (n, cin, h, w, cout, stride, act, pool).  LeakyReLU / none:
+    integer weights in {-3..3}, bias k / 256 with |k| <= 768.  ReLU6: weights in {-2..2} with about four non-zero taps per output
+    channel (a dense 3x3 over 8 channels would put every output at a clamp), bias _relu6_bias(spread 1.5)."""
+    n, cin, h, w, cout, stride, act, pool = shape
+    g = torch.Generator().manual_seed(seed)
+    ri = _ri(g)
+    mag = ri(512, 1023, n, cin, h, w) / 1024.0
+    sign = torch.where(ri(0, 1, n, cin, h, w) == 0, -1.0, 1.0)
+    x = torch.where(ri(0, 9, n, cin, h, w) == 0, torch.zeros(()), mag * sign)
+    if act == "relu6":
+        wt = ri(-2, 2, cout, cin, 3, 3) * (torch.rand(cout, cin, 3, 3, generator=g) < 4.0 / (9 * cin)).float()
+        return x, wt, _relu6_bias(ri, cout, 1.5)
+    return x, ri(-3, 3, cout, cin, 3, 3), ri(-768, 768, cout) / 256.0
+
+
+def first_layer_reference(x, wt, bias, *, stride, act, pool, narrow="rne"):
+    """(y bf16 NCHW, stats) of conv3x3 / pad 1 + bias + act on bf16(x), narrowed once, then MaxPool2d(2, 2) (floor) when `pool`.
+    narrow="rne" is the reference: exact_chain_reference with its guards, plus one on x itself (>= 50 % of x needs rounding, >= 10 %
+    are ties).  "trunc" / "wide" (sensitivity checks, no guards): x truncated to bf16 / not narrowed at all."""
+    import torch.nn.functional as F
+    assert narrow in ("rne", "trunc", "wide")
+    stats = {}
+    if narrow == "rne":
+        nonrep, ties = exact_rounding_shares(x, _BF16)
+        assert nonrep >= 0.50 and ties >= 0.10, f"x: {nonrep:.3f} need rounding, {ties:.3f} are ties"
+        y, _, stats = exact_chain_reference(x.to(_BF16).float(), [(wt, bias, stride, 1, act)], None, unit=2.0 ** -8)
+        stats = dict(stats, x_nonrep=nonrep, x_ties=ties)
+    else:
+        xin = _truncate_bf16(x) if narrow == "trunc" else x
+        with torch.no_grad():
+            y = _apply_act(F.conv2d(xin, wt, bias, stride=stride, padding=1), act).to(_BF16)
+    if pool:
+        y = F.max_pool2d(y.float(), 2, 2).to(_BF16)            # exact: the maximum is one of the bf16 values
+    return y, stats
+
+
+def exact_first_layer(shape, seed):
+    """exact_first_layer_case + first_layer_reference, once per process: (x, w, bias, y_ref, stats).  Do not modify them."""
+    key = ("first", tuple(shape), seed)
+    if key not in _POINT_CACHE:
+        x, wt, bias = exact_first_layer_case(shape, seed)
+        y, stats = first_layer_reference(x, wt, bias, stride=shape[5], act=shape[6], pool=shape[7])
+        _POINT_CACHE[key] = (x, wt, bias, y, stats)
+    return _POINT_CACHE[key]
+
+
+def dw_geometry(h, w, k, stride, geometry):
+    """(ho, wo, leading pad): "same" = TensorFlow's (Recorder.tf_same: the odd pad row / column below / right), "torch" = pad k // 2."""
+    if geometry == "same":
+        from pytorch_yolo_amd.engine import Recorder
+        (ho, pad), (wo, pad_w) = Recorder.tf_same(h, k, stride), Recorder.tf_same(w, k, stride)
+        assert pad == pad_w
+        return ho, wo, pad
+    assert geometry == "torch"
+    pad = k // 2
+    return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1, pad
+
+
+def exact_dw_case(shape, seed, dtype):
+    """(x, w [c, 1, k, k], bias) as float32 for shape = (n, c, h, w, k, stride, act).
+      * bf16, none / LeakyReLU / ReLU: x and w integers in {-3..3}, the bias of exact_conv_case (magnitude 260..1000 on five channels
+        of six, negative on about a fifth of those, {-3..3} on the sixth);
+      * bf16, ReLU6: the no-expand recipe of exact_mbconv_case - x = {-3..3} / 16, w = 4 {-2..2}, _relu6_bias with spread 1.0 (k = 3) or
+        1.7 (k = 5);
+      * float32: x integers of magnitude < 2^11, w in {-1, 0, 1}, small integer bias (exact_conv_case's float32 recipe)."""
+    n, c, h, w, k, stride, act = shape
+    g = torch.Generator().manual_seed(seed)
+    ri = _ri(g)
+    if dtype == torch.float32:
+        return ri(-2047, 2047, n, c, h, w), ri(-1, 1, c, 1, k, k), ri(-1500, 1500, c)
+    assert dtype == _BF16
+    if act == "relu6":
+        return ri(-3, 3, n, c, h, w) / 16.0, 4.0 * ri(-2, 2, c, 1, k, k), _relu6_bias(ri, c, 1.0 if k == 3 else 1.7)
+    x, wt = ri(-3, 3, n, c, h, w), ri(-3, 3, c, 1, k, k)
+    mag = ri(260, 1000, c)
+    sign = torch.where(ri(0, 4, c) == 0, -1.0, 1.0)
+    return x, wt, torch.where(torch.arange(c) % 6 == 5, ri(-3, 3, c), mag * sign)
+
+
+def exact_dw_reference(x, wt, bias, *, stride, pad, ho, wo, act, dtype, fault=None, strip=8):
+    """(y NCHW in dtype, stats) of a depthwise conv with an explicit LEADING pad and the caller's ho x wo: x is padded by hand (zeros:
+    `pad` above / left, what the last window needs below / right), then the unpadded grouped conv, bias, activation and - bf16 - one
+    narrowing.  Without `fault` a bf16 case is REJECTED unless the fp32 conv equals the fp64 conv and stays in fp32's exact range,
+    >= 15 % of the pre-activations are negative (none / LeakyReLU / ReLU) or >= 2 % of the values sit at each clamp (ReLU6), >= 25 % of
+    the outputs need rounding and >= 2 % are exact ties; a float32 case unless the conv is exact.
+    fault (sensitivity checks, no guards):
+      "drop_tap_row"    the tap below the centre is lost on the last row of every strip of `strip` output rows
+      "next_image_row"  the row below an image's last row holds the next image's first row instead of zeros
+      "relu_as_none"    ReLU is treated as no activation"""
+    import torch.nn.functional as F
+    assert fault in (None, "drop_tap_row", "next_image_row", "relu_as_none")
+    n, c, h, w = x.shape
+    k = wt.shape[-1]
+    below, right = max((ho - 1) * stride + k - pad - h, 0), max((wo - 1) * stride + k - pad - w, 0)
+    xp = F.pad(x, (pad, right, pad, below))
+    if fault == "next_image_row":
+        assert n >= 2 and below >= 1
+        xp[:-1, :, pad + h, pad:pad + w] = x[1:, :, 0, :]
+    with torch.no_grad():
+        v = F.conv2d(xp, wt, bias, stride=stride, groups=c)[:, :, :ho, :wo]
+        assert v.shape[2:] == (ho, wo), "ho x wo does not fit the padded input"
+        if fault is None:
+            unit = float(min(x[x != 0].abs().min(), 1.0)) if bool((x != 0).any()) else 1.0
+            v64 = F.conv2d(xp.double(), wt.double(), bias.double(), stride=stride, groups=c)[:, :, :ho, :wo]
+            assert v.dtype == torch.float32 and torch.equal(v.double(), v64), "the fp32 conv of the case is not exact"
+            bound = F.conv2d(xp.abs().double(), wt.abs().double(), bias.abs().double(), stride=stride, groups=c)
+            assert float(bound.max()) < 2.0 ** 24 * unit, "a partial sum can leave the exact range of fp32"
+        if fault == "drop_tap_row":
+            assert k == 3
+            one = torch.zeros_like(wt)
+            one[:, :, 2, 1] = wt[:, :, 2, 1]
+            lost = F.conv2d(xp, one, None, stride=stride, groups=c)[:, :, :ho, :wo]
+            v = v - lost * (torch.arange(ho) % strip == strip - 1).view(-1, 1).float()
+        stats = {"negative": float((v < 0).float().mean())}
+        v = _act_any(v, "none" if (fault == "relu_as_none" and act == "relu") else act)
+        if dtype == torch.float32:
+            return v, stats
+        stats["at0"], stats["at6"] = float((v == 0).float().mean()), float((v == 6).float().mean())
+        stats["nonrep"], stats["ties"] = exact_rounding_shares(v, _BF16)
+        if fault is None:
+            bad = []
+            if act == "relu6" and min(stats["at0"], stats["at6"]) < 0.02:
+                bad.append("too few values at a clamp")
+            if act != "relu6" and stats["negative"] < 0.15:
+                bad.append("too few pre-activations are negative")
+            if stats["nonrep"] < 0.25 or stats["ties"] < 0.02:
+                bad.append("too few values need rounding or are ties")
+            assert not bad, f"the case does not exercise the rounding: {bad}; shares {stats}"
+    return v.to(_BF16), stats
+
+
+def exact_dw(shape, seed, dtype, geometry):
+    """exact_dw_case + exact_dw_reference, once per process: (x, w, bias, ho, wo, pad, y_ref, stats).  Do not modify them."""
+    key = ("dw", tuple(shape), seed, dtype, geometry)
+    if key not in _POINT_CACHE:
+        n, c, h, w, k, stride, act = shape
+        x, wt, bias = exact_dw_case(shape, seed, dtype)
+        ho, wo, pad = dw_geometry(h, w, k, stride, geometry)
+        y, stats = exact_dw_reference(x, wt, bias, stride=stride, pad=pad, ho=ho, wo=wo, act=act, dtype=dtype)
+        _POINT_CACHE[key] = (x, wt, bias, ho, wo, pad, y, stats)
+    return _POINT_CACHE[key]
+
+
+# Squeeze-and-excitation, stage by stage.  With integer x every partial sum of the pooling pass is exact whatever the split, so the
+# MEANS have one answer; the rescale is one fp32 product per value, so given the kernel's own scales y has one answer; only the two
+# FCs in between (fp32 dot products in the kernel's order, expf, a division) are compared within a bound - one derived from the
+# operands, below.
+def exact_se_case(shape, seed, dtype):
+    """(x, w1 [sq, c], b1, w2 [c, sq], b2) for shape = (n, h, w, c, sq): x integers, |x| <= 8 (bf16) or of eleven significant bits
+    (float32); W1 scaled so that the hidden pre-activations are of order one whatever the map size."""
+    n, h, w, c, sq = shape
+    g = torch.Generator().manual_seed(seed)
+    amp = 8 if dtype == _BF16 else 2047
+    x = _ri(g)(-amp, amp, n, c, h, w)
+    mean_std = max(amp / (3.0 * h * w) ** 0.5, 2.0 ** -6)
+    w1, b1 = torch.randn(sq, c, generator=g) * (1.0 / c) ** 0.5 / mean_std, torch.randn(sq, generator=g) * 0.1
+    w2, b2 = torch.randn(c, sq, generator=g) * (1.0 / sq) ** 0.5, torch.randn(c, generator=g) * 0.1
+    return x, w1, b1, w2, b2
+
+
+def se_means_reference(x, dtype):
+    """[n, c] float32: float32(sum) * (float32(1) / float32(hw)) for the bf16 kernel (se_fc_kernel multiplies by the host's 1.f / hw),
+    float32(sum) / float32(hw) for the float32 one (se_fc_f32_kernel divides).  The sums are exact: asserted."""
+    hw = x.shape[2] * x.shape[3]
+    s = x.double().sum((2, 3))
+    assert torch.equal(x, x.round()) and float(x.abs().double().sum((2, 3)).max()) < 2.0 ** 24, "a partial sum can be inexact"
+    s32, hw32 = s.float(), torch.tensor(float(hw), dtype=torch.float32)
+    assert torch.equal(s32.double(), s)
+    return s32 * (torch.tensor(1.0, dtype=torch.float32) / hw32) if dtype == _BF16 else s32 / hw32
+
+
+def se_rescale_reference(x, scale, dtype):
+    """y NCHW: dtype(float32(x) * scale[n, c]) - one fp32 product, one narrowing (bf16) or none (float32)."""
+    y = x.float() * scale.float().view(x.shape[0], x.shape[1], 1, 1)
+    return y.to(_BF16) if dtype == _BF16 else y
+
+
+def _ulp32(t):
+    """The float32 unit in the last place of |t| (float64 tensor), normal range."""
+    return torch.exp2(torch.floor(torch.log2(t.abs().clamp(min=2.0 ** -126))) - 23.0)
+
+
+def se_scales_reference(mean, w1, b1, w2, b2):
+    """(scale, bound) in float64, [n, c] each: sigmoid(W2 swish(W1 mean + b1) + b2) evaluated in float64 from float32 means, and a
+    bound on |scale_fp32 - scale| for ANY fp32 evaluation that forms each dot product with one rounding per term (an fmaf chain, a
+    tree of partial chains: se_fc_kernel has at most c and sq roundings on a path, bias included) and calls expf and a division:
+      e_v  = gamma_c * (sum_i |w1_ji mean_i| + |b1_j|)                                 gamma_n = n u / (1 - n u), u = 2^-24
+      e_h  = 1.1 * e_v + 4 ulp(h_j)                      max |swish'| = 1.0998; 4 ulp for expf (<= 2), the add and the division
+      e_s  = gamma_sq * (|b2_i| + sum_j |w2_ij h_j|) + sum_j |w2_ij| e_h_j
+      e    = 0.25 * e_s + 4 ulp(scale_i)                 max sigmoid' = 1 / 4"""
+    u = 2.0 ** -24
+    gamma = lambda k: k * u / (1.0 - k * u)
+    m, w1, b1, w2, b2 = (t.double() for t in (mean, w1, b1, w2, b2))
+    c, sq = w1.shape[1], w1.shape[0]
+    v = m @ w1.t() + b1
+    e_v = gamma(c) * (m.abs() @ w1.abs().t() + b1.abs())
+    hid = v * torch.sigmoid(v)
+    e_h = 1.1 * e_v + 4.0 * _ulp32(hid)
+    s = hid @ w2.t() + b2
+    e_s = gamma(sq) * (hid.abs() @ w2.abs().t() + b2.abs()) + e_h @ w2.abs().t()
+    scale = torch.sigmoid(s)
+    return scale, 0.25 * e_s + 4.0 * _ulp32(scale)
+
+
+def exact_se(shape, seed, dtype):
+    """exact_se_case and the exact mean reference, once per process: (x, w1, b1, w2, b2, means).  Do not modify them."""
+    key = ("se", tuple(shape), seed, dtype)
+    if key not in _POINT_CACHE:
+        ops = exact_se_case(shape, seed, dtype)
+        _POINT_CACHE[key] = ops + (se_means_reference(ops[0], dtype),)
+    return _POINT_CACHE[key]

@@ -67,6 +67,11 @@ def test_argument_errors_are_reported_without_a_gpu():
     zeros = (ctypes.c_uint32 * 8)()
     assert lib.yolo_stream_create_cu_mask(zeros, 8, ctypes.byref(out)) == -1 and b"empty mask" in lib.yolo_last_error()
     assert lib.yolo_stream_destroy(None) == -1
+    # yolo_dwconv3x3_fwd applies every YOLO_ACT_*; a value outside the enum is an argument error, not a silent "no activation"
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    for act in (-1, _lib.ACT_SWISH + 1):
+        assert lib.yolo_dwconv3x3_fwd(p, p, p, p, 1, 4, 4, 8, 8, 0, 4, 4, 8, 0, 1, act, None) == -1 and b"activation" in lib.yolo_last_error()
 
 
 def test_c_weight_packer_matches_torch_packer():
