@@ -333,6 +333,41 @@ YOLO_API int yolo_loss_fwd(const float* const* p, const float* targets, int nt, 
                            const float* class_weight, void* workspace, size_t workspace_bytes, float* out, int32_t* status,
                            yolo_stream_t s);
 
+/* ---- COCO bbox evaluation (what utils/utils.py:330-354 asks of pycocotools: COCOeval.evaluate / accumulate, and the sums of the
+ *  reference's "Mean IOU") in float64, one IEEE operation per step in pycocotools' order (csrc/coco_eval.hip).
+ *  The parameter COUNTS are fixed: 10 IoU thresholds, 4 area ranges, 101 recall thresholds, 3 maxDets; their VALUES come from the
+ *  caller (numpy): iou_thrs device f64 [10], area_rng device f64 [4][2], rec_thrs device f64 [101], max_dets HOST int32 [3]
+ *  ascending, eps = np.spacing(1).
+ *  Groups: g = image index * n_cat + category index, images and categories in ascending id order.  dt_off / gt_off: device int32
+ *  [n_img * n_cat + 1], first element of each group (the last entry is n_dt / n_gt).  Boxes are (x, y, w, h).
+ *  Detections (dt_box f64 [n_dt, 4]) stand group by group and, inside a group, in EVALUATION ORDER: descending score, ties in the
+ *  order of the results list, cut to the first max_dets[2].  GTs (gt_box f64 [n_gt, 4], gt_area f64 [n_gt], gt_crowd u8 [n_gt]) stand
+ *  group by group in annotation order.  max_gt = the largest GT count of a group (the caller knows it): above yolo_coco_max_gt()
+ *  the call fails with YOLO_E_UNSUPPORTED before anything is launched; a group whose offsets nevertheless exceed the cap is skipped
+ *  and counted in status[0] (device int32 [1]) - never truncated.
+ *  yolo_coco_match_fwd: IoU (bbIou), then evaluateImg's greedy matching per group x area range a x threshold t.  Writes per
+ *    detection dt_match / dt_ignore (device u64 [n_dt]: bit a * 10 + t), npig (device int32 [n_cat, 4]: non-ignored GTs), per group
+ *    iou_sum f64 / iou_cnt int32 [n_img * n_cat] (entries >= 0.3 of the group's D x G IoU matrix), and into the workspace
+ *    (yolo_coco_workspace_bytes(n_dt); nothing in it needs initialising) the rank of each detection inside its group.
+ *    Matched flags are kept per GT slot; pycocotools keeps annotation ids and therefore loses a match to a GT whose id is 0.
+ *  yolo_coco_accumulate_fwd: accumulate's sweep per category x area range x maxDets x threshold over the SAME dt_match / dt_ignore /
+ *    npig / workspace.  order: device int32 [n_dt], the detection indices category by category (cat_off: device int32 [n_cat + 1])
+ *    and inside a category by descending score, ties in (image, rank) order.  Writes precision f64 [10, 101, n_cat, 4, 3] and recall
+ *    f64 [10, n_cat, 4, 3] (pycocotools' layout; -1 where a category has no non-ignored GT in the range), every element.
+ *    The sweep walks yolo_coco_sweep_chunk() detections at a time. */
+YOLO_API int yolo_coco_sweep_chunk(void);
+YOLO_API int yolo_coco_max_gt(void);
+YOLO_API size_t yolo_coco_workspace_bytes(int n_dt);
+YOLO_API int yolo_coco_match_fwd(const double* dt_box, const int32_t* dt_off, int n_dt, const double* gt_box, const double* gt_area,
+                                 const uint8_t* gt_crowd, const int32_t* gt_off, int n_gt, int n_img, int n_cat, int max_gt,
+                                 const double* iou_thrs, const double* area_rng, uint64_t* dt_match, uint64_t* dt_ignore,
+                                 int32_t* npig, double* iou_sum, int32_t* iou_cnt, int32_t* status, void* workspace,
+                                 size_t workspace_bytes, yolo_stream_t s);
+YOLO_API int yolo_coco_accumulate_fwd(const int32_t* order, const int32_t* cat_off, int n_dt, int n_cat, const uint64_t* dt_match,
+                                      const uint64_t* dt_ignore, const int32_t* npig, const double* rec_thrs, const int32_t* max_dets,
+                                      double eps, const void* workspace, size_t workspace_bytes, double* precision, double* recall,
+                                      yolo_stream_t s);
+
 /* ---- scale_coords (utils/utils.py:296-303): map kept boxes from the network-input frame back to each original
  *  image: dets [bs,cap,row_floats] (columns 0..3 = x1,y1,x2,y2) in place; params_dev: device f32 [bs][4] =
  *  {pad_x, pad_y, gain, n_rows}; do_round = the `.round()` of the caller at utils.py:313. */

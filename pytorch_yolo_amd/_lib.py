@@ -121,6 +121,13 @@ SIGNATURES = {
     "yolo_loss_fwd": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int32)] * 3 +
                       [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t,
                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_coco_sweep_chunk": (C.c_int, []),
+    "yolo_coco_max_gt": (C.c_int, []),
+    "yolo_coco_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "yolo_coco_match_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p] * 9 +
+                            [C.c_size_t, C.c_void_p]),
+    "yolo_coco_accumulate_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_int32), C.c_double,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yolo_scale_coords": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "yolo_letterbox_u8_fwd": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_double] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p] +
                               [C.c_int] * 4 + [C.c_float, C.c_void_p]),

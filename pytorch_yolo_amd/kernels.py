@@ -14,7 +14,8 @@ from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU6, DT_BF16, DT_F16, DT_F32, Yo
                    check, load)
 
 __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pick", "stem", "resunit", "resunit_supported", "resunit_form", "maxpool", "spp", "dwconv3x3", "dwconv", "se", "se_workspace_bytes", "mbconv", "mbconv_supported", "mbconv_form", "pack_mbconv", "conv3x3_pool", "conv3x3_pool_supported", "conv2d_splitk", "conv2d_splitk_plan", "decode", "head_decode", "head_decode_supported",
-           "nms_merge", "nms_styled", "nms_styled_compact", "loss_workspace_bytes", "build_targets_fwd", "loss_fwd", "LOSS_REC_WORDS", "pack_conv_weight", "roundup", "run_ops"]
+           "nms_merge", "nms_styled", "nms_styled_compact", "loss_workspace_bytes", "build_targets_fwd", "loss_fwd", "LOSS_REC_WORDS", "coco_workspace_bytes", "coco_match_fwd", "coco_accumulate_fwd", "coco_sweep_chunk", "coco_max_gt",
+           "COCO_T", "COCO_R", "COCO_A", "COCO_M", "pack_conv_weight", "roundup", "run_ops"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -570,6 +571,70 @@ def loss_fwd(p, targets, geom, anchor_vec, nc, iou_thresh, gains, class_weight, 
     check(load().yolo_loss_fwd(ptrs, _ptr(targets) if nt else None, nt, nl, na, ny, nx, av, bs, int(nc), float(iou_thresh),
                                (C.c_float * 4)(*[float(v) for v in gains]), _ptr(class_weight), _ptr(workspace),
                                workspace.numel() * workspace.element_size(), _ptr(out), _ptr(status), stream_ptr()), "loss")
+
+
+COCO_T, COCO_R, COCO_A, COCO_M = 10, 101, 4, 3      # fixed counts of csrc/coco_eval.hip: IoU thresholds, recall thresholds, area ranges, maxDets
+
+
+def coco_sweep_chunk() -> int:
+    """Detections one step of the precision / recall sweep covers (kChunk of csrc/coco_eval.hip)."""
+    return int(load().yolo_coco_sweep_chunk())
+
+
+def coco_max_gt() -> int:
+    """Cap on the GTs of one (image, category) group."""
+    return int(load().yolo_coco_max_gt())
+
+
+def coco_workspace_bytes(n_dt) -> int:
+    n = int(load().yolo_coco_workspace_bytes(int(n_dt)))
+    if n == 0:
+        check(-1, "coco_workspace_bytes")
+    return n
+
+
+def _coco_typed(what, t, dtype, numel):
+    if t.dtype != dtype or t.numel() != numel or not t.is_contiguous():
+        raise RuntimeError(f"coco: {what} must be contiguous {dtype} with {numel} elements, not {t.dtype} {tuple(t.shape)}")
+
+
+def coco_match_fwd(dt_box, dt_off, gt_box, gt_area, gt_crowd, gt_off, n_img, n_cat, max_gt, iou_thrs, area_rng, dt_match, dt_ignore,
+                   npig, iou_sum, iou_cnt, status, workspace):
+    """IoU and greedy matching (yolo_coco_match_fwd).  dt_box f64 [nD, 4] in evaluation order inside each (image, category) group,
+    gt_box f64 [nG, 4], gt_area f64 [nG], gt_crowd u8 [nG], dt_off / gt_off int32 [n_img * n_cat + 1]; writes dt_match / dt_ignore
+    int64 [nD] (bit a * 10 + t), npig int32 [n_cat, 4], iou_sum f64 / iou_cnt int32 [n_img * n_cat], status int32 [1]."""
+    _need_cuda(dt_box, dt_off, gt_box, gt_area, gt_crowd, gt_off, iou_thrs, area_rng, dt_match, dt_ignore, npig, iou_sum, iou_cnt, status,
+               workspace)
+    n_dt, n_gt, ng = dt_box.shape[0], gt_box.shape[0], int(n_img) * int(n_cat)
+    f64, i32, i64 = torch.float64, torch.int32, torch.int64
+    for what, t, dtype, numel in (("dt_box", dt_box, f64, n_dt * 4), ("dt_off", dt_off, i32, ng + 1), ("gt_box", gt_box, f64, n_gt * 4),
+                                  ("gt_area", gt_area, f64, n_gt), ("gt_crowd", gt_crowd, torch.uint8, n_gt), ("gt_off", gt_off, i32, ng + 1),
+                                  ("iou_thrs", iou_thrs, f64, COCO_T), ("area_rng", area_rng, f64, COCO_A * 2),
+                                  ("dt_match", dt_match, i64, n_dt), ("dt_ignore", dt_ignore, i64, n_dt), ("npig", npig, i32, n_cat * COCO_A),
+                                  ("iou_sum", iou_sum, f64, ng), ("iou_cnt", iou_cnt, i32, ng), ("status", status, i32, 1)):
+        _coco_typed(what, t, dtype, numel)
+    check(load().yolo_coco_match_fwd(_ptr(dt_box), _ptr(dt_off), n_dt, _ptr(gt_box), _ptr(gt_area), _ptr(gt_crowd), _ptr(gt_off), n_gt,
+                                     int(n_img), int(n_cat), int(max_gt), _ptr(iou_thrs), _ptr(area_rng), _ptr(dt_match), _ptr(dt_ignore),
+                                     _ptr(npig), _ptr(iou_sum), _ptr(iou_cnt), _ptr(status), _ptr(workspace),
+                                     workspace.numel() * workspace.element_size(), stream_ptr()), "coco_match")
+
+
+def coco_accumulate_fwd(order, cat_off, n_cat, dt_match, dt_ignore, npig, rec_thrs, max_dets, eps, workspace, precision, recall):
+    """Precision / recall sweep (yolo_coco_accumulate_fwd) over the flags coco_match_fwd wrote (same workspace).  order int32 [nD]:
+    detection indices category by category (cat_off int32 [n_cat + 1]), descending score inside; writes precision f64
+    [10, 101, n_cat, 4, 3] and recall f64 [10, n_cat, 4, 3]."""
+    _need_cuda(order, cat_off, dt_match, dt_ignore, npig, rec_thrs, workspace, precision, recall)
+    n_dt = order.numel()
+    f64, i32, i64 = torch.float64, torch.int32, torch.int64
+    for what, t, dtype, numel in (("order", order, i32, n_dt), ("cat_off", cat_off, i32, n_cat + 1), ("dt_match", dt_match, i64, n_dt),
+                                  ("dt_ignore", dt_ignore, i64, n_dt), ("npig", npig, i32, n_cat * COCO_A), ("rec_thrs", rec_thrs, f64, COCO_R),
+                                  ("precision", precision, f64, COCO_T * COCO_R * n_cat * COCO_A * COCO_M),
+                                  ("recall", recall, f64, COCO_T * n_cat * COCO_A * COCO_M)):
+        _coco_typed(what, t, dtype, numel)
+    md = (C.c_int32 * COCO_M)(*[int(v) for v in max_dets])
+    check(load().yolo_coco_accumulate_fwd(_ptr(order), _ptr(cat_off), n_dt, int(n_cat), _ptr(dt_match), _ptr(dt_ignore), _ptr(npig),
+                                          _ptr(rec_thrs), md, float(eps), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                          _ptr(precision), _ptr(recall), stream_ptr()), "coco_accumulate")
 
 
 def nms_compact_workspace_bytes(bs, rows, nc) -> int:

@@ -7,6 +7,9 @@ reference's four styles (``nms_style=``: 'MERGE', which the reference hard-codes
 ``compute_loss`` and ``build_targets`` (utils.py:124-197) run the kernels of csrc/loss.hip on the raw head tensors of an eval-mode
 forward: the reference's validation loss, FORWARD VALUE ONLY (no gradient, no ``grad_fn``).  ``wh_iou``, ``bbox_iou`` and
 ``xyxy2xywh`` are the reference's tensor helpers on whatever device their inputs live on.
+
+``bench_results`` and ``test_model`` (utils.py:330-393) score a results list with the COCO bbox metrics on the device
+(utils/coco_eval.py, csrc/coco_eval.hip) instead of pycocotools.
 """
 from __future__ import annotations
 
@@ -15,6 +18,8 @@ import torch
 
 from .. import kernels as K
 from .._lib import nms_style_id
+from . import coco_helper
+from .coco_eval import STAT_NAMES, coco_eval
 
 MIN_WH = 2.0               # reference utils.py:207
 MAX_PER_CLASS = 100        # reference utils.py:247-250
@@ -416,8 +421,8 @@ def _dict_from_results(data, targets, imgs_path, orig_shapes, cur_shape):
 def predict_dataset(model, batches, conf_thresh=0.1, nms_thresh=0.1, nms_style="MERGE", loss=False):
     """The loop of the reference's ``test_model`` (utils.py:357-378) up to its prediction dictionary: for every
     ``(imgs, targets, imgs_path, shapes)`` batch (the reference dataset's collate format): forward, NMS, back-projection.
-    The COCO scoring that follows in the reference (``coco_helper`` + pycocotools,
-    utils.py:380-393) is outside this path and not installed here.  ``nms_style``: see ``non_max_suppression``.
+    The COCO scoring that follows in the reference (``coco_helper`` + pycocotools, utils.py:380-393) is ``test_model`` /
+    ``bench_results`` below, on the kernels of csrc/coco_eval.hip.  ``nms_style``: see ``non_max_suppression``.
 
     ``loss=False`` ignores ``targets`` and returns the dictionary.  ``loss=True`` takes the two-line path per batch
     (``io, p = model(imgs)``, ``non_max_suppression(io, ...)``), computes ``compute_loss(p, targets, model)`` (the model needs
@@ -446,3 +451,32 @@ def predict_dataset(model, batches, conf_thresh=0.1, nms_thresh=0.1, nms_style="
     if loss:
         return data, ([float("nan")] * 5 if acc is None else (acc / seen).tolist())
     return data
+
+
+def bench_results(results_path, cocoGt, device="cuda"):
+    """Drop-in for the reference's ``bench_results`` (utils.py:330-354): the COCO bbox metrics of a results file (or an in-memory
+    results list) against ``cocoGt`` (a pycocotools ``COCO``, any object with a ``.dataset`` dict, or the dataset dict), computed
+    by ``coco_eval`` on ``device``.  Prints summarize's twelve lines and the Mean IOU line, returns the reference's dictionary."""
+    res = coco_eval(cocoGt, results_path, device)
+    for line in res.summary_lines():
+        print(line)
+    print(f"Mean IOU: {res.mean_iou:.2f}")
+    return dict(zip(STAT_NAMES + ("IOU",), [float(v) for v in res.stats] + [res.mean_iou]))
+
+
+def test_model(model, dataset, batch_size, num_workers, device, conf_thresh=0.1, nms_thresh=0.1):
+    """Drop-in for the reference's ``test_model`` (utils.py:357-393): a DataLoader over ``dataset`` with its ``collate_fn``,
+    ``predict_dataset``, ``results_from_dict`` against ``dataset.coco.dataset`` and ``bench_results``.  The results list goes to the
+    evaluation in memory (the reference writes it to a temporary JSON file for pycocotools).  ``model.training`` is restored."""
+    loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, num_workers=num_workers, shuffle=False, pin_memory=True,
+                                         collate_fn=dataset.collate_fn)
+    was_training = model.training
+    try:
+        data = predict_dataset(model, loader, conf_thresh, nms_thresh)
+        results = coco_helper.results_from_dict(data, dataset.coco.dataset)
+        return bench_results(results, dataset.coco, device)
+    finally:
+        model.train(was_training)
+
+
+test_model.__test__ = False        # (a name pytest would otherwise collect wherever it is imported)
