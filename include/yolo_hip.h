@@ -302,8 +302,8 @@ YOLO_API int yolo_nms_styled_compact(void* workspace, size_t workspace_bytes, in
                                      int max_per_class, float* out_dets, int32_t* out_idx, int32_t* out_count, int cap,
                                      int style, yolo_stream_t s);
 
-/* ---- compute_loss / build_targets / wh_iou (utils/utils.py:99-197) on the raw head tensors p of `io, p = model(x)`: FORWARD VALUE
- *  ONLY - nothing here forms a gradient (csrc/loss.hip).
+/* ---- compute_loss / build_targets / wh_iou (utils/utils.py:99-197) on the raw head tensors p of `io, p = model(x)`: the forward
+ *  value (yolo_loss_fwd) and its gradient with respect to p (yolo_loss_bwd); nothing else has a gradient (csrc/loss.hip).
  *  Geometry, all HOST arrays: na / ny / nx [nl] per YOLO layer (nl <= 4, na <= 8) and anchor_vec = the layers' anchor_vec values
  *  exactly as the Python layer holds them (anchors / stride, yolo_layer.py:109; never recomputed here), (w, h) pairs, layers back to
  *  back: 2 * sum(na) floats.  n_grids of layer l is (nx[l], ny[l]) (yolo_layer.py:111).
@@ -332,6 +332,23 @@ YOLO_API int yolo_loss_fwd(const float* const* p, const float* targets, int nt, 
                            const int32_t* nx, const float* anchor_vec, int bs, int nc, float iou_thresh, const float* gains,
                            const float* class_weight, void* workspace, size_t workspace_bytes, float* out, int32_t* status,
                            yolo_stream_t s);
+/*  yolo_loss_bwd: d loss / d p of the loss above, a first derivative that stops at p.  It takes the inputs of yolo_loss_fwd (not
+ *  its results out and status, which it neither reads nor writes) and
+ *    grad_loss  device f32 [1]: the upstream gradient of loss, read on the device;
+ *    grad_p     HOST array of nl device pointers, grad_p[l] = f32 of the shape of p[l], contiguous, 16-byte aligned.
+ *  EVERY element of every grad_p[l] is written, whatever it held.  With G = *grad_loss, n_l = the kept valid targets of layer l and
+ *  rows_l = bs na ny nx: word 4 of every row = G gains[3] / rows_l * (sigmoid(x4) - tconf); in the cell of a kept valid target, summed
+ *  over the targets that share the cell in target order (the reference gathers the cell once per target): words 0-1
+ *  G gains[0] (s - txy) s (1 - s) / n_l with s = sigmoid(x); words 2-3 G gains[1] (x - twh) / n_l; class word k, nc > 1,
+ *  G gains[2] w_c (softmax_k - [k == c]) / sum over the layer's targets of w_c (w = class_weight or 1); nc == 1
+ *  G gains[2] (sigmoid(x5) - c) / n_l; every other element +0.0.  Flagged targets are left out as in the forward.
+ *  Stateless: it runs the memset and the assignment itself, in the same workspace layout (yolo_loss_workspace_bytes), and needs nothing
+ *  an earlier call left there; no allocation, no host synchronisation, no retained pointer.  No atomics: bit-identical from run to
+ *  run, cells shared by any number of targets included.  G is multiplied into the gain first. */
+YOLO_API int yolo_loss_bwd(const float* const* p, const float* targets, int nt, int nl, const int32_t* na, const int32_t* ny,
+                           const int32_t* nx, const float* anchor_vec, int bs, int nc, float iou_thresh, const float* gains,
+                           const float* class_weight, void* workspace, size_t workspace_bytes, const float* grad_loss,
+                           float* const* grad_p, yolo_stream_t s);
 
 /* ---- COCO bbox evaluation (what utils/utils.py:330-354 asks of pycocotools: COCOeval.evaluate / accumulate, and the sums of the
  *  reference's "Mean IOU") in float64, one IEEE operation per step in pycocotools' order (csrc/coco_eval.hip).

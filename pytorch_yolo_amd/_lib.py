@@ -121,6 +121,9 @@ SIGNATURES = {
     "yolo_loss_fwd": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int32)] * 3 +
                       [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t,
                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yolo_loss_bwd": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int, C.c_int] + [C.POINTER(C.c_int32)] * 3 +
+                      [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_size_t,
+                       C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
     "yolo_coco_sweep_chunk": (C.c_int, []),
     "yolo_coco_max_gt": (C.c_int, []),
     "yolo_coco_workspace_bytes": (C.c_size_t, [C.c_int]),

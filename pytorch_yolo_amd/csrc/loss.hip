@@ -1,7 +1,8 @@
-// Validation loss on the device for gfx950: build_targets and compute_loss, FORWARD VALUE ONLY (no gradient is formed anywhere).
+// Validation loss on the device for gfx950: build_targets, compute_loss and the gradient of compute_loss with respect to p.
 //
 // Replaces the ATen dispatches and the Python loop of compute_loss / build_targets / wh_iou (reference utils/utils.py:99-197) on the
-// raw head tensors p that `io, p = model(x)` returns in eval mode.
+// raw head tensors p that `io, p = model(x)` returns in eval mode.  The gradient (yolo_loss_bwd, at the end of this file) is d loss /
+// d p and nothing else: it stops at p - nothing here propagates through a convolution -, and it is a first derivative only.
 //
 // Arithmetic contract
 //   * the target assignment (which anchor, kept or not, which cell, txy) is a chain of single IEEE fp32 operations in the reference's
@@ -28,6 +29,22 @@
 //                 call on the YOLOv3-SPP 640 x 32 shapes with 512 targets and nc = 80 (rocprofv3 kernel trace)
 //   loss_finish   one workgroup: per layer the conf partials and the records' terms in a fixed order, the means and gains;
 //                 writes out[5] = (lxy, lwh, lconf, lcls, loss) and status = (flagged targets, kept targets per layer)
+//
+// Launches of the gradient (yolo_loss_bwd; the same memset and loss_assign first: it uses nothing a forward call left behind):
+//   loss_grad_dense  the hot part: writes EVERY element of every gradient tensor (274 MB on the shapes above).  The tensor of a layer
+//                    is treated as one flat float array; a thread owns kGradVecs 16-byte pieces of it, 4 KiB apart, so a wave64 stores
+//                    1 KiB of consecutive bytes per instruction whatever the row length (6, 8, 85 floats: rows are not 16-byte
+//                    aligned, the pieces are).  A piece holds at most one word 4 (rows are >= 6 floats); only the lanes whose piece
+//                    holds one read anything: that word of p and the row's tconf byte.  Every other word is +0.0
+//   loss_grad_cells  one wave64 per record.  The records of a layer that share the cell (b, a, gj, gi) share the row of p; the one in
+//                    the lowest slot owns the cell, the others leave.  The owner counts the layer's valid records and sums their class
+//                    weights (float64, lane-strided, shuffle tree: the same bits in every wave), then sums the sharers' terms word by
+//                    word in slot order (float64) and STORES words 0-3 and 5.. of the row - a plain store over the zeros of the dense
+//                    pass, which ran before it on the stream; word 4 belongs to the dense pass.  No atomic anywhere: the result does
+//                    not depend on how workgroups are scheduled.  Every wave walks the nt records of its layer twice or three times:
+//                    quadratic in nt, 0.8 M record reads at nt = 512
+// Gradient arithmetic: fp32 terms; G = *grad_loss is folded into the gain first (G * gain, then / n), so that a call with G and a
+// call with G = 1 and the gains scaled by G agree bit for bit whenever G * gain is exact.
 #include "common.h"
 
 namespace {
@@ -39,6 +56,9 @@ constexpr int kWaves = kThreads / YOLO_WAVE;
 constexpr int kConfRows = 1024;      // rows of one loss_conf workgroup: four per thread
 constexpr int kRecWords = 12;        // valid, b, a, gj, gi, cls, txy[2], twh[2], flagged, 0  (48 bytes)
 constexpr int kTermWords = 4;        // float64 per record: xy terms, wh terms, class numerator, class denominator
+constexpr int kGradVecs = 4;         // 16-byte stores of one loss_grad_dense thread
+constexpr int kGradStep = kThreads * 4;               // floats between two of them: one store instruction of the workgroup
+constexpr int kGradChunk = kGradStep * kGradVecs;     // floats of one loss_grad_dense workgroup (16 KiB)
 
 struct Geom {
   int nl, bs, nc, nt;
@@ -53,6 +73,13 @@ struct Heads {
 };
 struct Gains {
   float xy, wh, cls, conf;
+};
+struct Grads {
+  float* g[kMaxLayers];
+};
+struct GradGeom {
+  int wg_first[kMaxLayers + 1];      // first loss_grad_dense workgroup of a layer
+  unsigned step_rows, step_words;    // kGradStep floats = step_rows rows + step_words words
 };
 
 // workspace: records int32 [nl][max(nt, 1)][kRecWords] | tconf uint8 [sum rows, each layer on a 256-byte boundary] | partials f64
@@ -303,7 +330,155 @@ __global__ __launch_bounds__(kThreads) void loss_finish_kernel(const Geom g, con
 }
 
 // ---------------------------------------------------------------------------------------------------
-// argument checks shared by the three entry points; fills g (anchors only when anchor_vec is given)
+// the gradient of compute_loss with respect to p
+__device__ __forceinline__ float sigmoid_f32(float x) { return __fdiv_rn(1.f, 1.f + expf(-x)); }
+
+__global__ __launch_bounds__(kThreads) void loss_grad_dense_kernel(const Geom g, const GradGeom gg, const Heads hd, const Grads gr,
+                                                                   const uint8_t* __restrict__ tconf, float gain_conf,
+                                                                   const float* __restrict__ grad_loss) {
+  const int wg = blockIdx.x;
+  int l = 0;
+#pragma unroll
+  for (int i = 1; i < kMaxLayers; ++i) l = (i < g.nl && wg >= gg.wg_first[i]) ? i : l;
+  const int rows = pick(g.rows, l);
+  const unsigned no = (unsigned)g.nc + 5u;
+  const unsigned n = (unsigned)rows * no;                                      // < 2^31 (loss_geometry)
+  const float* __restrict__ pl = pick(hd.p, l);
+  float* __restrict__ gl = pick(gr.g, l);
+  const uint8_t* __restrict__ tc = tconf + pick(g.tconf_off, l);
+  const float coef = __fdiv_rn(grad_loss[0] * gain_conf, (float)rows);         // BCEWithLogits' mean over the rows, :154
+  const unsigned e0 = (unsigned)(wg - pick(gg.wg_first, l)) * (unsigned)kGradChunk + threadIdx.x * 4u;
+  unsigned row = e0 / no, w = e0 - row * no;                                   // the first word of this thread's first piece
+  float x[kGradVecs];
+  uint8_t t[kGradVecs];                                                        // (raw: converting here would wait for each load in turn)
+  int k[kGradVecs];                                                            // where in the piece word 4 sits, or -1
+#pragma unroll
+  for (int u = 0; u < kGradVecs; ++u) {                                        // the loads of all pieces first
+    const bool has = e0 + (unsigned)(u * kGradStep) < n && w >= 1u && w <= 4u; // (row < rows then, and row * no + 4 < n)
+    k[u] = has ? 4 - (int)w : -1;
+    x[u] = 0.f;
+    t[u] = 0;
+    if (has) {
+      x[u] = pl[(size_t)row * no + 4];
+      t[u] = tc[row];
+    }
+    row += gg.step_rows;
+    w += gg.step_words;
+    if (w >= no) {
+      w -= no;
+      ++row;
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kGradVecs; ++u) {
+    const unsigned e = e0 + (unsigned)(u * kGradStep);
+    const float v = coef * (sigmoid_f32(x[u]) - (t[u] ? 1.f : 0.f));
+    const float4 o = make_float4(k[u] == 0 ? v : 0.f, k[u] == 1 ? v : 0.f, k[u] == 2 ? v : 0.f, k[u] == 3 ? v : 0.f);
+    if (e + 4u <= n) {
+      *reinterpret_cast<float4*>(gl + e) = o;                                  // (gl is 16-byte aligned: yolo_loss_bwd checks)
+    } else {                                                                   // the last 1-3 floats of a layer
+      if (e < n) gl[e] = o.x;
+      if (e + 1u < n) gl[e + 1u] = o.y;
+      if (e + 2u < n) gl[e + 2u] = o.z;
+    }
+  }
+}
+
+// one wave64 per (layer, target) record; every branch on the record, the slot or a ballot is wave-uniform
+__global__ __launch_bounds__(kThreads) void loss_grad_cells_kernel(const Geom g, const Heads hd, const Grads gr,
+                                                                   const int32_t* __restrict__ rec,
+                                                                   const float* __restrict__ class_weight, const Gains gains,
+                                                                   const float* __restrict__ grad_loss) {
+  const int lane = threadIdx.x & (YOLO_WAVE - 1);
+  const int slot = blockIdx.x * kWaves + (int)(threadIdx.x / YOLO_WAVE);
+  if (slot >= g.nl * g.nt) return;
+  const int l = slot / g.nt, t = slot - l * g.nt;
+  const int32_t* __restrict__ rl = rec + (long)l * g.nt * kRecWords;           // the records of this layer
+  const int32_t* r = rl + (long)t * kRecWords;
+  if (!r[0]) return;
+  const int b = r[1], a = r[2], gj = r[3], gi = r[4];
+  const bool weighted = g.nc > 1 && class_weight != nullptr;
+  // the layer's valid records: how many, the sum of their class weights, and whether an earlier one shares this cell
+  int cnt = 0;
+  double sw = 0.0;
+  bool earlier = false;
+  for (int u = lane; u < g.nt; u += YOLO_WAVE) {
+    const int32_t* q = rl + (long)u * kRecWords;
+    if (q[0]) {
+      ++cnt;
+      if (weighted) sw += (double)class_weight[q[5]];
+      earlier |= u < t && q[1] == b && q[2] == a && q[3] == gj && q[4] == gi;
+    }
+  }
+  if (__any(earlier)) return;                                                  // the lowest slot owns the cell
+#pragma unroll
+  for (int off = YOLO_WAVE / 2; off > 0; off >>= 1) {
+    cnt += __shfl_down(cnt, off);
+    sw += __shfl_down(sw, off);
+  }
+  const float nf = (float)__shfl(cnt, 0);
+  const float den = weighted ? (float)__shfl(sw, 0) : nf;                      // CrossEntropyLoss(weight=) divides by the weights' sum
+  const float G = grad_loss[0];
+  const float cxy = __fdiv_rn(G * gains.xy, nf), cwh = __fdiv_rn(G * gains.wh, nf);     // MSELoss: 2 d / (2 n), :146-147
+  const float ccls = __fdiv_rn(G * gains.cls, g.nc > 1 ? den : nf);
+  const int na = pick(g.na, l), ny = pick(g.ny, l), nx = pick(g.nx, l);
+  const int no = g.nc + 5;
+  const long cell = ((((long)b * na + a) * ny + gj) * nx + gi) * no;
+  const float* __restrict__ pi = pick(hd.p, l) + cell;
+  float* __restrict__ go = pick(gr.g, l) + cell;
+  float m = 0.f, sef = 1.f;
+  if (g.nc > 1) {                                                              // the softmax of the row, as loss_terms forms it
+    m = -INFINITY;
+    for (int c = lane; c < g.nc; c += YOLO_WAVE) m = fmaxf(m, pi[5 + c]);
+#pragma unroll
+    for (int off = YOLO_WAVE / 2; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    double se = 0.0;
+    for (int c = lane; c < g.nc; c += YOLO_WAVE) se += (double)expf(pi[5 + c] - m);
+#pragma unroll
+    for (int off = YOLO_WAVE / 2; off > 0; off >>= 1) se += __shfl_down(se, off);
+    sef = (float)__shfl(se, 0);
+  }
+  for (int w0 = 0; w0 < no; w0 += YOLO_WAVE) {
+    const int w = w0 + lane;
+    const bool live = w < no && w != 4;
+    const float x = live ? pi[w] : 0.f;
+    const float sg = sigmoid_f32(x);
+    const float dsg = sg * (1.f - sg);
+    const float sm = __fdiv_rn(expf(x - m), sef);
+    double acc = 0.0;
+    for (int u0 = 0; u0 < g.nt; u0 += YOLO_WAVE) {
+      const int u = u0 + lane;
+      bool same = false;
+      if (u < g.nt) {
+        const int32_t* q = rl + (long)u * kRecWords;
+        same = q[0] && q[1] == b && q[2] == a && q[3] == gj && q[4] == gi;
+      }
+      unsigned long long sharers = __ballot(same);
+      while (sharers) {                                                        // in slot order
+        const int32_t* q = rl + (long)(u0 + __ffsll(sharers) - 1) * kRecWords;
+        sharers &= sharers - 1;
+        if (live) {
+          float c;
+          if (w < 2) {
+            c = cxy * ((sg - __int_as_float(q[6 + w])) * dsg);
+          } else if (w < 4) {
+            c = cwh * (x - __int_as_float(q[6 + w]));
+          } else if (g.nc > 1) {
+            const float wc = weighted ? class_weight[q[5]] : 1.f;
+            c = ccls * (wc * (sm - (w - 5 == q[5] ? 1.f : 0.f)));
+          } else {
+            c = ccls * (sg - (float)q[5]);                                     // BCEWithLogits on the class INDEX, :152
+          }
+          acc += (double)c;
+        }
+      }
+    }
+    if (live) go[w] = (float)acc;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// argument checks shared by the entry points; fills g (anchors only when anchor_vec is given)
 int loss_geometry(const char* who, int nl, const int32_t* na, const int32_t* ny, const int32_t* nx, const float* anchor_vec, int bs,
                   int nc, int nt, Geom* g) {
   YOLO_REQUIRE(na && ny && nx, "%s: null geometry array", who);
@@ -394,4 +569,45 @@ extern "C" int yolo_loss_fwd(const float* const* p, const float* targets, int nt
   const Gains gn{gains[0], gains[1], gains[2], gains[3]};
   hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kThreads), 0, st, g, c.rec, c.partials, c.terms, gn, out, status);
   return yolo_check_launch("yolo_loss_fwd(finish)");
+}
+
+extern "C" int yolo_loss_bwd(const float* const* p, const float* targets, int nt, int nl, const int32_t* na, const int32_t* ny,
+                             const int32_t* nx, const float* anchor_vec, int bs, int nc, float iou_thresh, const float* gains,
+                             const float* class_weight, void* workspace, size_t workspace_bytes, const float* grad_loss,
+                             float* const* grad_p, yolo_stream_t s) {
+  YOLO_REQUIRE(p && workspace && anchor_vec && gains && (targets || nt == 0), "loss_bwd: null pointer");
+  YOLO_REQUIRE(grad_loss, "loss_bwd: null grad_loss");
+  YOLO_REQUIRE(grad_p, "loss_bwd: null grad_p");
+  Geom g;
+  if (int rc = loss_geometry("loss_bwd", nl, na, ny, nx, anchor_vec, bs, nc, nt, &g)) return rc;
+  Heads hd{};
+  Grads gr{};
+  GradGeom gg{};
+  const long no = nc + 5;
+  int wg = 0;
+  for (int l = 0; l < nl; ++l) {
+    YOLO_REQUIRE(p[l], "loss_bwd: null head tensor of layer %d", l);
+    YOLO_REQUIRE(grad_p[l], "loss_bwd: null gradient tensor of layer %d", l);
+    YOLO_REQUIRE(((uintptr_t)grad_p[l] & 15) == 0, "loss_bwd: the gradient tensor of layer %d is not 16-byte aligned", l);
+    hd.p[l] = p[l];
+    gr.g[l] = grad_p[l];
+    gg.wg_first[l] = wg;
+    wg += (int)((g.rows[l] * no + kGradChunk - 1) / kGradChunk);
+  }
+  for (int l = nl; l <= kMaxLayers; ++l) gg.wg_first[l] = wg;
+  gg.step_rows = (unsigned)(kGradStep / no);
+  gg.step_words = (unsigned)(kGradStep % no);
+  const Carved c = carve(workspace, g);
+  if (workspace_bytes < c.bytes) return yolo_set_error(YOLO_E_WORKSPACE, "loss_bwd: workspace %zu < %zu bytes", workspace_bytes, c.bytes);
+  hipStream_t st = (hipStream_t)s;
+  if (int rc = launch_targets(g, c, targets, iou_thresh, st)) return rc;
+  hipLaunchKernelGGL(loss_grad_dense_kernel, dim3((unsigned)wg), dim3(kThreads), 0, st, g, gg, hd, gr, c.tconf, gains[3], grad_loss);
+  if (int rc = yolo_check_launch("yolo_loss_bwd(dense)")) return rc;
+  if (nt > 0) {
+    const Gains gn{gains[0], gains[1], gains[2], gains[3]};
+    const unsigned blocks = (unsigned)(((long)nl * nt + kWaves - 1) / kWaves);
+    hipLaunchKernelGGL(loss_grad_cells_kernel, dim3(blocks), dim3(kThreads), 0, st, g, hd, gr, c.rec, class_weight, gn, grad_loss);
+    if (int rc = yolo_check_launch("yolo_loss_bwd(cells)")) return rc;
+  }
+  return 0;
 }

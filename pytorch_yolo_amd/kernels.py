@@ -14,7 +14,7 @@ from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU6, DT_BF16, DT_F16, DT_F32, Yo
                    check, load)
 
 __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pick", "stem", "resunit", "resunit_supported", "resunit_form", "maxpool", "spp", "dwconv3x3", "dwconv", "se", "se_workspace_bytes", "mbconv", "mbconv_supported", "mbconv_form", "pack_mbconv", "conv3x3_pool", "conv3x3_pool_supported", "conv2d_splitk", "conv2d_splitk_plan", "decode", "head_decode", "head_decode_supported",
-           "nms_merge", "nms_styled", "nms_styled_compact", "loss_workspace_bytes", "build_targets_fwd", "loss_fwd", "LOSS_REC_WORDS", "coco_workspace_bytes", "coco_match_fwd", "coco_accumulate_fwd", "coco_sweep_chunk", "coco_max_gt",
+           "nms_merge", "nms_styled", "nms_styled_compact", "loss_workspace_bytes", "build_targets_fwd", "loss_fwd", "loss_bwd", "LOSS_REC_WORDS", "coco_workspace_bytes", "coco_match_fwd", "coco_accumulate_fwd", "coco_sweep_chunk", "coco_max_gt",
            "COCO_T", "COCO_R", "COCO_A", "COCO_M", "pack_conv_weight", "roundup", "run_ops"]
 
 
@@ -550,19 +550,25 @@ def build_targets_fwd(targets, geom, anchor_vec, bs, nc, iou_thresh, workspace):
                                         _ptr(workspace), workspace.numel() * workspace.element_size(), stream_ptr()), "build_targets")
 
 
+def _loss_heads(p, geom, nc, class_weight, what="head"):
+    """Checks of the head tensors (or tensors of their shape) against ``geom``; returns the batch size."""
+    if len(geom) != len(p) or not p:
+        raise RuntimeError(f"loss: one geometry entry per {what} tensor")
+    bs = p[0].shape[0]
+    for t, (na_l, ny_l, nx_l) in zip(p, geom):
+        if tuple(t.shape) != (bs, na_l, ny_l, nx_l, nc + 5) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError(f"loss: {what} tensor {tuple(t.shape)} is not contiguous float32 [{bs}, {na_l}, {ny_l}, {nx_l}, {nc + 5}]")
+    if class_weight is not None and (class_weight.dtype != torch.float32 or class_weight.numel() != nc or not class_weight.is_contiguous()):
+        raise RuntimeError(f"loss: class_weight must be contiguous float32 [{nc}]")
+    return bs
+
+
 def loss_fwd(p, targets, geom, anchor_vec, nc, iou_thresh, gains, class_weight, workspace, out, status):
     """compute_loss forward (yolo_loss_fwd): ``p`` = the raw head tensors [bs, na, ny, nx, 5 + nc] (contiguous float32), ``gains`` =
     (k xy_loss, k wh_loss, k cls_loss, k conf_loss); writes out f32 [5] and status int32 [1 + nl]."""
     _need_cuda(targets, class_weight, workspace, out, status, *p)
     nt = _loss_targets(targets)
-    if len(geom) != len(p) or not p:
-        raise RuntimeError("loss: one geometry entry per head tensor")
-    bs = p[0].shape[0]
-    for t, (na_l, ny_l, nx_l) in zip(p, geom):
-        if tuple(t.shape) != (bs, na_l, ny_l, nx_l, nc + 5) or t.dtype != torch.float32 or not t.is_contiguous():
-            raise RuntimeError(f"loss: head tensor {tuple(t.shape)} is not contiguous float32 [{bs}, {na_l}, {ny_l}, {nx_l}, {nc + 5}]")
-    if class_weight is not None and (class_weight.dtype != torch.float32 or class_weight.numel() != nc or not class_weight.is_contiguous()):
-        raise RuntimeError(f"loss: class_weight must be contiguous float32 [{nc}]")
+    bs = _loss_heads(p, geom, nc, class_weight)
     if out.dtype != torch.float32 or out.numel() != 5 or status.dtype != torch.int32 or status.numel() != 1 + len(p) \
             or not out.is_contiguous() or not status.is_contiguous():
         raise RuntimeError("loss: out must be float32 [5] and status int32 [1 + layers]")
@@ -571,6 +577,25 @@ def loss_fwd(p, targets, geom, anchor_vec, nc, iou_thresh, gains, class_weight, 
     check(load().yolo_loss_fwd(ptrs, _ptr(targets) if nt else None, nt, nl, na, ny, nx, av, bs, int(nc), float(iou_thresh),
                                (C.c_float * 4)(*[float(v) for v in gains]), _ptr(class_weight), _ptr(workspace),
                                workspace.numel() * workspace.element_size(), _ptr(out), _ptr(status), stream_ptr()), "loss")
+
+
+def loss_bwd(p, targets, geom, anchor_vec, nc, iou_thresh, gains, class_weight, workspace, grad_loss, grad_p):
+    """Gradient of compute_loss with respect to ``p`` (yolo_loss_bwd): the arguments of loss_fwd, ``grad_loss`` = the upstream gradient
+    of the loss (device float32 [1], read on the device) and ``grad_p`` = one contiguous float32 tensor of the shape of p[l] per layer,
+    EVERY element of which is written.  ``workspace`` as for loss_fwd; nothing a forward call left in it is used."""
+    _need_cuda(targets, class_weight, workspace, grad_loss, *p, *grad_p)
+    nt = _loss_targets(targets)
+    bs = _loss_heads(p, geom, nc, class_weight)
+    if _loss_heads(grad_p, geom, nc, None, "gradient") != bs:
+        raise RuntimeError("loss: the gradient tensors must have the shapes of the head tensors")
+    if grad_loss.dtype != torch.float32 or grad_loss.numel() != 1:
+        raise RuntimeError("loss: grad_loss must be a float32 tensor of one element")
+    nl, na, ny, nx, av = _loss_geometry(geom, anchor_vec)
+    ptrs = (C.c_void_p * nl)(*[t.data_ptr() for t in p])
+    gptrs = (C.c_void_p * nl)(*[t.data_ptr() for t in grad_p])
+    check(load().yolo_loss_bwd(ptrs, _ptr(targets) if nt else None, nt, nl, na, ny, nx, av, bs, int(nc), float(iou_thresh),
+                               (C.c_float * 4)(*[float(v) for v in gains]), _ptr(class_weight), _ptr(workspace),
+                               workspace.numel() * workspace.element_size(), _ptr(grad_loss), gptrs, stream_ptr()), "loss_bwd")
 
 
 COCO_T, COCO_R, COCO_A, COCO_M = 10, 101, 4, 3      # fixed counts of csrc/coco_eval.hip: IoU thresholds, recall thresholds, area ranges, maxDets

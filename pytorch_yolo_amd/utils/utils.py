@@ -5,7 +5,8 @@
 reference's four styles (``nms_style=``: 'MERGE', which the reference hard-codes, 'OR', 'AND', 'SOFT').
 
 ``compute_loss`` and ``build_targets`` (utils.py:124-197) run the kernels of csrc/loss.hip on the raw head tensors of an eval-mode
-forward: the reference's validation loss, FORWARD VALUE ONLY (no gradient, no ``grad_fn``).  ``wh_iou``, ``bbox_iou`` and
+forward: the reference's loss, and - where some ``p[i]`` requires grad - its gradient with respect to ``p`` through autograd
+(``loss_grad_raw``); the chain ends at ``p``, nothing propagates through the convolutions.  ``wh_iou``, ``bbox_iou`` and
 ``xyxy2xywh`` are the reference's tensor helpers on whatever device their inputs live on.
 
 ``bench_results`` and ``test_model`` (utils.py:330-393) score a results list with the COCO bbox metrics on the device
@@ -351,38 +352,115 @@ def loss_raw(p, targets, model, class_weight=None, workspace=None, out=None, sta
     """Launch only (no host sync once the layers' geometry is cached): returns ``(out, status, workspace)`` device tensors - out
     float32 [5] = (lxy, lwh, lconf, lcls, loss), status int32 [1 + layers] = (targets outside the batch / grid / class range, kept
     targets per layer).  ``workspace`` / ``out`` / ``status`` let a caller pass static buffers (graph capture, guarded tests)."""
-    h = _hyper_params(model)
+    a = _loss_args(p, targets, model, class_weight)
+    return _loss_launch(a, workspace, out, status)
+
+
+def _as_head_tensors(p):
+    """The list ``p`` with every tensor float32 and contiguous (torch operations: differentiable where autograd is recording)."""
     p = list(p)
     if not p or not all(isinstance(t, torch.Tensor) for t in p):
         raise RuntimeError("compute_loss: p must be the list of raw head tensors that `io, p = model(x)` returns")
     if not all(t.is_cuda for t in p):
         raise RuntimeError("pytorch_yolo_amd.compute_loss runs on a ROCm device only (no CPU fallback)")
+    return [t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous() for t in p]
+
+
+def _loss_args(p, targets, model, class_weight):
+    """What a loss launch needs beside its buffers, read from the model once: a forward and its backward share one of these, so a
+    model whose layers move on to another grid in between changes nothing."""
+    h = _hyper_params(model)
+    p = [t.detach() for t in _as_head_tensors(p)]
     device = p[0].device
-    p = [t if (t.dtype == torch.float32 and t.is_contiguous()) else t.float().contiguous() for t in p]
     geom, vecs = _loss_geometry(model, [t.shape for t in p])
     targets = _device_targets(targets, device)
-    nc, bs, nt = int(model.n_class), p[0].shape[0], targets.shape[0]
+    bs = p[0].shape[0]
     if class_weight is not None:
         class_weight = torch.as_tensor(class_weight).to(device=device, dtype=torch.float32).contiguous()
     gains = [bs * h["xy_loss"], bs * h["wh_loss"], bs * h["cls_loss"], bs * h["conf_loss"]]       # k = bs, utils.py:135-136
+    return dict(p=p, targets=targets, geom=geom, vecs=vecs, nc=int(model.n_class), bs=bs, nt=targets.shape[0], device=device,
+                iou_thresh=h["iou_thresh"], gains=gains, class_weight=class_weight)
+
+
+def _loss_launch(a, workspace=None, out=None, status=None):
+    device = a["device"]
     with torch.cuda.device(device):
         if workspace is None:
-            workspace = _loss_workspace(device, geom, bs, nt)
+            workspace = _loss_workspace(device, a["geom"], a["bs"], a["nt"])
         if out is None:
             out = torch.empty((5,), dtype=torch.float32, device=device)
         if status is None:
-            status = torch.empty((1 + len(p),), dtype=torch.int32, device=device)
-        K.loss_fwd(p, targets, geom, vecs, nc, h["iou_thresh"], gains, class_weight, workspace, out, status)
+            status = torch.empty((1 + len(a["p"]),), dtype=torch.int32, device=device)
+        K.loss_fwd(a["p"], a["targets"], a["geom"], a["vecs"], a["nc"], a["iou_thresh"], a["gains"], a["class_weight"], workspace, out,
+                   status)
     return out, status, workspace
 
 
+def _loss_grad_launch(a, grad_loss=None, workspace=None, out=None):
+    device = a["device"]
+    with torch.cuda.device(device):
+        if workspace is None:
+            workspace = _loss_workspace(device, a["geom"], a["bs"], a["nt"])
+        if grad_loss is None:
+            grad_loss = torch.ones((1,), dtype=torch.float32, device=device)
+        else:
+            grad_loss = grad_loss.detach().to(device=device, dtype=torch.float32).reshape(1)
+        if out is None:
+            out = [torch.empty_like(t) for t in a["p"]]
+        K.loss_bwd(a["p"], a["targets"], a["geom"], a["vecs"], a["nc"], a["iou_thresh"], a["gains"], a["class_weight"], workspace,
+                   grad_loss, list(out))
+    return list(out)
+
+
+def loss_grad_raw(p, targets, model, class_weight=None, grad_loss=None, workspace=None, out=None):
+    """Launch only: the gradient of ``compute_loss(p, targets, model, class_weight)[0]`` with respect to every ``p[i]``, times
+    ``grad_loss`` (a float32 tensor of one element ON THE DEVICE, read there: no host sync; default 1.0).  Returns the list of gradient
+    tensors, float32 of the shapes of ``p``; EVERY element is written.  ``out`` (a list of contiguous float32 tensors of those shapes)
+    and ``workspace`` (``kernels.loss_workspace_bytes`` bytes) let a caller pass static buffers (graph capture, guarded tests).  The
+    call is self-contained: it runs the target assignment itself and uses nothing a forward call left in a workspace.  Targets outside
+    the batch / grid / class range are left out, as ``loss_raw`` leaves them out (and counts them in its status array)."""
+    return _loss_grad_launch(_loss_args(p, targets, model, class_weight), grad_loss, workspace, out)
+
+
+class _LossFunction(torch.autograd.Function):
+    """loss_raw with a backward: forward(a, *p) returns the five items (out[4] is the loss), backward hands the gradient of out[4] to
+    the gradient kernels.  ``p`` are the float32 contiguous head tensors that ``a`` (_loss_args) holds detached.  The gradient of
+    items 0-3 is NOT formed: compute_loss hands out only out[4:5] attached.  Once differentiable: a double backward raises."""
+
+    @staticmethod
+    def forward(ctx, a, *p):
+        ctx.loss_args = dict(a, p=None)
+        ctx.save_for_backward(*p)                               # (so that torch notices a p modified in place before the backward)
+        out, status, _ = _loss_launch(a)
+        ctx.mark_non_differentiable(status)
+        return out, status
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out, _grad_status):
+        a = dict(ctx.loss_args, p=[t.detach() for t in ctx.saved_tensors])
+        grads = _loss_grad_launch(a, grad_out.contiguous()[4:5])
+        return (None,) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[1:]))
+
+
 def compute_loss(p, targets, model, class_weight=None, check=True):
-    """Drop-in for reference ``compute_loss`` (utils.py:124-157), FORWARD VALUE ONLY: returns ``(loss, items)`` - ``loss`` float32 [1],
-    ``items`` float32 [5] = cat(lxy, lwh, lconf, lcls, loss) - on the device, WITHOUT ``grad_fn``: nothing here can be back-propagated.
+    """Drop-in for reference ``compute_loss`` (utils.py:124-157): returns ``(loss, items)`` - ``loss`` float32 [1], ``items`` float32 [5]
+    = cat(lxy, lwh, lconf, lcls, loss) - on the device.
+
+    WHAT IS DIFFERENTIABLE: ``loss`` with respect to ``p``, once.  Where autograd is recording (``torch.is_grad_enabled()``) and some
+    ``p[i].requires_grad``, ``loss`` carries a ``grad_fn`` and ``loss.backward()`` runs the gradient kernels of csrc/loss.hip
+    (``loss_grad_raw``): ``p[i].grad`` is what the reference's ``loss.backward()`` leaves there within 5e-6 of each word group's
+    largest element, bit-identical from run to run; a ``p[i]`` that does not require grad gets none.  The forward value has the same
+    bits either way; ``items`` is always detached (``:157``).  WHAT IS NOT: nothing propagates through this package's convolutions -
+    the ``p`` of ``io, p = model(x)`` has no ``grad_fn``, so the chain ends at ``p`` unless ``p`` comes from torch code of the caller's
+    (``p = [t.detach().requires_grad_() for t in p]``, heads computed in torch) -, a training-mode forward keeps raising, targets and
+    class weights get no gradient, and a double backward raises.  Otherwise (``torch.no_grad()``, or no ``p[i]`` requiring grad)
+    ``loss.grad_fn is None`` and nothing can be back-propagated.
 
     ``p`` is the list of raw head tensors [bs, na, ny, nx, 5 + nc] that ``io, p = model(x)`` returns in eval mode (in the reference the
     same tensors in training and eval mode), on the device (no CPU fallback); tensors that are not float32 or not contiguous are
-    converted.  ``targets`` [nt, 6] = image, class, x, y, w, h (normalised) may live on the host; ``nt == 0`` is legal.  ``model`` is
+    converted (by torch operations, which autograd differentiates: such a ``p[i]`` gets a gradient of its own dtype and layout).
+    ``targets`` [nt, 6] = image, class, x, y, w, h (normalised) may live on the host; ``nt == 0`` is legal.  ``model`` is
     read for ``hyper_params`` (keys iou_thresh, xy_loss, wh_loss, cls_loss, conf_loss: ``ValueError`` without them), ``n_class`` and,
     per YOLO layer, ``anchor_vec`` / ``n_grids`` / ``n_classes`` - which must describe ``p`` (``RuntimeError`` otherwise: run the
     forward at this input size first).  The reference's quirks are kept: k = bs, a duplicate cell is gathered once per target, and
@@ -394,12 +472,19 @@ def compute_loss(p, targets, model, class_weight=None, check=True):
         of the remaining targets (``loss_raw`` also returns the status array);
       * ties between anchors go to the first maximum (torch.max leaves the choice open);
       * the sums are float64 in a fixed order: the value is bit-identical from run to run, within 5e-6 relative of the reference's."""
-    out, status, _ = loss_raw(p, targets, model, class_weight)
+    p = list(p)
+    tracked = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in p)
+    if tracked:
+        _hyper_params(model)
+        p = _as_head_tensors(p)                                 # outside the Function: torch differentiates the conversions
+        out, status = _LossFunction.apply(_loss_args(p, targets, model, class_weight), *p)
+    else:
+        out, status, _ = loss_raw(p, targets, model, class_weight)
     if check:
         bad = int(status[0])
         if bad:
             raise RuntimeError("compute_loss: " + _out_of_range_message(bad))
-    return out[4:5], out
+    return out[4:5], (out.detach() if tracked else out)         # items detached, :157
 
 
 def _dict_from_results(data, targets, imgs_path, orig_shapes, cur_shape):
