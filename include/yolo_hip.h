@@ -422,7 +422,8 @@ YOLO_API int yolo_pack_input_nchw_f32_nhwc(const float* x, float* y, int n, int 
 YOLO_API int yolo_pack_conv_weight_f32_f32(const float* w_oihw, int cout, int cin_w, int ksize, int cin, int cout_pad, int kpad,
                                            float* out);
 
-/* ---- fp32 mode, the depthwise encoder families (csrc/efficient_f32.hip): float32 NHWC views in multiples of 4 channels, float32
+/* ---- fp32 mode, the depthwise encoder families (the float instances of csrc/efficient.hip and, for the shuffle,
+ *  csrc/pointwise.hip; yolo_maxpool_f32_fwd and yolo_pack_input_nchw_f32_nhwc above live in pointwise.hip too): float32 NHWC views in multiples of 4 channels, float32
  *  arithmetic, expf and an IEEE division in the activations, fmaf chains in a fixed order (no result depends on the grid).
  *  yolo_dwconv_f32_fwd: depthwise k x k conv (k = 3 or 5, stride 1 or 2) + bias + act (any YOLO_ACT_*) with an explicit leading pad
  *  and the caller's ho x wo, everything outside the image reads zero - arguments and geometry rule of yolo_dwconv_fwd.  One entry

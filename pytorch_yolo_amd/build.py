@@ -14,7 +14,8 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libyolo_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-# per-file extra flags: nms.hip must not contract a*b+c into fma (bit-exact IoU, see its header)
+# per-file extra flags: nms.hip must not contract a*b+c into fma (bit-exact IoU, see its header); efficient.hip holds the fp32
+# instances of the depthwise and squeeze-excite kernels
 SOURCES = {
     "runtime.hip": [],
     "conv_igemm.hip": [],
@@ -30,8 +31,7 @@ SOURCES = {
     "conv_f32.hip": ["-ffp-contract=off"],
     "conv1x1_stream.hip": [],
     "pointwise.hip": [],
-    "efficient.hip": [],
-    "efficient_f32.hip": ["-ffp-contract=off"],
+    "efficient.hip": ["-ffp-contract=off"],
     "preprocess.hip": ["-ffp-contract=off"],
     "nms.hip": ["-ffp-contract=off"],
     "loss.hip": ["-ffp-contract=off"],

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "../../include/yolo_hip.h"
 #include "tuning.h"
@@ -30,9 +31,9 @@ int yolo_set_error(int code, const char* fmt, ...);
     if (!(cond)) return yolo_set_error(YOLO_E_ARG, __VA_ARGS__);  \
   } while (0)
 
-static inline int yolo_check_launch(const char* what) {
+static inline int yolo_check_launch(const char* what, const char* stage = "") {
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return yolo_set_error((int)e, "%s: %s", what, hipGetErrorString(e));
+  if (e != hipSuccess) return yolo_set_error((int)e, "%s%s: %s", what, stage, hipGetErrorString(e));
   return 0;
 }
 
@@ -54,6 +55,44 @@ static inline int yolo_max_dyn_lds(const void* fn, int bytes, std::atomic<uint64
 
 // bf16 <-> f32 bit helpers (device).  Widening is exact; narrowing uses the hardware RNE cast.
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
+
+// fp32 -> IEEE half as the conv epilogues narrow (conv_common.h narrow<f16_t>): RNE, finite overflow clamps to +-65504
+__device__ __forceinline__ f16_t to_f16(float v) {
+  const float m = __builtin_fabsf(v);
+  if (m > 65504.f && m < __builtin_inff()) v = __builtin_copysignf(65504.f, v);
+  return (f16_t)v;
+}
+
+// ---- element kernels (efficient.hip, pointwise.hip): one template per op for bf16_t, f16_t and float ---------------------
+// A thread owns one 16-byte lane group of an NHWC view: V = 8 16-bit or 4 fp32 channels.  The arithmetic is fp32 whatever T is;
+// widening is exact, narrowing rounds to nearest even (IEEE half also clamps, see to_f16) and is the identity for float.
+template <typename T>
+struct Lanes {
+  static constexpr int V = 16 / (int)sizeof(T);
+  typedef T vec __attribute__((ext_vector_type(V)));
+  static __device__ __forceinline__ float widen(T v) { return (float)v; }
+  static __device__ __forceinline__ T narrow(float v) {
+    if constexpr (std::is_same<T, f16_t>::value) return to_f16(v);
+    else return (T)v;
+  }
+};
+
+__device__ __forceinline__ float act_f(float v, int act) {
+  if (act == YOLO_ACT_SWISH) return v / (1.f + expf(-v));          // x * sigmoid(x)
+  if (act == YOLO_ACT_LEAKY01) return fmaxf(v, 0.1f * v);
+  if (act == YOLO_ACT_RELU6) return fminf(fmaxf(v, 0.f), 6.f);
+  if (act == YOLO_ACT_RELU) return fmaxf(v, 0.f);
+  return v;
+}
+
+// their launches: 1-D grids of 256-thread blocks, one thread per lane group
+constexpr long kMaxThreads = 0x7fffffffL * 256;
+static inline unsigned blocks_for(long total) { return (unsigned)((total + 255) / 256); }
+
+// the channel view [offset, offset + c) of a buffer `total` channels wide starts and ends on lane groups of v channels
+static inline bool yolo_view_ok(int c, int total, int offset, int v) {
+  return total % v == 0 && offset % v == 0 && offset >= 0 && (long)offset + c <= total;
+}
 
 // One element of the YOLOLayer decode (reference models/yolo_layer.py:90-96): raw head value r of role k
 // (0,1 = x,y; 2,3 = w,h; 4 = objectness; 5.. = classes) at grid cell (gx, gy); anchor = anchor_px / stride for

@@ -7,8 +7,8 @@
 //
 // Replaces, like conv_igemm.hip: ConvBlock.forward (reference models/yolo_base.py:19-44, BN folded per
 // utils/torch_utils.py:33-60), plain nn.Conv2d heads (models/yolov3_tiny.py:38,42), Add (models/yolov3_spp.py:12-14),
-// Upsample (models/yolo_layer.py:6-13), the Concat placement (models/yolo_layer.py:16-22) and MaxPool
-// (models/yolo_base.py:60-66; the SPP pyramid models/yolov3_spp.py:75-77 is three pool launches into the concat buffer).
+// Upsample (models/yolo_layer.py:6-13) and the Concat placement (models/yolo_layer.py:16-22).  MaxPool and the input packing of
+// this mode are the float instances of pointwise.hip's templates.
 //
 // GEMM view: D[cout][pixel] = sum_k W[cout][k] X[k][pixel], k = (kh*ks + kw)*cin + c.  Block tile 128 pixels x 128 couts,
 // K step 32 floats, 4 waves of 64 x 64 (2 x 2 accumulators of 32 x 32).  Operands are staged global -> registers -> LDS
@@ -194,49 +194,6 @@ __global__ __launch_bounds__(256) void conv_f32_kernel(const ConvF32Args a) {
   }
 }
 
-// Generic max pool on fp32 NHWC views, -inf padding (nn.MaxPool2d semantics); one thread = 4 channels of one output pixel.
-__global__ __launch_bounds__(256) void maxpool_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int h, int w, int cg,
-                                                          int in_ct, int in_co, int ho, int wo, int out_ct, int out_co, int k,
-                                                          int stride, int pad, int dil, long total) {
-  const long t = (long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= total) return;
-  const int g = (int)(t % cg);
-  long p = t / cg;
-  const int ow = (int)(p % wo);
-  p /= wo;
-  const int oh = (int)(p % ho);
-  const long b = p / ho;
-  f32x4 m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  for (int i = 0; i < k; ++i) {
-    const int hi = oh * stride - pad + i * dil;
-    if ((unsigned)hi >= (unsigned)h) continue;
-    for (int j = 0; j < k; ++j) {
-      const int wi = ow * stride - pad + j * dil;
-      if ((unsigned)wi >= (unsigned)w) continue;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(x + ((b * h + hi) * w + wi) * in_ct + in_co + g * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], v[e]);
-    }
-  }
-  *reinterpret_cast<f32x4*>(y + ((b * ho + oh) * wo + ow) * out_ct + out_co + g * 4) = m;
-}
-
-// NCHW f32 -> NHWC f32, channels padded with zeros.
-__global__ __launch_bounds__(256) void pack_input_f32_kernel(const float* __restrict__ x, float* __restrict__ y, int c, long hw,
-                                                             long total_pix, int c_pad) {
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= total_pix) return;
-  const long b = p / hw, sp = p - b * hw;
-  const float* src = x + b * c * hw + sp;
-  float* dst = y + p * c_pad;
-  for (int c0 = 0; c0 < c_pad; c0 += 4) {
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (c0 + e < c) ? src[(long)(c0 + e) * hw] : 0.f;
-    *reinterpret_cast<f32x4*>(dst + c0) = o;
-  }
-}
-
 }  // namespace
 
 extern "C" int yolo_conv2d_f32_fwd(const float* x, const float* w_packed, const float* bias, const float* residual, float* y,
@@ -271,30 +228,6 @@ extern "C" int yolo_conv2d_f32_fwd(const float* x, const float* w_packed, const 
   YOLO_REQUIRE(grid <= 0x7fffffffL, "conv_f32: grid too large");
   hipLaunchKernelGGL(conv_f32_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)s, a);
   return yolo_check_launch("yolo_conv2d_f32_fwd");
-}
-
-extern "C" int yolo_maxpool_f32_fwd(const float* x, float* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho,
-                                    int wo, int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation,
-                                    yolo_stream_t s) {
-  YOLO_REQUIRE(x && y, "maxpool_f32: null pointer");
-  YOLO_REQUIRE(c > 0 && c % 4 == 0 && in_c_total % 4 == 0 && in_c_offset % 4 == 0 && out_c_total % 4 == 0 && out_c_offset % 4 == 0,
-               "maxpool_f32: channels / views must be multiples of 4");
-  YOLO_REQUIRE(in_c_offset + c <= in_c_total && out_c_offset + c <= out_c_total, "maxpool_f32: view out of range");
-  YOLO_REQUIRE(ksize >= 1 && stride >= 1 && dilation >= 1 && pad >= 0 && ho > 0 && wo > 0, "maxpool_f32: bad geometry");
-  YOLO_REQUIRE((ho - 1) * stride - pad < h && (wo - 1) * stride - pad < w, "maxpool_f32: an output window starts outside the input");
-  const long total = (long)n * ho * wo * (c / 4);
-  hipLaunchKernelGGL(maxpool_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)s, x, y, h, w, c / 4,
-                     in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, total);
-  return yolo_check_launch("yolo_maxpool_f32_fwd");
-}
-
-extern "C" int yolo_pack_input_nchw_f32_nhwc(const float* x, float* y, int n, int c, int h, int w, int c_pad, yolo_stream_t s) {
-  YOLO_REQUIRE(x && y && n > 0 && c > 0 && h > 0 && w > 0, "pack_input_f32: bad arguments");
-  YOLO_REQUIRE(c_pad >= c && c_pad % 4 == 0, "pack_input_f32: c_pad %d must be a multiple of 4 >= c", c_pad);
-  const long total = (long)n * h * w;
-  hipLaunchKernelGGL(pack_input_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)s, x, y, c, (long)h * w,
-                     total, c_pad);
-  return yolo_check_launch("yolo_pack_input_nchw_f32_nhwc");
 }
 
 // Host-side weight packer of the fp32 mode: OIHW f32 -> [cout_pad][kpad] f32, k = (kh*ks + kw)*cin + c, zero padded.

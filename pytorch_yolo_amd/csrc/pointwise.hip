@@ -1,81 +1,76 @@
 // HBM-bound element kernels of the path (gfx950): input packing, max pools / SPP pyramid,
-// depthwise 3x3, YOLO-layer decode.  All are coalesced 16-byte-per-lane streams over NHWC data.
+// depthwise 3x3, channel shuffle, YOLO-layer decode.  All are coalesced 16-byte-per-lane streams over NHWC data.  Packing, the
+// generic max pool and the shuffle are templates over the element (Lanes<T>, common.h): bf16, IEEE half (packing and pool) and
+// float, the element of model.precision = "fp32".
 #include "common.h"
-
-#include <type_traits>
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------
-// fp32 -> IEEE half as the conv epilogues narrow (conv_common.h narrow<f16_t>): RNE, finite overflow clamps to +-65504
-__device__ __forceinline__ f16_t to_f16(float v) {
-  const float m = __builtin_fabsf(v);
-  if (m > 65504.f && m < __builtin_inff()) v = __builtin_copysignf(65504.f, v);
-  return (f16_t)v;
-}
+// NCHW f32 -> NHWC bf16 / fp16 / f32 (T), channels padded with zeros (first-layer layout).
 template <typename T>
-__device__ __forceinline__ T to_elem(float v) {
-  if constexpr (std::is_same<T, f16_t>::value) return to_f16(v);
-  else return (T)v;
-}
-
-// NCHW f32 -> NHWC bf16 / fp16 (T), channels padded with zeros (first-layer layout).
-template <typename T, typename X8>
 __global__ __launch_bounds__(256) void pack_input_kernel(const float* __restrict__ x, T* __restrict__ y, int c,
                                                          long hw, long total_pix, int c_pad) {
+  typedef Lanes<T> L;
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
   if (p >= total_pix) return;
   const long b = p / hw, sp = p - b * hw;
   const float* src = x + b * c * hw + sp;
   T* dst = y + p * c_pad;
-  for (int c0 = 0; c0 < c_pad; c0 += 8) {
-    X8 o;
+  for (int c0 = 0; c0 < c_pad; c0 += L::V) {
+    typename L::vec o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = to_elem<T>((c0 + e < c) ? src[(long)(c0 + e) * hw] : 0.f);
-    *reinterpret_cast<X8*>(dst + c0) = o;
+    for (int e = 0; e < L::V; ++e) o[e] = L::narrow((c0 + e < c) ? src[(long)(c0 + e) * hw] : 0.f);
+    *reinterpret_cast<typename L::vec*>(dst + c0) = o;
   }
 }
 
 // ------------------------------------------------------------------------------------------------
-// bf16x8 lane-wise max (bf16 -> f32 widening is exact, so comparing as f32 and keeping the bits is exact)
-__device__ __forceinline__ void max8(float (&m)[8], const u32x4 v) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    m[2 * e] = fmaxf(m[2 * e], __uint_as_float(v[e] << 16));
-    m[2 * e + 1] = fmaxf(m[2 * e + 1], __uint_as_float(v[e] & 0xffff0000u));
-  }
-}
-__device__ __forceinline__ u32x4 pack8(const float (&m)[8]) {
-  u32x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = (__float_as_uint(m[2 * e]) >> 16) | (__float_as_uint(m[2 * e + 1]) & 0xffff0000u);
-  return o;
-}
-
-// ... and for IEEE half, which widens by a real convert (exact) and narrows back exactly: the maximum IS one of the inputs
+// The max pool's policies: the element, and how a lane group of it meets the running maxima and leaves them.
+// bf16 by bits (bf16 -> f32 widening is exact, so comparing as f32 and keeping the bits is exact) ...
 struct PoolBf16 {
-  static __device__ __forceinline__ void max8(float (&m)[8], const u32x4 v) { ::max8(m, v); }
-  static __device__ __forceinline__ u32x4 pack8(const float (&m)[8]) { return ::pack8(m); }
-};
-struct PoolF16 {
-  static __device__ __forceinline__ void max8(float (&m)[8], const u32x4 v) {
-    const f16x8 h = __builtin_bit_cast(f16x8, v);
+  typedef bf16_t elem;
+  static __device__ __forceinline__ void max(float (&m)[8], const u32x4 v) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], (float)h[e]);
+    for (int e = 0; e < 4; ++e) {
+      m[2 * e] = fmaxf(m[2 * e], __uint_as_float(v[e] << 16));
+      m[2 * e + 1] = fmaxf(m[2 * e + 1], __uint_as_float(v[e] & 0xffff0000u));
+    }
   }
-  static __device__ __forceinline__ u32x4 pack8(const float (&m)[8]) {
-    f16x8 h;
+  static __device__ __forceinline__ u32x4 pack(const float (&m)[8]) {
+    u32x4 o;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) h[e] = (f16_t)m[e];
+    for (int e = 0; e < 4; ++e) o[e] = (__float_as_uint(m[2 * e]) >> 16) | (__float_as_uint(m[2 * e + 1]) & 0xffff0000u);
+    return o;
+  }
+};
+// ... IEEE half by a real convert, which widens exactly and narrows back exactly (the maximum IS one of the inputs), and fp32,
+// where both are the identity
+template <typename T>
+struct PoolCvt {
+  typedef T elem;
+  typedef Lanes<T> L;
+  static __device__ __forceinline__ void max(float (&m)[L::V], const u32x4 v) {
+    const typename L::vec h = __builtin_bit_cast(typename L::vec, v);
+#pragma unroll
+    for (int e = 0; e < L::V; ++e) m[e] = fmaxf(m[e], (float)h[e]);
+  }
+  static __device__ __forceinline__ u32x4 pack(const float (&m)[L::V]) {
+    typename L::vec h;
+#pragma unroll
+    for (int e = 0; e < L::V; ++e) h[e] = (T)m[e];
     return __builtin_bit_cast(u32x4, h);
   }
 };
+typedef PoolCvt<f16_t> PoolF16;
+typedef PoolCvt<float> PoolF32;
 
-// Generic max pool, -inf padding (nn.MaxPool2d semantics), one thread = 8 channels of one output pixel.
+// Generic max pool, -inf padding (nn.MaxPool2d semantics), one thread = one lane group (cg per pixel) of one output pixel.
 template <typename P>
-__global__ __launch_bounds__(256) void maxpool_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int h, int w,
-                                                      int cg, int in_ct, int in_co, int ho, int wo, int out_ct, int out_co,
+__global__ __launch_bounds__(256) void maxpool_kernel(const typename P::elem* __restrict__ x, typename P::elem* __restrict__ y, int h,
+                                                      int w, int cg, int in_ct, int in_co, int ho, int wo, int out_ct, int out_co,
                                                       int k, int stride, int pad, int dil, long total) {
+  constexpr int V = Lanes<typename P::elem>::V;
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
   if (t >= total) return;
   const int g = (int)(t % cg);
@@ -84,19 +79,19 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const bf16_t* __restrict__
   p /= wo;
   const int oh = (int)(p % ho);
   const long b = p / ho;
-  float m[8];
+  float m[V];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) m[e] = -INFINITY;
+  for (int e = 0; e < V; ++e) m[e] = -INFINITY;
   for (int i = 0; i < k; ++i) {
     const int hi = oh * stride - pad + i * dil;
     if ((unsigned)hi >= (unsigned)h) continue;
     for (int j = 0; j < k; ++j) {
       const int wi = ow * stride - pad + j * dil;
       if ((unsigned)wi >= (unsigned)w) continue;
-      P::max8(m, *reinterpret_cast<const u32x4*>(x + ((b * h + hi) * w + wi) * in_ct + in_co + g * 8));
+      P::max(m, *reinterpret_cast<const u32x4*>(x + ((b * h + hi) * w + wi) * in_ct + in_co + g * V));
     }
   }
-  *reinterpret_cast<u32x4*>(y + ((b * ho + oh) * wo + ow) * out_ct + out_co + g * 8) = P::pack8(m);
+  *reinterpret_cast<u32x4*>(y + ((b * ho + oh) * wo + ow) * out_ct + out_co + g * V) = P::pack(m);
 }
 
 // SPP pyramid: one block = one image x 8 channels; the hxw plane lives in LDS; separable running max
@@ -203,7 +198,7 @@ __global__ __launch_bounds__(512) void spp_lines_kernel(bf16_t* __restrict__ buf
 }
 
 // ------------------------------------------------------------------------------------------------
-// Activation of both depthwise 3x3 forms: every YOLO_ACT_*, with the operations of efficient.hip's act_f (LeakyReLU as the select
+// Activation of both depthwise 3x3 forms: every YOLO_ACT_*, with the operations of common.h's act_f (LeakyReLU as the select
 // this file has always used: the same bits as fmaxf(v, 0.1f * v) on finite values).  `act` is a kernel argument, tested after the
 // last tap.  The stride-1 strip kernel sits at 168 registers, the most that leave three waves per SIMD: the selects stay a
 // sequence of conditional assignments (a chain of early returns compiles to 174), and swish - expf and a division, 174 as well -
@@ -302,91 +297,121 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a) {
   }
 }
 
-inline unsigned blocks_for(long total) { return (unsigned)((total + 255) / 256); }
+// channel_shuffle(cat(a, b), 2) in the two-slot layout (see include/yolo_hip.h): thread = one lane group of physical output
+// channels of a pixel; the pad channels of both slots are written as zero
+template <typename T>
+__global__ __launch_bounds__(256) void shuffle2_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ y, int half,
+                                                       int c_slot, int a_ct, int a_co, int b_ct, int b_co, int y_ct, int y_co,
+                                                       long total) {
+  typedef Lanes<T> L;
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int groups = 2 * c_slot / L::V;
+  const int g = (int)(t % groups);
+  const long pix = t / groups;
+  const T* const pa = a + pix * a_ct + a_co;
+  const T* const pb = b + pix * b_ct + b_co;
+  typename L::vec o;
+#pragma unroll
+  for (int e = 0; e < L::V; ++e) {
+    const int pc = g * L::V + e, slot = pc / c_slot, r = pc - slot * c_slot;
+    const int j = slot * half + r;                    // logical output channel (only read where r < half: j / 2 < half)
+    o[e] = r < half ? ((j & 1) ? pb[j >> 1] : pa[j >> 1]) : (T)0.f;
+  }
+  *reinterpret_cast<typename L::vec*>(y + pix * y_ct + y_co + g * L::V) = o;
+}
 
 }  // namespace
 
-extern "C" int yolo_pack_input_nchw_f32(const float* x, void* y, int n, int c, int h, int w, int c_pad, yolo_stream_t s) {
-  YOLO_REQUIRE(x && y && n > 0 && c > 0 && h > 0 && w > 0, "pack_input: bad arguments");
-  YOLO_REQUIRE(c_pad % 8 == 0 && c_pad >= c, "pack_input: c_pad %d must be a multiple of 8 and >= c %d", c_pad, c);
+// The host side of packing, pool and shuffle for every element type; fn = the entry point's name.  The 16-bit pointers travel as
+// bytes: bf16 and IEEE half have the same size and alignment.
+template <typename T>
+static int pack_input(const char* fn, const float* x, void* y, int n, int c, int h, int w, int c_pad, yolo_stream_t s) {
+  constexpr int V = Lanes<T>::V;
+  YOLO_REQUIRE(x && y && n > 0 && c > 0 && h > 0 && w > 0, "%s: bad arguments", fn);
+  YOLO_REQUIRE(c_pad % V == 0 && c_pad >= c, "%s: c_pad %d must be a multiple of %d and >= c %d", fn, c_pad, V, c);
   const long total = (long)n * h * w;
-  hipLaunchKernelGGL((pack_input_kernel<bf16_t, bf16x8>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, x, (bf16_t*)y, c,
-                     (long)h * w, total, c_pad);
-  return yolo_check_launch("yolo_pack_input_nchw_f32");
+  YOLO_REQUIRE(total <= kMaxThreads, "%s: grid too large", fn);
+  hipLaunchKernelGGL(pack_input_kernel<T>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, x, (T*)y, c, (long)h * w, total,
+                     c_pad);
+  return yolo_check_launch(fn);
 }
 
+extern "C" int yolo_pack_input_nchw_f32(const float* x, void* y, int n, int c, int h, int w, int c_pad, yolo_stream_t s) {
+  return pack_input<bf16_t>("yolo_pack_input_nchw_f32", x, y, n, c, h, w, c_pad, s);
+}
 extern "C" int yolo_pack_input_nchw_f32_f16(const float* x, void* y, int n, int c, int h, int w, int c_pad, yolo_stream_t s) {
-  YOLO_REQUIRE(x && y && n > 0 && c > 0 && h > 0 && w > 0, "pack_input_f16: bad arguments");
-  YOLO_REQUIRE(c_pad % 8 == 0 && c_pad >= c, "pack_input_f16: c_pad %d must be a multiple of 8 and >= c %d", c_pad, c);
-  const long total = (long)n * h * w;
-  hipLaunchKernelGGL((pack_input_kernel<f16_t, f16x8>), dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, x, (f16_t*)y, c,
-                     (long)h * w, total, c_pad);
-  return yolo_check_launch("yolo_pack_input_nchw_f32_f16");
+  return pack_input<f16_t>("yolo_pack_input_nchw_f32_f16", x, y, n, c, h, w, c_pad, s);
+}
+extern "C" int yolo_pack_input_nchw_f32_nhwc(const float* x, float* y, int n, int c, int h, int w, int c_pad, yolo_stream_t s) {
+  return pack_input<float>("yolo_pack_input_nchw_f32_nhwc", x, y, n, c, h, w, c_pad, s);
 }
 
 template <typename P>
-static int maxpool16(const void* x, void* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho, int wo,
-                     int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation, yolo_stream_t s) {
-  YOLO_REQUIRE(x && y && n > 0 && c > 0 && c % 8 == 0, "maxpool: bad arguments (c %d must be a multiple of 8)", c);
-  YOLO_REQUIRE(in_c_total % 8 == 0 && in_c_offset % 8 == 0 && out_c_total % 8 == 0 && out_c_offset % 8 == 0,
-               "maxpool: views must be 8-channel aligned");
-  YOLO_REQUIRE(ksize >= 1 && stride >= 1 && dilation >= 1 && pad >= 0, "maxpool: bad geometry");
+static int maxpool(const char* fn, const void* x, void* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho, int wo,
+                   int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation, yolo_stream_t s) {
+  typedef typename P::elem T;
+  constexpr int V = Lanes<T>::V;
+  YOLO_REQUIRE(x && y && n > 0 && h > 0 && w > 0 && c > 0, "%s: bad arguments", fn);
+  YOLO_REQUIRE(c % V == 0 && yolo_view_ok(c, in_c_total, in_c_offset, V) && yolo_view_ok(c, out_c_total, out_c_offset, V),
+               "%s: bad arguments: c %d must be a multiple of %d, views aligned to multiples of %d channels and inside their buffers", fn, c,
+               V, V);
+  YOLO_REQUIRE(ksize >= 1 && stride >= 1 && dilation >= 1 && pad >= 0 && ho > 0 && wo > 0, "%s: bad geometry", fn);
   // floor mode, or torch's ceil_mode (one more row / column whose window still starts inside the input or its left
   // padding; the taps beyond the input count as -inf like the padding does)
   const int hf = (h + 2 * pad - dilation * (ksize - 1) - 1) / stride + 1, wf = (w + 2 * pad - dilation * (ksize - 1) - 1) / stride + 1;
   YOLO_REQUIRE((ho == hf || (ho == hf + 1 && (ho - 1) * stride < h + pad)) && (wo == wf || (wo == wf + 1 && (wo - 1) * stride < w + pad)),
-               "maxpool: output %dx%d inconsistent with %dx%d k%d s%d p%d d%d", ho, wo, h, w, ksize, stride, pad, dilation);
-  const long total = (long)n * ho * wo * (c / 8);
-  hipLaunchKernelGGL(maxpool_kernel<P>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (bf16_t*)y, h,
-                     w, c / 8, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, total);
-  return yolo_check_launch("yolo_maxpool_fwd");
+               "%s: output %dx%d inconsistent with %dx%d k%d s%d p%d d%d", fn, ho, wo, h, w, ksize, stride, pad, dilation);
+  const long total = (long)n * ho * wo * (c / V);
+  YOLO_REQUIRE(total <= kMaxThreads, "%s: grid too large", fn);
+  hipLaunchKernelGGL(maxpool_kernel<P>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const T*)x, (T*)y, h, w, c / V,
+                     in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, total);
+  return yolo_check_launch(fn);
 }
 
 extern "C" int yolo_maxpool_fwd(const void* x, void* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho,
                                 int wo, int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation,
                                 yolo_stream_t s) {
-  return maxpool16<PoolBf16>(x, y, n, h, w, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, s);
+  return maxpool<PoolBf16>("yolo_maxpool_fwd", x, y, n, h, w, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, s);
 }
-// IEEE-half NHWC views (the 16-bit pointers are passed as bytes: same size and alignment)
 extern "C" int yolo_maxpool_f16_fwd(const void* x, void* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho,
                                     int wo, int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation,
                                     yolo_stream_t s) {
-  return maxpool16<PoolF16>(x, y, n, h, w, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, s);
+  return maxpool<PoolF16>("yolo_maxpool_f16_fwd", x, y, n, h, w, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, s);
+}
+extern "C" int yolo_maxpool_f32_fwd(const float* x, float* y, int n, int h, int w, int c, int in_c_total, int in_c_offset, int ho,
+                                    int wo, int out_c_total, int out_c_offset, int ksize, int stride, int pad, int dilation,
+                                    yolo_stream_t s) {
+  return maxpool<PoolF32>("yolo_maxpool_f32_fwd", x, y, n, h, w, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, ksize, stride, pad, dilation, s);
 }
 
-// channel_shuffle(cat(a, b), 2) in the two-slot layout (see include/yolo_hip.h): thread = 8 physical output channels of a pixel
-__global__ __launch_bounds__(256) void shuffle2_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b,
-                                                       bf16_t* __restrict__ y, int half, int c_slot, int a_ct, int a_co, int b_ct,
-                                                       int b_co, int y_ct, int y_co, long total) {
-  const long t = (long)blockIdx.x * 256 + threadIdx.x;
-  if (t >= total) return;
-  const int groups = 2 * c_slot / 8;
-  const int g = (int)(t % groups);
-  const long pix = t / groups;
-  const bf16_t* const pa = a + pix * a_ct + a_co;
-  const bf16_t* const pb = b + pix * b_ct + b_co;
-  bf16x8 o;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int pc = g * 8 + e, slot = pc / c_slot, r = pc - slot * c_slot;
-    const int j = slot * half + r;                    // logical output channel
-    o[e] = r < half ? ((j & 1) ? pb[j >> 1] : pa[j >> 1]) : (bf16_t)0.f;
-  }
-  *reinterpret_cast<bf16x8*>(y + pix * y_ct + y_co + g * 8) = o;
+template <typename T>
+static int channel_shuffle2(const char* fn, const void* a, const void* b, void* y, int n, int h, int w, int half, int c_slot,
+                            int a_c_total, int a_c_offset, int b_c_total, int b_c_offset, int y_c_total, int y_c_offset,
+                            yolo_stream_t s) {
+  constexpr int V = Lanes<T>::V;
+  YOLO_REQUIRE(a && b && y && n > 0 && h > 0 && w > 0, "%s: bad arguments", fn);
+  YOLO_REQUIRE(half >= 1 && half <= c_slot && c_slot % V == 0, "%s: %d logical channels per slot of %d", fn, half, c_slot);
+  // a and b are read one channel at a time: only y's view has to start and end on lane groups
+  YOLO_REQUIRE(yolo_view_ok(c_slot, a_c_total, a_c_offset, 1) && yolo_view_ok(c_slot, b_c_total, b_c_offset, 1) &&
+                   yolo_view_ok(2 * c_slot, y_c_total, y_c_offset, V),
+               "%s: bad views", fn);
+  const long total = (long)n * h * w * (2 * c_slot / V);
+  YOLO_REQUIRE(total <= kMaxThreads, "%s: grid too large", fn);
+  hipLaunchKernelGGL(shuffle2_kernel<T>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const T*)a, (const T*)b, (T*)y, half,
+                     c_slot, a_c_total, a_c_offset, b_c_total, b_c_offset, y_c_total, y_c_offset, total);
+  return yolo_check_launch(fn);
 }
 
 extern "C" int yolo_channel_shuffle2_fwd(const void* a, const void* b, void* y, int n, int h, int w, int half, int c_slot,
                                          int a_c_total, int a_c_offset, int b_c_total, int b_c_offset, int y_c_total,
                                          int y_c_offset, yolo_stream_t s) {
-  YOLO_REQUIRE(a && b && y && n > 0 && h > 0 && w > 0, "shuffle2: bad arguments");
-  YOLO_REQUIRE(half >= 1 && half <= c_slot && c_slot % 8 == 0, "shuffle2: %d logical channels per slot of %d", half, c_slot);
-  YOLO_REQUIRE(a_c_offset + c_slot <= a_c_total && b_c_offset + c_slot <= b_c_total && y_c_offset + 2 * c_slot <= y_c_total &&
-                   y_c_offset % 8 == 0 && y_c_total % 8 == 0,
-               "shuffle2: bad views");
-  const long total = (long)n * h * w * (2 * c_slot / 8);
-  hipLaunchKernelGGL(shuffle2_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)a, (const bf16_t*)b,
-                     (bf16_t*)y, half, c_slot, a_c_total, a_c_offset, b_c_total, b_c_offset, y_c_total, y_c_offset, total);
-  return yolo_check_launch("yolo_channel_shuffle2_fwd");
+  return channel_shuffle2<bf16_t>("yolo_channel_shuffle2_fwd", a, b, y, n, h, w, half, c_slot, a_c_total, a_c_offset, b_c_total, b_c_offset, y_c_total, y_c_offset, s);
+}
+extern "C" int yolo_channel_shuffle2_f32_fwd(const float* a, const float* b, float* y, int n, int h, int w, int half, int c_slot,
+                                             int a_c_total, int a_c_offset, int b_c_total, int b_c_offset, int y_c_total,
+                                             int y_c_offset, yolo_stream_t s) {
+  return channel_shuffle2<float>("yolo_channel_shuffle2_f32_fwd", a, b, y, n, h, w, half, c_slot, a_c_total, a_c_offset, b_c_total, b_c_offset, y_c_total, y_c_offset, s);
 }
 
 extern "C" int yolo_spp_fwd(void* buf, int n, int h, int w, int c, yolo_stream_t s) {

@@ -305,7 +305,7 @@ def dw3_shape(nchw, stride, act):
     return tuple(nchw) + (3, stride, act)
 
 
-# yolo_dwconv_fwd (efficient.hip) and yolo_dwconv_f32_fwd (efficient_f32.hip): k {3, 5} x stride {1, 2} on 6x8, 7x9 and 1x1 maps of two
+# yolo_dwconv_fwd and yolo_dwconv_f32_fwd (efficient.hip, dwconv_kernel<bf16_t> and <float>): k {3, 5} x stride {1, 2} on 6x8, 7x9 and 1x1 maps of two
 # images, in TensorFlow-"same" geometry and with torch's pad k // 2 where that is another one (an even map at stride 2: leading pad
 # k // 2 - 1 against k // 2); c = 8 and 24 (bf16) / 12 (float32).  (k, stride, h, w, geometry)
 def _dw_geometries():

@@ -92,8 +92,9 @@ def test_fp16_still_refuses_and_names_fp32(family):
 
 
 def test_new_entry_points_check_their_arguments():
-    """Every YOLO_REQUIRE of the three entry points and the relaxed output-size rule of yolo_conv2d_f32_fwd return YOLO_E_ARG before
-    anything is launched (the pointers are host memory: nothing may dereference them)."""
+    """Every YOLO_REQUIRE of the three entry points, the checks their 16-bit siblings and the three max pools share with them, and
+    the relaxed output-size rule of yolo_conv2d_f32_fwd return YOLO_E_ARG before anything is launched (the pointers are host memory:
+    nothing may dereference them)."""
     lib = _lib.load()
     buf = ctypes.create_string_buffer(64)
     p = ctypes.cast(buf, ctypes.c_void_p)
@@ -121,6 +122,19 @@ def test_new_entry_points_check_their_arguments():
     assert sh(1, 4, 4, 6, 6, 6, 0, 6, 0, 12, 0) == -1 and b"logical channels" in err()                 # slot % 4
     assert sh(1, 4, 4, 6, 8, 8, 0, 8, 0, 12, 0) == -1 and b"bad views" in err()                        # y too narrow
     assert sh(1, 4, 4, 6, 8, 8, 4, 8, 0, 16, 0) == -1 and b"bad views" in err()                        # a past its buffer
+    # every precision of an op goes through one validator: what only the fp32 (or only the 16-bit) entry point used to check
+    # max pool: (n, h, w, c, in_ct, in_co, ho, wo, out_ct, out_co, k, stride, pad, dilation)
+    for pool, lanes in ((lib.yolo_maxpool_fwd, 8), (lib.yolo_maxpool_f16_fwd, 8), (lib.yolo_maxpool_f32_fwd, 4)):
+        mp = lambda *a: pool(p, p, *a, None)
+        text = b"multiple of 8" if lanes == 8 else b"multiples of 4"
+        assert mp(1, 8, 8, 16, 16, lanes, 4, 4, 16, 0, 2, 2, 0, 1) == -1 and text in err()             # input view past its buffer
+        assert mp(1, 8, 8, 16, 16, 0, 4, 4, 16, lanes, 2, 2, 0, 1) == -1 and text in err()             # output view past its buffer
+        assert mp(1, 8, 8, 16, 16, -lanes, 4, 4, 32, 0, 2, 2, 0, 1) == -1 and text in err()            # negative offset
+        assert mp(1, 7, 7, 16, 16, 0, 5, 4, 16, 0, 2, 2, 0, 1) == -1 and b"inconsistent" in err()      # ceil mode allows 4 rows, not 5
+        assert mp(1, 8, 8, 16, 16, 0, 5, 4, 16, 0, 2, 2, 0, 1) == -1 and b"inconsistent" in err()      # row 4 would start at 8 >= h
+    dw16 = lambda *a: lib.yolo_dwconv_fwd(p, p, p, p, *a, None)
+    assert dw16(1, 8, 8, 16, 16, 0, 8, 8, 16, 0, 3, 1, 1, 9) == -1 and b"activation" in err()
+    assert dw16(1, 8, 8, 16, 16, -8, 8, 8, 16, 0, 3, 1, 1, 0) == -1 and b"aligned" in err()            # negative offset
     # conv_f32: one row / column beyond the symmetric-pad size is accepted only while its window starts inside the image
     def desc(h, k, stride, pad, extra):
         d = K.conv_desc(n=1, h=h, w=h, cin=8, in_c_total=8, in_c_offset=0, cout=8, out_c_total=8, out_c_offset=0, ksize=k, stride=stride,

@@ -1,4 +1,5 @@
-"""fp32 reference-precision mode of the depthwise encoder families (csrc/efficient_f32.hip; MobileNetV2, ShuffleNetV2,
+"""fp32 reference-precision mode of the depthwise encoder families (the float instances of csrc/efficient.hip and
+csrc/pointwise.hip; MobileNetV2, ShuffleNetV2,
 EfficientNet-B0 and - no new kernel, never driven before - SqueezeNet): kernels against torch fp32 on the CPU on the SAME fp32
 operands, models against the fp32 oracle forwards, kept-index sets against the oracle NMS.
 
