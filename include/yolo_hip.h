@@ -48,8 +48,10 @@ YOLO_API const char* yolo_last_error(void);
  * YoloPipeStep / yolo_pipeline_step / yolo_event_* / yolo_pack_detections / yolo_nms_merge_compact were added. */
 YOLO_API int yolo_abi_version(void);
 /* Tuning / A-B hook (process-wide, not part of the numerics contract): overrides what the environment variables
- * YOLO_CONV_VARIANT (knob 0), YOLO_CONV_DEBUG (knob 1), YOLO_CONV_PP (knob 2), YOLO_RESUNIT_DEBUG (knob 3) and YOLO_MBCONV_DEBUG (knob 4) set at load time.
- * Returns the old value.  pytorch_yolo_amd/csrc/tuning.h names every bit of every knob. */
+ * YOLO_CONV_VARIANT (knob 0), YOLO_CONV_DEBUG (knob 1), YOLO_CONV_PP (knob 2), YOLO_RESUNIT_DEBUG (knob 3), YOLO_MBCONV_DEBUG (knob 4),
+ * YOLO_STEM_DEBUG (knob 5), YOLO_STEM_ONE_ROLE (knob 6), YOLO_MBWIDE_DEBUG (knob 7), YOLO_MBWIDE_FORM (knob 8), YOLO_DWCONV_DEBUG
+ * (knob 9), YOLO_SPP_NO_LINES (knob 10) and YOLO_RESUNIT_STAGGER (knob 11) set at the first use.  Returns the old value; any other
+ * knob is YOLO_E_ARG.  pytorch_yolo_amd/csrc/tuning.h is the table of the knobs and names every bit of them. */
 YOLO_API int yolo_set_tuning(int knob, int value);
 
 /* ---- input packing: the `imgs.to(device)` + first-layer layout step (utils/utils.py:374) -----
@@ -189,6 +191,10 @@ YOLO_API int yolo_resunit_supported(int c, int h, int w);
  *  (slower than the two-launch path above C = 64: a planner should not fuse there), 2 the persistent 64-channel kernel, 3 the
  *  20-pixel-wide tile kernels (conv_resunit_t20.hip).  No launch, works without a GPU. */
 YOLO_API int yolo_resunit_form(int c, int n, int h, int w);
+/** The kernel + grid yolo_resunit_fwd would launch for d (the unit's 3x3) under the current tuning, in the style of yolo_conv2d_pick:
+ *  "resunit64_t20<...> grid N", "resunit_t20w<C 128, ...> grid N", "resunit64<..., persistent> grid N" or "resunit<C 128, ...> grid N".
+ *  Runs the checks of yolo_resunit_fwd that need no pointer; no launch, works without a GPU. */
+YOLO_API int yolo_resunit_pick(const YoloConvDesc* d, int has_preadd, char* out, int out_len);
 YOLO_API int yolo_resunit_fwd(const void* x, const void* w1_packed, const float* b1, const void* w2_packed,
                               const float* b2, void* y, void* y_preadd, const YoloConvDesc* d, int kpad1,
                               int cout_pad1, yolo_stream_t s);
@@ -199,6 +205,10 @@ YOLO_API int yolo_resunit_fwd(const void* x, const void* w1_packed, const float*
  *  largest activation of the network) stays in LDS.  d describes the stride-2 conv (h,w = input size,
  *  cin 32, cout 64, kpad = packing of W2); W1 is packed as for yolo_conv1_nchw_f32_fwd (cin = 8, kpad1 >= 80). */
 YOLO_API int yolo_stem_supported(int cin_real, int c1, int c2, int h, int w);
+/** The kernel + grid yolo_stem_fwd would launch under the current tuning: "stem2<leaky,8x16 outputs> grid N" (3 input channels) or
+ *  "stem<leaky,CIN 0,16x16 outputs> grid N" (CIN 3: three channels under knob 6 or beyond 32-bit offsets).  Runs the checks of
+ *  yolo_stem_fwd that need no pointer; no launch, works without a GPU. */
+YOLO_API int yolo_stem_pick(int cin_real, const YoloConvDesc* d, char* out, int out_len);
 YOLO_API int yolo_stem_fwd(const float* x_nchw, int cin_real, const void* w1_packed, const float* b1, int kpad1,
                            const void* w2_packed, const float* b2, void* y, const YoloConvDesc* d, yolo_stream_t s);
 
@@ -223,6 +233,11 @@ typedef struct YoloMbconvDesc {
 } YoloMbconvDesc;
 YOLO_API int yolo_mbconv_dstride(int ce);
 YOLO_API int yolo_mbconv_supported(int cin, int hidden, int cout, int stride);
+/** The kernel + grid yolo_mbconv_fwd would launch under the current tuning: "mbconv<S 1,8x8,expand,512 threads> grid N" (tile form),
+ *  "mbstrip<S 1,expand,8 rows x 26> grid N" (knob 4 bit kMbStripForm, where the strip form can hold the block) or
+ *  "mbwide<S 1,13x13,512 threads,MC 4> grid N".  Runs the checks of yolo_mbconv_fwd that need no pointer; no launch, works without
+ *  a GPU. */
+YOLO_API int yolo_mbconv_pick(const YoloMbconvDesc* d, char* out, int out_len);
 YOLO_API int yolo_mbconv_fwd(const void* x, const void* w_exp, const float* b_exp, const float* w_dw, const float* b_dw,
                              const void* w_proj, const float* b_proj, void* y, const YoloMbconvDesc* d, yolo_stream_t s);
 

@@ -80,15 +80,18 @@ SIGNATURES = {
     "yolo_conv2d_pick": (C.c_int, [C.POINTER(YoloConvDesc), C.c_int, C.c_int, C.c_char_p, C.c_int]),
     "yolo_pack_conv_weight_f32": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "yolo_stem_supported": (C.c_int, [C.c_int] * 5),
+    "yolo_stem_pick": (C.c_int, [C.c_int, C.POINTER(YoloConvDesc), C.c_char_p, C.c_int]),
     "yolo_stem_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                 C.POINTER(YoloConvDesc), C.c_void_p]),
     "yolo_resunit_supported": (C.c_int, [C.c_int] * 3),
     "yolo_resunit_form": (C.c_int, [C.c_int] * 4),
+    "yolo_resunit_pick": (C.c_int, [C.POINTER(YoloConvDesc), C.c_int, C.c_char_p, C.c_int]),
     "yolo_resunit_fwd": (C.c_int, [C.c_void_p] * 7 + [C.POINTER(YoloConvDesc), C.c_int, C.c_int, C.c_void_p]),
     "yolo_conv3x3_pool_supported": (C.c_int, [C.c_int] * 2),
     "yolo_conv3x3_pool_fwd": (C.c_int, [C.c_void_p] * 4 + [C.POINTER(YoloConvDesc), C.c_int, C.c_void_p]),
     "yolo_mbconv_dstride": (C.c_int, [C.c_int]),
     "yolo_mbconv_supported": (C.c_int, [C.c_int] * 4),
+    "yolo_mbconv_pick": (C.c_int, [C.POINTER(YoloMbconvDesc), C.c_char_p, C.c_int]),
     "yolo_mbconv_fwd": (C.c_int, [C.c_void_p] * 8 + [C.POINTER(YoloMbconvDesc), C.c_void_p]),
     "yolo_dwconv3x3_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 12 + [C.c_void_p]),
     "yolo_dwconv_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 14 + [C.c_void_p]),

@@ -25,6 +25,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 #define YOLO_WAVE 64
 
 int yolo_set_error(int code, const char* fmt, ...);
+int yolo_device_cus();   // CU count of the device that is current at the first call, 256 if unknown (the persistent kernels' grids)
 
 #define YOLO_REQUIRE(cond, ...)                                   \
   do {                                                            \
@@ -115,6 +116,18 @@ __device__ __forceinline__ float yolo_decode_elem(float r, int k, int gx, int gy
   if (nc == 1 && k == 5) v = 1.f;                                     // :95-96
   return v;
 }
+
+// The answer of choose_mbconv (conv_mbconv.hip; the wide forms' part is choose_mbwide, conv_mbwide.hip): which kernel a fused MBConv
+// block takes, and its launch shape
+enum class MbForm { kTile, kStrip, kWide };   // mbconv_kernel, mbstrip_kernel, mbwide_kernel
+struct MbconvPick {
+  MbForm form;
+  int th, tw;           // output tile (strip form: rows of a band x columns of a segment)
+  int mc;               // wide form: cout tiles per wave
+  int threads, grid;
+  size_t lds;           // dynamic LDS bytes
+  int tiles_x, tiles_y, n_tiles;
+};
 
 // per-op launch entry points shared with the batched launcher
 int yolo_conv2d_launch(const void* x, const void* w, const float* bias, const void* res, void* y, void* y_aux,

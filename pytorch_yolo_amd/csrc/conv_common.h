@@ -365,11 +365,12 @@ __device__ __forceinline__ int xcd_swizzle(int bid, int nblk) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
-// yolo_conv2d_pick (the tile-rule regression guard): while pick_buffer() is non-null the launch functions write the name of the
-// kernel instance they would launch there and return 0 WITHOUT launching (no GPU needed).
-bool resunit_t20_applies(int c, int n, int h, int w);   // conv_resunit_t20.hip: the shipped rule of the 20-pixel-wide tile kernels
-int launch_resunit_t20(const ConvArgs& c, const bf16_t* w1, const float* b1, int kpad1, uint32_t w1_bytes, bool force, hipStream_t s);
+// conv_resunit_t20.hip: the 20-pixel-wide tile kernels of the fused residual units, in the form choose_resunit (conv_resunit.hip) named
+int launch_resunit_t20(const ConvArgs& c, const bf16_t* w1, const float* b1, int kpad1, uint32_t w1_bytes, int stagger, dim3 grid, size_t lds,
+                       hipStream_t s);
 int launch_cus();                  // compute units the coming launches may use (256, or a CU-masked stream's share)
+// yolo_conv2d_pick (the tile-rule regression guard): while pick_buffer() is non-null the launch functions of yolo_conv2d_fwd write
+// the name of the kernel instance they would launch there and return 0 WITHOUT launching (no GPU needed).
 char* pick_buffer();
 bool pick_only(const char* fmt, ...);   // true (and the name recorded) in pick mode
 

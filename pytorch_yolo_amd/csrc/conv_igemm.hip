@@ -592,13 +592,17 @@ static int env_int(const char* name, int unset) {
 }
 Tuning& tuning() {   // the environment at first use, yolo_set_tuning afterwards
   static Tuning t{env_int("YOLO_CONV_VARIANT", -1), env_int("YOLO_CONV_DEBUG", 0), env_int("YOLO_CONV_PP", 0),
-                  env_int("YOLO_RESUNIT_DEBUG", 0), env_int("YOLO_MBCONV_DEBUG", 0)};
+                  env_int("YOLO_RESUNIT_DEBUG", 0), env_int("YOLO_MBCONV_DEBUG", 0), env_int("YOLO_STEM_DEBUG", 0),
+                  getenv("YOLO_STEM_ONE_ROLE") != nullptr, env_int("YOLO_MBWIDE_DEBUG", 0), env_int("YOLO_MBWIDE_FORM", 0),
+                  env_int("YOLO_DWCONV_DEBUG", 0), getenv("YOLO_SPP_NO_LINES") != nullptr, env_int("YOLO_RESUNIT_STAGGER", 0)};
   return t;
 }
 
 extern "C" int yolo_set_tuning(int knob, int value) {
-  static constexpr int Tuning::* kKnobs[] = {&Tuning::variant, &Tuning::conv_debug, &Tuning::families, &Tuning::resunit, &Tuning::mbconv};
-  YOLO_REQUIRE(knob >= 0 && knob < 5, "set_tuning: unknown knob %d", knob);
+  static constexpr int Tuning::* kKnobs[] = {&Tuning::variant, &Tuning::conv_debug, &Tuning::families, &Tuning::resunit, &Tuning::mbconv,
+                                             &Tuning::stem_debug, &Tuning::stem_one_role, &Tuning::mbwide_debug, &Tuning::mbwide_form,
+                                             &Tuning::dwconv, &Tuning::spp_no_lines, &Tuning::resunit_stagger};
+  YOLO_REQUIRE(knob >= 0 && knob < 12, "set_tuning: unknown knob %d", knob);
   int& slot = tuning().*kKnobs[knob];
   const int old = slot;
   slot = value;

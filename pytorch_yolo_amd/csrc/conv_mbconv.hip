@@ -798,78 +798,59 @@ __global__ __launch_bounds__(1024) void mbstrip_kernel(const MbArgs a) {
   }
 }
 
-template <int S, bool EXPAND>
-size_t strip_lds_bytes(const MbArgs& a) {
+template <int S>
+size_t strip_lds_bytes(bool expand, int ce, int cop, int dstride) {
   using G = MbStrip<S>;
-  const size_t estride = a.ce * 2 + (EXPAND ? 8 : 0);
-  return (size_t)(EXPAND ? G::RX * G::IWS * kXStride : 0) + (size_t)(EXPAND ? G::RE : G::RNE) * G::IWE * estride + (size_t)2 * G::OPS * a.dstride +
-         (size_t)(EXPAND ? a.ce * kXStride : 0) + (size_t)a.cop * a.dstride + (size_t)(a.ce + a.cop) * 4 +
-         (size_t)(EXPAND ? 3 * G::IWF * (a.ce / 16) * 4 : 0);
+  const size_t estride = ce * 2 + (expand ? 8 : 0);
+  return (size_t)(expand ? G::RX * G::IWS * kXStride : 0) + (size_t)(expand ? G::RE : G::RNE) * G::IWE * estride + (size_t)2 * G::OPS * dstride +
+         (size_t)(expand ? ce * kXStride : 0) + (size_t)cop * dstride + (size_t)(ce + cop) * 4 +
+         (size_t)(expand ? 3 * G::IWF * (ce / 16) * 4 : 0);
 }
 
-// 1: the strip form does not take the block (the caller goes on to the tile form)
-template <int S, bool EXPAND>
-int launch_strip(const MbArgs& a0, hipStream_t s) {
-  MbArgs a = a0;
+// can the strip form hold the block?  (depthwise role: 512 threads; the stride-1 form needs seven four-pixel runs per channel pair:
+// hidden <= 146)
+template <int S>
+bool strip_holds(int cin, int ce, int cop, size_t lds) {
   using G = MbStrip<S>;
-  // (depthwise role: 512 threads; the stride-1 form needs seven four-pixel runs per channel pair: hidden <= 146)
-  if (a.cin % 8 || a.cin > 32 || 3 * G::IW * (a.cin / 8) > G::NPX * G::NE || a.ce % 32 || a.cop > 64 || (S == 1 ? (a.ce / 2) * 7 : a.ce / 4) > G::NDW) return 1;
-  const size_t lds = strip_lds_bytes<S, EXPAND>(a);
-  if (lds > 160 * 1024) return 1;
-  a.tiles_x = (a.wo + G::TW - 1) / G::TW;                    // column segments
-  // one 16-wave workgroup per CU: bands so that the grid is about four rounds of the chip, at least 8 rows each (a band re-expands
-  // S + 1 input rows); narrow maps (few strips of few rows) stay with the tile form
-  const long strips = (long)a.n * a.tiles_x;
-  int bands = (int)((4 * 256 + strips - 1) / strips);
-  if (bands < 1) bands = 1;
-  a.th = (a.ho + bands - 1) / bands;
-  if (a.th < 8) a.th = a.ho < 8 ? a.ho : 8;
-  a.tiles_y = (a.ho + a.th - 1) / a.th;
-  a.n_tiles = a.n * a.tiles_x * a.tiles_y;
+  return !(cin % 8 || cin > 32 || 3 * G::IW * (cin / 8) > G::NPX * G::NE || ce % 32 || cop > 64 || (S == 1 ? (ce / 2) * 7 : ce / 4) > G::NDW) &&
+         lds <= 160 * 1024;
+}
+
+size_t tile_lds_bytes(int S, int TH, int TW, bool expand, int ce, int cop, int dstride) {
+  const int IH = (TH - 1) * S + 3, IW = (TW - 1) * S + 3, HP = IH * IW, HPP = (HP + 15) / 16 * 16, P = TH * TW;
+  return (size_t)(expand ? HPP * kXStride : 0) + (size_t)HPP * (ce * 2 + (expand ? 8 : 0)) + (size_t)P * dstride +
+         (size_t)(expand ? ce * kXStride : 0) + (size_t)cop * dstride + (size_t)(ce + cop + (expand ? ce : 0)) * 4;
+}
+
+template <int S, bool EXPAND>
+int launch_strip(MbArgs a, const MbconvPick& p, hipStream_t s) {
 #ifdef YOLO_STAMPS
   a.stamps = getenv("YOLO_STAMP_PTR") ? (unsigned long long*)strtoull(getenv("YOLO_STAMP_PTR"), nullptr, 0) : nullptr;
-  a.stamp_lds = (int)((lds + 15) / 16 * 16);
+  a.stamp_lds = (int)((p.lds + 15) / 16 * 16);
   if (a.stamp_lds + 768 > 160 * 1024) a.stamps = nullptr;
-  const size_t lds_launch = a.stamps ? (size_t)a.stamp_lds + 768 : lds;
+  const size_t lds_launch = a.stamps ? (size_t)a.stamp_lds + 768 : p.lds;
 #else
-  const size_t lds_launch = lds;
+  const size_t lds_launch = p.lds;
 #endif
   static std::atomic<uint64_t> lds_set{0};                 // per device (common.h)
   if (const int rc = yolo_max_dyn_lds(reinterpret_cast<const void*>(&mbstrip_kernel<S, EXPAND>), 160 * 1024, lds_set, "mbconv (strip)")) return rc;
-  hipLaunchKernelGGL((mbstrip_kernel<S, EXPAND>), dim3((unsigned)a.n_tiles), dim3(1024), lds_launch, s, a);
+  hipLaunchKernelGGL((mbstrip_kernel<S, EXPAND>), dim3((unsigned)p.grid), dim3(1024), lds_launch, s, a);
   return yolo_check_launch("yolo_mbconv_fwd (strip)");
 }
 
 template <int S, int TH, int TW, bool EXPAND, int NT>
-int launch_nt(const MbArgs& a, size_t lds, int slots, hipStream_t s) {
+int launch_nt(const MbArgs& a, const MbconvPick& p, hipStream_t s) {
   static std::atomic<uint64_t> lds_set{0};                 // per device (common.h)
   if (const int rc = yolo_max_dyn_lds(reinterpret_cast<const void*>(&mbconv_kernel<S, TH, TW, EXPAND, NT>), 160 * 1024, lds_set, "mbconv")) return rc;
-  const int grid = a.n_tiles < slots ? a.n_tiles : slots;
-  hipLaunchKernelGGL((mbconv_kernel<S, TH, TW, EXPAND, NT>), dim3((unsigned)grid), dim3(NT), lds, s, a);
+  hipLaunchKernelGGL((mbconv_kernel<S, TH, TW, EXPAND, NT>), dim3((unsigned)p.grid), dim3(NT), p.lds, s, a);
   return yolo_check_launch("yolo_mbconv_fwd");
 }
 
 template <int S, int TH, int TW, bool EXPAND>
-size_t lds_bytes(const MbArgs& a) {
-  constexpr int IH = (TH - 1) * S + 3, IW = (TW - 1) * S + 3, HP = IH * IW, HPP = (HP + 15) / 16 * 16, P = TH * TW;
-  return (size_t)(EXPAND ? HPP * kXStride : 0) + (size_t)HPP * (a.ce * 2 + (EXPAND ? 8 : 0)) + (size_t)P * a.dstride +
-         (size_t)(EXPAND ? a.ce * kXStride : 0) + (size_t)a.cop * a.dstride + (size_t)(a.ce + a.cop + (EXPAND ? a.ce : 0)) * 4;
-}
-
-template <int S, int TH, int TW, bool EXPAND>
-int launch(const MbArgs& a0, hipStream_t s) {
-  MbArgs a = a0;
-  a.tiles_x = (a.wo + TW - 1) / TW;
-  a.tiles_y = (a.ho + TH - 1) / TH;
-  a.n_tiles = a.n * a.tiles_x * a.tiles_y;
-  const size_t lds = lds_bytes<S, TH, TW, EXPAND>(a);
-  YOLO_REQUIRE(lds <= 160 * 1024, "mbconv: %zu bytes of LDS needed", lds);
-  YOLO_REQUIRE((TH * TW / 16) * (a.cop / 16) <= 16, "mbconv: %d projection tiles per output tile (the kernel keeps <= 16 residual fragments)", (TH * TW / 16) * (a.cop / 16));
-  // persistent workgroups; the phases of one tile (load, expand, depthwise, project) are latency chains, so a CU
-  // needs more than 8 waves in flight: two 512-thread workgroups per CU when the LDS allows, else one of 1024 threads
-  if (lds <= 40 * 1024) return launch_nt<S, TH, TW, EXPAND, 256>(a, lds, 1024, s);   // four per CU: phases of four tiles overlap
-  if (lds <= 80 * 1024) return launch_nt<S, TH, TW, EXPAND, 512>(a, lds, 512, s);
-  return launch_nt<S, TH, TW, EXPAND, 1024>(a, lds, 256, s);
+int launch_tile(const MbArgs& a, const MbconvPick& p, hipStream_t s) {
+  if (p.threads == 256) return launch_nt<S, TH, TW, EXPAND, 256>(a, p, s);
+  if (p.threads == 512) return launch_nt<S, TH, TW, EXPAND, 512>(a, p, s);
+  return launch_nt<S, TH, TW, EXPAND, 1024>(a, p, s);
 }
 
 }  // namespace
@@ -884,8 +865,10 @@ extern "C" int yolo_mbconv_dstride(int ce) {
 
 // the wide blocks (hidden dimension streamed in chunks): conv_mbwide.hip
 int yolo_mbwide_supported(int cin, int hidden, int cout, int stride);
+MbconvPick choose_mbwide(const YoloMbconvDesc& d, const Tuning& t);
+int yolo_mbwide_check(const YoloMbconvDesc& d, const MbconvPick& p);
 int yolo_mbwide_launch(const void* x, const void* w_exp, const float* b_exp, const float* w_dw, const float* b_dw, const void* w_proj,
-                       const float* b_proj, void* y, const YoloMbconvDesc& d, hipStream_t st);
+                       const float* b_proj, void* y, const YoloMbconvDesc& d, const MbconvPick& p, hipStream_t st);
 
 // 0: not covered; 1: the whole hidden tile in LDS (this file); 2: the wide form (conv_mbwide.hip) - the two take different weight images
 extern "C" int yolo_mbconv_supported(int cin, int hidden, int cout, int stride) {
@@ -896,21 +879,98 @@ extern "C" int yolo_mbconv_supported(int cin, int hidden, int cout, int stride) 
   return yolo_mbwide_supported(cin, hidden, cout, stride) ? 2 : 0;
 }
 
-extern "C" int yolo_mbconv_fwd(const void* x, const void* w_exp, const float* b_exp, const float* w_dw, const float* b_dw,
-                               const void* w_proj, const float* b_proj, void* y, const YoloMbconvDesc* dp, yolo_stream_t s) {
-  YOLO_REQUIRE(x && w_dw && b_dw && w_proj && b_proj && y && dp, "mbconv: null argument");
-  const YoloMbconvDesc& d = *dp;
+// Which kernel a block yolo_mbconv_supported covers takes, and its launch shape.
+static MbconvPick choose_mbconv(const YoloMbconvDesc& d, const Tuning& t) {
+  if (yolo_mbconv_supported(d.cin, d.hidden, d.cout, d.stride) == 2) return choose_mbwide(d, t);
+  const int ho = (d.h + 2 - 3) / d.stride + 1, wo = (d.w + 2 - 3) / d.stride + 1;
+  const int ce = (d.hidden + 31) / 32 * 32, cop = (d.cout + 15) / 16 * 16, dstride = yolo_mbconv_dstride(ce);
+  const bool expand = d.has_expand != 0;
+  MbconvPick p = {};
+  // the row-strip form, OPT-IN (kMbStripForm; measured slower than the tile form on every block: DESIGN.md Appendix A; tests run
+  // both) and only where it can hold the block
+  if (t.mbconv & kMbStripForm) {
+    p.lds = d.stride == 1 ? strip_lds_bytes<1>(expand, ce, cop, dstride) : strip_lds_bytes<2>(expand, ce, cop, dstride);
+    if (d.stride == 1 ? strip_holds<1>(d.cin, ce, cop, p.lds) : strip_holds<2>(d.cin, ce, cop, p.lds)) {
+      p.form = MbForm::kStrip;
+      p.tw = MbStrip<1>::TW;
+      p.threads = 1024;
+      p.tiles_x = (wo + p.tw - 1) / p.tw;                    // column segments
+      // one 16-wave workgroup per CU: bands so that the grid is about four rounds of the chip, at least 8 rows each (a band
+      // re-expands S + 1 input rows)
+      const long strips = (long)d.n * p.tiles_x;
+      int bands = (int)((4 * 256 + strips - 1) / strips);
+      if (bands < 1) bands = 1;
+      p.th = (ho + bands - 1) / bands;
+      if (p.th < 8) p.th = ho < 8 ? ho : 8;
+      p.tiles_y = (ho + p.th - 1) / p.th;
+      p.grid = p.n_tiles = d.n * p.tiles_x * p.tiles_y;
+      return p;
+    }
+  }
+  // tile: 8x8 outputs (4x8 at stride 2).  192 hidden channels at stride 1: 4x8, which lets two 512-thread workgroups
+  // share a CU instead of one of 1024 threads (-10 %; with 144 hidden channels and at stride 2 the larger halo
+  // share of a half tile costs more than the overlap gains: measured, kMbFullTile = always the full tile)
+  p.form = MbForm::kTile;
+  p.tw = 8;
+  p.th = d.stride == 2 || (expand && (ce >= 192 || (t.mbconv & kMbHalfTile)) && !(t.mbconv & kMbFullTile) &&
+                           tile_lds_bytes(1, 4, 8, true, ce, cop, dstride) <= 80 * 1024) ? 4 : 8;
+  p.lds = tile_lds_bytes(d.stride, p.th, p.tw, expand, ce, cop, dstride);
+  p.tiles_x = (wo + p.tw - 1) / p.tw;
+  p.tiles_y = (ho + p.th - 1) / p.th;
+  p.n_tiles = d.n * p.tiles_x * p.tiles_y;
+  // persistent workgroups; the phases of one tile (load, expand, depthwise, project) are latency chains, so a CU
+  // needs more than 8 waves in flight: four 256-thread workgroups per CU (phases of four tiles overlap) or two of 512 threads
+  // when the LDS allows, else one of 1024 threads
+  p.threads = p.lds <= 40 * 1024 ? 256 : p.lds <= 80 * 1024 ? 512 : 1024;
+  const int slots = 256 * 1024 / p.threads;
+  p.grid = p.n_tiles < slots ? p.n_tiles : slots;
+  return p;
+}
+
+// the checks of yolo_mbconv_fwd that need no pointer, the rule, and what the chosen kernel must hold
+static int plan_mbconv(const YoloMbconvDesc& d, MbconvPick* p) {
   YOLO_REQUIRE(yolo_mbconv_supported(d.cin, d.hidden, d.cout, d.stride), "mbconv: cin %d hidden %d cout %d stride %d not covered",
                d.cin, d.hidden, d.cout, d.stride);
-  YOLO_REQUIRE(d.has_expand ? (w_exp && b_exp) : d.hidden == d.cin, "mbconv: a block without expand conv has hidden == cin");
+  YOLO_REQUIRE(d.has_expand || d.hidden == d.cin, "mbconv: a block without expand conv has hidden == cin");
   YOLO_REQUIRE(!d.has_res || (d.stride == 1 && d.cin == d.cout), "mbconv: residual needs stride 1 and cin == cout");
   YOLO_REQUIRE(d.in_c_offset % 8 == 0 && d.in_c_total % 8 == 0 && d.in_c_offset + d.cin <= d.in_c_total, "mbconv: bad input view");
   YOLO_REQUIRE(d.out_c_offset % 4 == 0 && d.out_c_total % 4 == 0 && d.out_c_offset + d.cout <= d.out_c_total, "mbconv: bad output view");
   YOLO_REQUIRE(d.n > 0 && d.h > 0 && d.w > 0, "mbconv: empty input");
-  if (yolo_mbconv_supported(d.cin, d.hidden, d.cout, d.stride) == 2) {
+  *p = choose_mbconv(d, tuning());
+  if (p->form == MbForm::kWide) {
     YOLO_REQUIRE(d.has_expand, "mbconv: the wide form needs the expand conv");
-    return yolo_mbwide_launch(x, w_exp, b_exp, w_dw, b_dw, w_proj, b_proj, y, d, (hipStream_t)s);
+    return yolo_mbwide_check(d, *p);
   }
+  if (p->form == MbForm::kTile) {
+    const int ptiles = (p->th * p->tw / 16) * (((d.cout + 15) / 16 * 16) / 16);
+    YOLO_REQUIRE(p->lds <= 160 * 1024, "mbconv: %zu bytes of LDS needed", p->lds);
+    YOLO_REQUIRE(ptiles <= 16, "mbconv: %d projection tiles per output tile (the kernel keeps <= 16 residual fragments)", ptiles);
+  }
+  return 0;
+}
+
+extern "C" int yolo_mbconv_pick(const YoloMbconvDesc* dp, char* out, int out_len) {
+  YOLO_REQUIRE(dp && out && out_len > 0, "mbconv_pick: bad arguments");
+  MbconvPick p;
+  if (const int rc = plan_mbconv(*dp, &p)) return rc;
+  const char* ex = dp->has_expand ? "expand" : "no expand";
+  switch (p.form) {
+    case MbForm::kTile: snprintf(out, out_len, "mbconv<S %d,%dx%d,%s,%d threads> grid %d", dp->stride, p.th, p.tw, ex, p.threads, p.grid); break;
+    case MbForm::kStrip: snprintf(out, out_len, "mbstrip<S %d,%s,%d rows x %d> grid %d", dp->stride, ex, p.th, p.tw, p.grid); break;
+    case MbForm::kWide: snprintf(out, out_len, "mbwide<S %d,%dx%d,%d threads,MC %d> grid %d", dp->stride, p.th, p.tw, p.threads, p.mc, p.grid); break;
+  }
+  return 0;
+}
+
+extern "C" int yolo_mbconv_fwd(const void* x, const void* w_exp, const float* b_exp, const float* w_dw, const float* b_dw,
+                               const void* w_proj, const float* b_proj, void* y, const YoloMbconvDesc* dp, yolo_stream_t s) {
+  YOLO_REQUIRE(x && w_dw && b_dw && w_proj && b_proj && y && dp, "mbconv: null argument");
+  const YoloMbconvDesc& d = *dp;
+  YOLO_REQUIRE(!d.has_expand || (w_exp && b_exp), "mbconv: a block with expand conv needs its weights");
+  MbconvPick p;
+  if (const int rc = plan_mbconv(d, &p)) return rc;
+  hipStream_t st = (hipStream_t)s;
+  if (p.form == MbForm::kWide) return yolo_mbwide_launch(x, w_exp, b_exp, w_dw, b_dw, w_proj, b_proj, y, d, p, st);
   MbArgs a;
   a.x = (const bf16_t*)x;
   a.y = (bf16_t*)y;
@@ -935,22 +995,15 @@ extern "C" int yolo_mbconv_fwd(const void* x, const void* w_exp, const float* b_
   a.out_co = d.out_c_offset;
   a.has_res = d.has_res;
   a.dstride = yolo_mbconv_dstride(a.ce);
-  a.tiles_x = a.tiles_y = a.n_tiles = a.th = 0;
+  a.tiles_x = p.tiles_x;
+  a.tiles_y = p.tiles_y;
+  a.n_tiles = p.n_tiles;
+  a.th = p.form == MbForm::kStrip ? p.th : 0;
   a.debug = tuning().mbconv;
-  hipStream_t st = (hipStream_t)s;
-  if (a.debug & kMbStripForm) {              // round 5: the row-strip form, OPT-IN (measured slower than the tile form on every block: DESIGN.md
-                                    // Appendix A; tests run both); 1: it does not take the block
-    const int rc = d.stride == 1 ? (d.has_expand ? launch_strip<1, true>(a, st) : launch_strip<1, false>(a, st))
-                                 : (d.has_expand ? launch_strip<2, true>(a, st) : launch_strip<2, false>(a, st));
-    if (rc != 1) return rc;
-  }
-  // tile: 8x8 outputs (4x8 at stride 2).  192 hidden channels at stride 1: 4x8, which lets two 512-thread workgroups
-  // share a CU instead of one of 1024 threads (-10 %; with 144 hidden channels and at stride 2 the larger halo
-  // share of a half tile costs more than the overlap gains: measured, kMbFullTile = always the full tile)
-  if (d.stride == 1) {
-    if (!d.has_expand) return launch<1, 8, 8, false>(a, st);
-    if ((a.ce >= 192 || (a.debug & kMbHalfTile)) && !(a.debug & kMbFullTile) && lds_bytes<1, 4, 8, true>(a) <= 80 * 1024) return launch<1, 4, 8, true>(a, st);
-    return launch<1, 8, 8, true>(a, st);
-  }
-  return d.has_expand ? launch<2, 4, 8, true>(a, st) : launch<2, 4, 8, false>(a, st);
+  if (p.form == MbForm::kStrip)
+    return d.stride == 1 ? (d.has_expand ? launch_strip<1, true>(a, p, st) : launch_strip<1, false>(a, p, st))
+                         : (d.has_expand ? launch_strip<2, true>(a, p, st) : launch_strip<2, false>(a, p, st));
+  if (d.stride == 2) return d.has_expand ? launch_tile<2, 4, 8, true>(a, p, st) : launch_tile<2, 4, 8, false>(a, p, st);
+  if (!d.has_expand) return launch_tile<1, 8, 8, false>(a, p, st);
+  return p.th == 4 ? launch_tile<1, 4, 8, true>(a, p, st) : launch_tile<1, 8, 8, true>(a, p, st);
 }

@@ -329,36 +329,17 @@ __global__ __launch_bounds__(NT) void mbwide_kernel(const MbwArgs a) {
 }
 
 template <int S, int TH, int TW, int NT, int MC>
-int launch(MbwArgs a, hipStream_t s) {
-  a.tiles_x = (a.wo + TW - 1) / TW;
-  a.tiles_y = (a.ho + TH - 1) / TH;
-  a.n_tiles = a.n * a.tiles_x * a.tiles_y;
-  const Lds m = lds_map<S, TH, TW>(a.cin, a.cop);
-  const long x_bytes = (long)a.n * a.h * a.w * a.in_ct * 2;
-  YOLO_REQUIRE(m.total <= 160 * 1024 && a.cop <= 16 * MC * (NT / 256) && a.cin <= 160 && x_bytes < (1l << 31) && (long)a.cop * a.ce * 2 < (1l << 31),
-               "mbconv (wide): cin %d cout %d does not fit the %dx%d tile form (%d bytes of LDS), or a tensor of 2 GB", a.cin, a.cout,
-               TH, TW, m.total);
-  a.x_bytes = (uint32_t)x_bytes;
+int launch(const MbwArgs& a, const MbconvPick& p, hipStream_t s) {
   static std::atomic<uint64_t> lds_set{0};                 // per device (common.h)
   if (const int rc = yolo_max_dyn_lds(reinterpret_cast<const void*>(&mbwide_kernel<S, TH, TW, NT, MC>), 160 * 1024, lds_set, "mbconv (wide)")) return rc;
-  const int grid = a.n_tiles < 256 ? a.n_tiles : 256;
-  hipLaunchKernelGGL((mbwide_kernel<S, TH, TW, NT, MC>), dim3((unsigned)grid), dim3(NT), (size_t)m.total, s, a);
+  hipLaunchKernelGGL((mbwide_kernel<S, TH, TW, NT, MC>), dim3((unsigned)p.grid), dim3(NT), p.lds, s, a);
   return yolo_check_launch("yolo_mbconv_fwd (wide)");
 }
-
-const int mbw_form = [] {      // YOLO_MBWIDE_FORM (tests / tuning): 1 = 13x13 tiles whenever they fit, 2 = 7x7 tiles always
-  const char* e = getenv("YOLO_MBWIDE_FORM");
-  return e ? atoi(e) : 0;
-}();
-const int mbw_debug = [] {
-  const char* e = getenv("YOLO_MBWIDE_DEBUG");
-  return e ? atoi(e) : 0;
-}();
 
 }  // namespace
 
 // The wide form covers: expand conv present, cin a multiple of 32 in 64..160 (stride 2: ..96), hidden a multiple of 64,
-// cout a multiple of 4 up to 320 - AND the 7x7-tile form (the one yolo_mbwide_launch falls back to for every map size) must fit the
+// cout a multiple of 4 up to 320 - AND the 7x7-tile form (the one choose_mbwide falls back to for every map size) must fit the
 // CU: its LDS map within 160 KB and cout within its 16 * MC * 2 accumulator columns.  (stride 2, cin 96, cout in
 // (256, 320] passed the channel tests, the planner fused the block away, and the launch then refused it at run time.)
 int yolo_mbwide_supported(int cin, int hidden, int cout, int stride) {
@@ -370,8 +351,39 @@ int yolo_mbwide_supported(int cin, int hidden, int cout, int stride) {
   return total <= 160 * 1024 && cop <= 16 * 10 * 2;
 }
 
+// The wide form's part of choose_mbconv (conv_mbconv.hip): 7x7 output tiles, or at stride 1 13x13 tiles (a quarter of a 26x26 map:
+// 42 % halo instead of 127 %, a quarter of the weight passes) while they give every CU a tile and the block is narrow enough for
+// their LDS / accumulator budget.  Tuning::mbwide_form: 1 = 13x13 whenever they fit, 2 = 7x7 always.
+MbconvPick choose_mbwide(const YoloMbconvDesc& d, const Tuning& t) {
+  const int ho = (d.h + 2 - 3) / d.stride + 1, wo = (d.w + 2 - 3) / d.stride + 1, cop = (d.cout + 15) / 16 * 16;
+  const long t13 = (long)d.n * ((ho + 12) / 13) * ((wo + 12) / 13);
+  const bool wide13 = d.stride == 1 && d.cin <= 96 && cop <= 128 && (t13 >= 192 || t.mbwide_form == 1) && t.mbwide_form != 2 &&
+                      lds_map<1, 13, 13>(d.cin, cop).total <= 160 * 1024;
+  MbconvPick p = {};
+  p.form = MbForm::kWide;
+  p.th = p.tw = wide13 ? 13 : 7;
+  p.mc = wide13 ? 4 : 10;
+  p.threads = 512;
+  p.lds = wide13 ? lds_map<1, 13, 13>(d.cin, cop).total : d.stride == 2 ? lds_map<2, 7, 7>(d.cin, cop).total : lds_map<1, 7, 7>(d.cin, cop).total;
+  p.tiles_x = (wo + p.tw - 1) / p.tw;
+  p.tiles_y = (ho + p.th - 1) / p.th;
+  p.n_tiles = d.n * p.tiles_x * p.tiles_y;
+  p.grid = p.n_tiles < 256 ? p.n_tiles : 256;              // one workgroup of 8 waves per CU
+  return p;
+}
+
+// what the kernel's tile form and its 32-bit buffer offsets must hold
+int yolo_mbwide_check(const YoloMbconvDesc& d, const MbconvPick& p) {
+  const int cop = (d.cout + 15) / 16 * 16;
+  const long x_bytes = (long)d.n * d.h * d.w * d.in_c_total * 2;
+  YOLO_REQUIRE(p.lds <= 160 * 1024 && cop <= 16 * p.mc * (p.threads / 256) && d.cin <= 160 && x_bytes < (1l << 31) && (long)cop * d.hidden * 2 < (1l << 31),
+               "mbconv (wide): cin %d cout %d does not fit the %dx%d tile form (%d bytes of LDS), or a tensor of 2 GB", d.cin, d.cout,
+               p.th, p.tw, (int)p.lds);
+  return 0;
+}
+
 int yolo_mbwide_launch(const void* x, const void* w_exp, const float* b_exp, const float* w_dw, const float* b_dw, const void* w_proj,
-                       const float* b_proj, void* y, const YoloMbconvDesc& d, hipStream_t st) {
+                       const float* b_proj, void* y, const YoloMbconvDesc& d, const MbconvPick& p, hipStream_t st) {
   MbwArgs a;
   a.x = (const bf16_t*)x;
   a.y = (bf16_t*)y;
@@ -395,13 +407,11 @@ int yolo_mbwide_launch(const void* x, const void* w_exp, const float* b_exp, con
   a.out_ct = d.out_c_total;
   a.out_co = d.out_c_offset;
   a.has_res = d.has_res;
-  a.tiles_x = a.tiles_y = a.n_tiles = 0;
-  a.debug = mbw_debug;
-  if (d.stride == 2) return launch<2, 7, 7, 512, 10>(a, st);
-  // 13x13 tiles (a quarter of a 26x26 map: 42 % halo instead of 127 %, a quarter of the weight passes) while they give every
-  // CU a tile and the block is narrow enough for their LDS / accumulator budget
-  const long t13 = (long)d.n * ((a.ho + 12) / 13) * ((a.wo + 12) / 13);
-  if (d.cin <= 96 && a.cop <= 128 && (t13 >= 192 || mbw_form == 1) && mbw_form != 2 && lds_map<1, 13, 13>(a.cin, a.cop).total <= 160 * 1024)
-    return launch<1, 13, 13, 512, 4>(a, st);
-  return launch<1, 7, 7, 512, 10>(a, st);
+  a.tiles_x = p.tiles_x;
+  a.tiles_y = p.tiles_y;
+  a.n_tiles = p.n_tiles;
+  a.x_bytes = (uint32_t)((long)d.n * d.h * d.w * d.in_c_total * 2);
+  a.debug = tuning().mbwide_debug;
+  if (d.stride == 2) return launch<2, 7, 7, 512, 10>(a, p, st);
+  return p.th == 13 ? launch<1, 13, 13, 512, 4>(a, p, st) : launch<1, 7, 7, 512, 10>(a, p, st);
 }

@@ -561,13 +561,70 @@ __global__ __launch_bounds__(512) void resunit64_kernel(const ResUnitArgs ra) {
   }
 }
 
-template <int C>
-int launch(const ResUnitArgs& ra, hipStream_t s) {
-  const YoloConvDesc& d = ra.c.d;
-  const long grid = (long)d.n * ((d.h + 15) / 16) * ((d.w + 15) / 16);
-  if (grid > 0x7fffffffL) return yolo_set_error(YOLO_E_UNSUPPORTED, "resunit grid too large");
-  hipLaunchKernelGGL((resunit_kernel<C>), dim3((unsigned)grid), dim3(512), 0, s, ra);
-  return yolo_check_launch("yolo_resunit_fwd");
+// Which kernel a unit takes, and its launch shape.
+enum class RuForm { kT20C64, kT20wC128, kT20wC256, kPersistent64, kGeneric };   // resunit64_t20, resunit_t20w<64, 5> / <128, 2>, resunit64, resunit<C>
+struct ResunitPick {
+  RuForm form;
+  int th, tw, threads;  // output tile of a workgroup
+  long grid;
+  size_t lds;           // dynamic LDS bytes
+};
+
+// The shipped rule of the 20-pixel-wide tile kernels (conv_resunit_t20.hip) for a C-channel unit on n maps of h x w.  Partial tiles
+// idle lanes (and MFMAs): tiles must cover >= 90 % of the map; few tiles leave CUs without their two workgroups: >= 256 tiles of
+// 20x20 for C = 64, >= 512 of 20x20 (C = 128) or 8x20 (C = 256).
+bool t20_fills_the_chip(int c, int n, int h, int w, int th, long tiles) {
+  return (double)n * h * w >= 0.9 * (20.0 * th) * tiles && tiles >= (c == 64 ? 256 : 512);
+}
+
+// d: a unit yolo_resunit_supported accepts (C = d.cout in {64, 128, 256}); the residual is the input view.
+ResunitPick choose_resunit(const YoloConvDesc& d, bool has_aux, int n_cu, const Tuning& t) {
+  const int C = d.cout;
+  ResunitPick p;
+  p.lds = 0;
+  // the 20-pixel-wide tile kernels: LeakyReLU / ReLU6 / no activation, 32-bit byte offsets into y, x and the pre-add copy; where
+  // their tiles fill the chip, or on every such unit (kRuT20Always)
+  const size_t npix = (size_t)d.n * d.h * d.w;
+  const bool fits32 = npix * d.out_c_total * 2 < kOobOffset && npix * d.in_c_total * 2 < kOobOffset && !(has_aux && npix * d.aux_c_total * 2 >= kOobOffset);
+  if (!(t.resunit & kRuT20Never) && d.act != YOLO_ACT_SWISH && fits32) {
+    p.th = C == 256 ? 8 : 20;
+    p.tw = 20;
+    p.grid = (long)d.n * ((d.h + p.th - 1) / p.th) * ((d.w + p.tw - 1) / p.tw);
+    if (((t.resunit & kRuT20Always) || t20_fills_the_chip(C, d.n, d.h, d.w, p.th, p.grid)) && p.grid <= 0x7fffffffL) {
+      p.form = C == 64 ? RuForm::kT20C64 : C == 128 ? RuForm::kT20wC128 : RuForm::kT20wC256;
+      p.threads = 256;
+      if (C != 64 && (t.resunit & kRuT20OnePerCu)) p.lds = 40 * 1024;     // one workgroup per CU (diagnosis)
+      return p;
+    }
+  }
+  p.th = p.tw = 16;
+  p.threads = 512;
+  const long tiles = (long)d.n * ((d.h + 15) / 16) * ((d.w + 15) / 16);
+  if (C == 64 && !(t.resunit & kRuGeneric64)) {      // persistent, software-pipelined form (kRuGeneric64: generic kernel)
+    p.form = RuForm::kPersistent64;
+    p.grid = tiles < n_cu ? tiles : n_cu;
+    return p;
+  }
+  p.form = RuForm::kGeneric;
+  p.grid = tiles;
+  return p;
+}
+
+// the checks of yolo_resunit_fwd that need no pointer, then the rule
+int plan_resunit(const YoloConvDesc& d, bool has_aux, ResunitPick* p) {
+  const int C = d.cout;            // d describes the 3x3: cin = C/2, cout = C; the input view describes x (C channels)
+  YOLO_REQUIRE(yolo_resunit_supported(C, d.h, d.w), "resunit: C=%d on %dx%d is not covered (use the two-kernel path)", C, d.h, d.w);
+  YOLO_REQUIRE(d.cin * 2 == C && d.ksize == 3 && d.stride == 1 && d.pad == 1 && d.ho == d.h && d.wo == d.w && !d.upsample2x &&
+                   d.out_dtype == YOLO_DT_BF16,
+               "resunit: descriptor must be the unit's 3x3/s1/p1 conv with cin = cout/2");
+  YOLO_REQUIRE(d.in_c_offset % 8 == 0 && d.in_c_total % 8 == 0 && d.in_c_offset + C <= d.in_c_total, "resunit: bad input view");
+  YOLO_REQUIRE(d.out_c_offset % 8 == 0 && d.out_c_total % 8 == 0 && d.out_c_offset + C <= d.out_c_total, "resunit: bad output view");
+  if (has_aux) YOLO_REQUIRE(d.aux_c_total % 8 == 0 && d.aux_c_offset % 8 == 0, "resunit: bad aux view");
+  YOLO_REQUIRE(d.kpad % 64 == 0 && d.kpad >= 9 * d.cin && d.cout_pad % 128 == 0 && d.cout_pad >= C, "resunit: bad W2 packing");
+  YOLO_REQUIRE(conv_x_bytes(d) < kOobOffset && conv_w_bytes(d) < kOobOffset, "resunit: tensor larger than 3.75 GiB not supported");
+  *p = choose_resunit(d, has_aux, yolo_device_cus(), tuning());
+  if (p->grid > 0x7fffffffL) return yolo_set_error(YOLO_E_UNSUPPORTED, "resunit grid too large");
+  return 0;
 }
 
 }  // namespace
@@ -578,29 +635,40 @@ extern "C" int yolo_resunit_supported(int c, int h, int w) {
   return (double)h * w >= 0.85 * 256.0 * tiles && (long)h * w >= 80 * 80;
 }
 
+// 0 not supported, 1 generic 16x16-tile kernel, 2 persistent 64-channel kernel, 3 the 20-pixel-wide tile kernels: the rule's answer
+// for a LeakyReLU unit on dense views, with every knob at its default
 extern "C" int yolo_resunit_form(int c, int n, int h, int w) {
   if (!yolo_resunit_supported(c, h, w)) return 0;
-  if (resunit_t20_applies(c, n, h, w)) return 3;
-  return c == 64 ? 2 : 1;
+  YoloConvDesc d = {};
+  d.n = n, d.h = d.ho = h, d.w = d.wo = w, d.cin = c / 2, d.cout = d.in_c_total = d.out_c_total = c, d.act = YOLO_ACT_LEAKY01;
+  const RuForm f = choose_resunit(d, false, 256, Tuning()).form;
+  return f == RuForm::kGeneric ? 1 : f == RuForm::kPersistent64 ? 2 : 3;
+}
+
+extern "C" int yolo_resunit_pick(const YoloConvDesc* dp, int has_preadd, char* out, int out_len) {
+  YOLO_REQUIRE(dp && out && out_len > 0, "resunit_pick: bad arguments");
+  ResunitPick p;
+  if (const int rc = plan_resunit(*dp, has_preadd != 0, &p)) return rc;
+  const int C = dp->cout;
+  switch (p.form) {
+    case RuForm::kT20C64: snprintf(out, out_len, "resunit64_t20<400px x 64 couts, 4 waves> grid %ld", p.grid); break;
+    case RuForm::kT20wC128:
+    case RuForm::kT20wC256: snprintf(out, out_len, "resunit_t20w<C %d, %dpx x %d couts, 4 waves> grid %ld", C, p.th * p.tw, C, p.grid); break;
+    case RuForm::kPersistent64: snprintf(out, out_len, "resunit64<256px x 64 couts, 8 waves, persistent> grid %ld", p.grid); break;
+    case RuForm::kGeneric: snprintf(out, out_len, "resunit<C %d, 256px x %d couts, 8 waves> grid %ld", C, C, p.grid); break;
+  }
+  return 0;
 }
 
 extern "C" int yolo_resunit_fwd(const void* x, const void* w1_packed, const float* b1, const void* w2_packed, const float* b2,
                                 void* y, void* y_preadd, const YoloConvDesc* dp, int kpad1, int cout_pad1,
                                 yolo_stream_t s) {
   YOLO_REQUIRE(x && w1_packed && b1 && w2_packed && b2 && y && dp, "resunit: null pointer");
-  const YoloConvDesc& d = *dp;     // describes the 3x3: cin = C/2, cout = C; the input view describes x (C channels)
-  const int C = d.cout;
-  YOLO_REQUIRE(yolo_resunit_supported(C, d.h, d.w), "resunit: C=%d on %dx%d is not covered (use the two-kernel path)", C, d.h, d.w);
-  YOLO_REQUIRE(d.cin * 2 == C && d.ksize == 3 && d.stride == 1 && d.pad == 1 && d.ho == d.h && d.wo == d.w && !d.upsample2x &&
-                   d.out_dtype == YOLO_DT_BF16,
-               "resunit: descriptor must be the unit's 3x3/s1/p1 conv with cin = cout/2");
-  YOLO_REQUIRE(d.in_c_offset % 8 == 0 && d.in_c_total % 8 == 0 && d.in_c_offset + C <= d.in_c_total, "resunit: bad input view");
-  YOLO_REQUIRE(d.out_c_offset % 8 == 0 && d.out_c_total % 8 == 0 && d.out_c_offset + C <= d.out_c_total, "resunit: bad output view");
-  if (y_preadd) YOLO_REQUIRE(d.aux_c_total % 8 == 0 && d.aux_c_offset % 8 == 0, "resunit: bad aux view");
-  YOLO_REQUIRE(d.kpad % 64 == 0 && d.kpad >= 9 * d.cin && d.cout_pad % 128 == 0 && d.cout_pad >= C, "resunit: bad W2 packing");
-  YOLO_REQUIRE(kpad1 % 64 == 0 && kpad1 >= C && cout_pad1 % 128 == 0 && cout_pad1 >= d.cin, "resunit: bad W1 packing");
+  const YoloConvDesc& d = *dp;
+  ResunitPick p;
+  if (const int rc = plan_resunit(d, y_preadd != nullptr, &p)) return rc;
+  YOLO_REQUIRE(kpad1 % 64 == 0 && kpad1 >= d.cout && cout_pad1 % 128 == 0 && cout_pad1 >= d.cin, "resunit: bad W1 packing");
   YOLO_REQUIRE(x != y, "resunit: y must not alias x (blocks read their neighbours' x halo)");
-  YOLO_REQUIRE(conv_x_bytes(d) < kOobOffset && conv_w_bytes(d) < kOobOffset, "resunit: tensor larger than 3.75 GiB not supported");
   ResUnitArgs ra;
   ra.c = make_conv_args(x, w2_packed, b2, x, y, y_preadd, d);   // (ho x wo = h x w: checked above)
   ra.c.d.res_c_total = d.in_c_total;
@@ -611,23 +679,18 @@ extern "C" int yolo_resunit_fwd(const void* x, const void* w1_packed, const floa
   ra.b1 = b1;
   ra.kpad1 = kpad1;
   ra.w1_bytes = (uint32_t)((size_t)cout_pad1 * kpad1 * 2);
-  if (!(ra.c.debug & kRuT20Never)) {       // the 20-pixel-wide tile kernels (conv_resunit_t20.hip) where their tiles cover the map, or on every unit (kRuT20Always)
-    const int rc = launch_resunit_t20(ra.c, ra.w1, ra.b1, ra.kpad1, ra.w1_bytes, (ra.c.debug & kRuT20Always) != 0, (hipStream_t)s);
-    if (rc != 1) return rc;
+  hipStream_t st = (hipStream_t)s;
+  const dim3 g((unsigned)p.grid), blk(p.threads);
+  switch (p.form) {
+    case RuForm::kT20C64:
+    case RuForm::kT20wC128:
+    case RuForm::kT20wC256: return launch_resunit_t20(ra.c, ra.w1, ra.b1, ra.kpad1, ra.w1_bytes, tuning().resunit_stagger, g, p.lds, st);
+    case RuForm::kPersistent64: hipLaunchKernelGGL(resunit64_kernel, g, blk, 0, st, ra); break;
+    case RuForm::kGeneric:
+      if (d.cout == 64) hipLaunchKernelGGL((resunit_kernel<64>), g, blk, 0, st, ra);
+      else if (d.cout == 128) hipLaunchKernelGGL((resunit_kernel<128>), g, blk, 0, st, ra);
+      else hipLaunchKernelGGL((resunit_kernel<256>), g, blk, 0, st, ra);
+      break;
   }
-  if (C == 64 && !(ra.c.debug & kRuGeneric64)) {        // persistent, software-pipelined form (kRuGeneric64: generic kernel)
-    static const int n_cu = [] {
-      int dev = 0, v = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-        v = 256;
-      return v;
-    }();
-    const long tiles = (long)d.n * ((d.h + 15) / 16) * ((d.w + 15) / 16);
-    const long grid = tiles < n_cu ? tiles : n_cu;
-    hipLaunchKernelGGL(resunit64_kernel, dim3((unsigned)grid), dim3(512), 0, (hipStream_t)s, ra);
-    return yolo_check_launch("yolo_resunit_fwd");
-  }
-  if (C == 64) return launch<64>(ra, (hipStream_t)s);
-  if (C == 128) return launch<128>(ra, (hipStream_t)s);
-  return launch<256>(ra, (hipStream_t)s);
+  return yolo_check_launch("yolo_resunit_fwd");
 }

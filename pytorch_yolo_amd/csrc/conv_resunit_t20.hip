@@ -682,41 +682,14 @@ __global__ __launch_bounds__(256, 2) void resunit_t20w_kernel(const RU20Args ra)
   RU_STAMP(5);
 }
 
-template <int CMID, int TPH>
-int launch_ruw(const RU20Args& ra, bool force, hipStream_t s) {
-  const YoloConvDesc& d = ra.c.d;
-  const long tiles = (long)d.n * ((d.h + 4 * TPH - 1) / (4 * TPH)) * ((d.w + kT - 1) / kT);
-  if (!force && !resunit_t20_applies(2 * CMID, d.n, d.h, d.w)) return 1;
-  if (tiles > 0x7fffffffL) return 1;
-  if (pick_only("resunit_t20w<C %d, %dpx x %d couts, 4 waves> grid %ld", 2 * CMID, 80 * TPH, 2 * CMID, tiles)) return 0;
-  const size_t dyn = (ra.c.debug & kRuT20OnePerCu) ? 40 * 1024 : 0;                    // one workgroup per CU (diagnosis)
-  if (ra.c.d.act == YOLO_ACT_LEAKY01) hipLaunchKernelGGL((resunit_t20w_kernel<CMID, TPH, true>), dim3((unsigned)tiles), dim3(256), dyn, s, ra);
-  else hipLaunchKernelGGL((resunit_t20w_kernel<CMID, TPH, false>), dim3((unsigned)tiles), dim3(256), dyn, s, ra);
-  return yolo_check_launch("yolo_resunit_fwd(t20w)");
-}
-
 }  // namespace
 
 namespace yolo_conv {
 
-// The shipped rule: do the 20-pixel-wide tile kernels take a C-channel unit on n maps of h x w?  Partial tiles idle lanes (and
-// MFMAs): tiles must cover >= 90 % of the map; few tiles leave CUs without their two workgroups: >= 256 tiles of 20x20 for C = 64,
-// >= 512 of 20x20 (C = 128) or 20x8 (C = 256).
-bool resunit_t20_applies(int c, int n, int h, int w) {
-  const int th = c == 256 ? 8 : 20;
-  if (c != 64 && c != 128 && c != 256) return false;
-  const long tiles = (long)n * ((h + th - 1) / th) * ((w + kT - 1) / kT);
-  return (double)n * h * w >= 0.9 * (20.0 * th) * tiles && tiles >= (c == 64 ? 256 : 512);
-}
-
-// 1: not this kernel's case (the caller falls back to the 16x16-tile kernels)
-int launch_resunit_t20(const ConvArgs& c, const bf16_t* w1, const float* b1, int kpad1, uint32_t w1_bytes, bool force, hipStream_t s) {
-  const YoloConvDesc& d = c.d;
-  if (d.cin * 2 != d.cout || d.act == YOLO_ACT_SWISH || !c.res) return 1;
-  if (d.cout != 64 && d.cout != 128 && d.cout != 256) return 1;
-  const size_t npix = (size_t)d.n * d.h * d.w;
-  if (npix * d.out_c_total * 2 >= kOobOffset || npix * d.res_c_total * 2 >= kOobOffset || (c.aux && npix * d.aux_c_total * 2 >= kOobOffset))
-    return 1;
+// The unit's launch in the form choose_resunit (conv_resunit.hip) named: d.cout 64 -> resunit64_t20_kernel, 128 / 256 ->
+// resunit_t20w_kernel<64, 5> / <128, 2>; grid = its tiles, lds = dynamic LDS bytes.
+int launch_resunit_t20(const ConvArgs& c, const bf16_t* w1, const float* b1, int kpad1, uint32_t w1_bytes, int stagger, dim3 grid, size_t lds,
+                       hipStream_t s) {
   RU20Args ra;
   ra.c = c;
   ra.w1 = w1;
@@ -724,18 +697,22 @@ int launch_resunit_t20(const ConvArgs& c, const bf16_t* w1, const float* b1, int
   ra.kpad1 = kpad1;
   ra.w1_bytes = w1_bytes;
   YOLO_SET_STAMPS(ra.c);
-  static const int stagger_env = getenv("YOLO_RESUNIT_STAGGER") ? atoi(getenv("YOLO_RESUNIT_STAGGER")) : -1;   // tuning only
-  ra.stagger = stagger_env >= 0 ? stagger_env : 0;
-  if (d.cout == 128) return launch_ruw<64, 5>(ra, force, s);
-  if (d.cout == 256) return launch_ruw<128, 2>(ra, force, s);
-  const long tiles = (long)d.n * ((d.h + kT - 1) / kT) * ((d.w + kT - 1) / kT);
-  // otherwise the persistent 16x16-tile kernel (YOLO_RESUNIT_DEBUG bit 64 forces this one)
-  if (!force && !resunit_t20_applies(64, d.n, d.h, d.w)) return 1;
-  if (tiles > 0x7fffffffL) return 1;
-  if (pick_only("resunit64_t20<400px x 64 couts, 4 waves> grid %ld", tiles)) return 0;
-  if (d.act == YOLO_ACT_LEAKY01) hipLaunchKernelGGL(resunit64_t20_kernel<true>, dim3((unsigned)tiles), dim3(256), 0, s, ra);
-  else hipLaunchKernelGGL(resunit64_t20_kernel<false>, dim3((unsigned)tiles), dim3(256), 0, s, ra);
-  return yolo_check_launch("yolo_resunit_fwd(t20)");
+  ra.stagger = stagger;
+  const bool leaky = c.d.act == YOLO_ACT_LEAKY01;
+  const dim3 blk(256);
+  if (c.d.cout == 64) {
+    if (leaky) hipLaunchKernelGGL(resunit64_t20_kernel<true>, grid, blk, lds, s, ra);
+    else hipLaunchKernelGGL(resunit64_t20_kernel<false>, grid, blk, lds, s, ra);
+    return yolo_check_launch("yolo_resunit_fwd(t20)");
+  }
+  if (c.d.cout == 128) {
+    if (leaky) hipLaunchKernelGGL((resunit_t20w_kernel<64, 5, true>), grid, blk, lds, s, ra);
+    else hipLaunchKernelGGL((resunit_t20w_kernel<64, 5, false>), grid, blk, lds, s, ra);
+  } else {
+    if (leaky) hipLaunchKernelGGL((resunit_t20w_kernel<128, 2, true>), grid, blk, lds, s, ra);
+    else hipLaunchKernelGGL((resunit_t20w_kernel<128, 2, false>), grid, blk, lds, s, ra);
+  }
+  return yolo_check_launch("yolo_resunit_fwd(t20w)");
 }
 
 }  // namespace yolo_conv

@@ -671,16 +671,60 @@ extern "C" int yolo_stem_supported(int cin_real, int c1, int c2, int h, int w) {
   return cin_real >= 1 && cin_real <= 8 && c1 == 32 && c2 == 64 && h >= 2 && w >= 2;
 }
 
-extern "C" int yolo_stem_fwd(const float* x_nchw, int cin_real, const void* w1_packed, const float* b1, int kpad1,
-                             const void* w2_packed, const float* b2, void* y, const YoloConvDesc* dp, yolo_stream_t s) {
-  YOLO_REQUIRE(x_nchw && w1_packed && b1 && w2_packed && b2 && y && dp, "stem: null pointer");
-  const YoloConvDesc& d = *dp;     // the stride-2 conv: h x w = size of x and of the intermediate, cin 32, cout 64
+// Which kernel a stem takes, and its grid.  stem2_kernel (producer and consumer waves, 8x16 output tiles) needs the three input
+// channels of an image and addresses x and y through buffer descriptors with 32-bit byte offsets (and keeps pixel indices in int):
+// batches whose input or output view reaches the out-of-range marker (~4 GB: 873 images of 640x640), other channel counts and
+// Tuning::stem_one_role take stem_kernel (every wave loads and computes, 16x16 tiles; CIN = 3 or 0: any count).
+struct StemPick {
+  bool two_roles;       // stem2_kernel
+  int cin;              // stem_kernel's CIN
+  int th, tw, threads;
+  long tiles, grid;     // one persistent block per CU (stem_kernel: 144 KB of static LDS each)
+};
+
+static StemPick choose_stem(int cin_real, const YoloConvDesc& d, int n_cu, const Tuning& t) {
+  const bool fits32 = (size_t)d.n * 3 * d.h * d.w * 4 < kOobOffset && (size_t)d.n * d.ho * d.wo * d.out_c_total * 2 < kOobOffset;
+  StemPick p;
+  p.two_roles = !t.stem_one_role && cin_real == 3 && fits32;
+  p.cin = cin_real == 3 ? 3 : 0;
+  p.th = p.two_roles ? 8 : 16;
+  p.tw = 16;
+  p.threads = 512;
+  p.tiles = (long)d.n * ((d.ho + p.th - 1) / p.th) * ((d.wo + p.tw - 1) / p.tw);
+  p.grid = p.tiles < n_cu ? p.tiles : n_cu;
+  return p;
+}
+
+// the checks of yolo_stem_fwd that need no pointer, then the rule
+static int plan_stem(int cin_real, const YoloConvDesc& d, StemPick* p) {
   YOLO_REQUIRE(yolo_stem_supported(cin_real, d.cin, d.cout, d.h, d.w), "stem: needs 1..8 input channels, 32 -> 64 channels");
   YOLO_REQUIRE(d.ksize == 3 && d.stride == 2 && d.pad == 1 && d.ho == (d.h - 1) / 2 + 1 && d.wo == (d.w - 1) / 2 + 1 &&
                    !d.upsample2x && d.out_dtype == YOLO_DT_BF16,
                "stem: descriptor must be the 3x3 / stride 2 / pad 1 conv");
   YOLO_REQUIRE(d.out_c_offset % 8 == 0 && d.out_c_total % 8 == 0 && d.out_c_offset + d.cout <= d.out_c_total, "stem: bad output view");
-  YOLO_REQUIRE(kpad1 >= 80 && kpad1 % 8 == 0 && d.kpad >= 288 && d.kpad % 8 == 0, "stem: bad weight packing");
+  YOLO_REQUIRE(d.kpad >= 288 && d.kpad % 8 == 0, "stem: bad weight packing");
+  *p = choose_stem(cin_real, d, yolo_device_cus(), tuning());
+  if (p->tiles > 0x7fffffffL) return yolo_set_error(YOLO_E_UNSUPPORTED, "stem: too many tiles");
+  return 0;
+}
+
+extern "C" int yolo_stem_pick(int cin_real, const YoloConvDesc* dp, char* out, int out_len) {
+  YOLO_REQUIRE(dp && out && out_len > 0, "stem_pick: bad arguments");
+  StemPick p;
+  if (const int rc = plan_stem(cin_real, *dp, &p)) return rc;
+  const char* act = dp->act == YOLO_ACT_LEAKY01 ? "leaky" : "any act";
+  if (p.two_roles) snprintf(out, out_len, "stem2<%s,%dx%d outputs> grid %ld", act, p.th, p.tw, p.grid);
+  else snprintf(out, out_len, "stem<%s,CIN %d,%dx%d outputs> grid %ld", act, p.cin, p.th, p.tw, p.grid);
+  return 0;
+}
+
+extern "C" int yolo_stem_fwd(const float* x_nchw, int cin_real, const void* w1_packed, const float* b1, int kpad1,
+                             const void* w2_packed, const float* b2, void* y, const YoloConvDesc* dp, yolo_stream_t s) {
+  YOLO_REQUIRE(x_nchw && w1_packed && b1 && w2_packed && b2 && y && dp, "stem: null pointer");
+  const YoloConvDesc& d = *dp;     // the stride-2 conv: h x w = size of x and of the intermediate, cin 32, cout 64
+  StemPick p;
+  if (const int rc = plan_stem(cin_real, d, &p)) return rc;
+  YOLO_REQUIRE(kpad1 >= 80 && kpad1 % 8 == 0, "stem: bad weight packing");
   StemArgs a;
   a.x = x_nchw;
   a.w1 = (const bf16_t*)w1_packed;
@@ -699,35 +743,16 @@ extern "C" int yolo_stem_fwd(const float* x_nchw, int cin_real, const void* w1_p
   a.kpad1 = kpad1;
   a.kpad2 = d.kpad;
   a.act = d.act;
-  static const int dbg = getenv("YOLO_STEM_DEBUG") ? atoi(getenv("YOLO_STEM_DEBUG")) : 0;
-  a.debug = dbg;
+  a.debug = tuning().stem_debug;
   a.stamps = nullptr;
   YOLO_SET_STAMPS(a);
-  static const int n_cu = [] {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-      v = 256;
-    return v;
-  }();
   hipStream_t st = (hipStream_t)s;
   const bool leaky = d.act == YOLO_ACT_LEAKY01;
-  static const bool one_role = getenv("YOLO_STEM_ONE_ROLE") != nullptr;      // A/B knob: stem_kernel (round 2)
-  // stem2_kernel addresses x and y through buffer descriptors with 32-bit byte offsets (and keeps pixel indices in int):
-  // batches whose input or output view reaches the out-of-range marker (~4 GB: 873 images of 640x640) take stem_kernel
-  const bool fits32 = (size_t)d.n * 3 * d.h * d.w * 4 < kOobOffset && (size_t)d.n * d.ho * d.wo * d.out_c_total * 2 < kOobOffset;
-  if (!one_role && cin_real == 3 && fits32) {
-    const long tiles = (long)d.n * ((d.ho + 7) / 8) * ((d.wo + 15) / 16);
-    if (tiles > 0x7fffffffL) return yolo_set_error(YOLO_E_UNSUPPORTED, "stem: too many tiles");
-    const dim3 g((unsigned)(tiles < n_cu ? tiles : n_cu)), blk(512);     // one persistent block per CU
+  const dim3 g((unsigned)p.grid), blk(p.threads);
+  if (p.two_roles) {
     if (leaky) hipLaunchKernelGGL((stem2_kernel<true>), g, blk, 0, st, a);
     else hipLaunchKernelGGL((stem2_kernel<false>), g, blk, 0, st, a);
-    return yolo_check_launch("yolo_stem_fwd");
-  }
-  const long tiles = (long)d.n * ((d.ho + 15) / 16) * ((d.wo + 15) / 16);
-  if (tiles > 0x7fffffffL) return yolo_set_error(YOLO_E_UNSUPPORTED, "stem: too many tiles");
-  const long grid = tiles < n_cu ? tiles : n_cu;       // one persistent block per CU (144 KB LDS each)
-  const dim3 g((unsigned)grid), blk(512);
-  if (cin_real == 3) {
+  } else if (p.cin == 3) {
     if (leaky) hipLaunchKernelGGL((stem_kernel<true, 3>), g, blk, 0, st, a);
     else hipLaunchKernelGGL((stem_kernel<false, 3>), g, blk, 0, st, a);
   } else {

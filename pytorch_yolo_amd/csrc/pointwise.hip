@@ -414,28 +414,44 @@ extern "C" int yolo_channel_shuffle2_f32_fwd(const float* a, const float* b, flo
   return channel_shuffle2<float>("yolo_channel_shuffle2_f32_fwd", a, b, y, n, h, w, half, c_slot, a_c_total, a_c_offset, b_c_total, b_c_offset, y_c_total, y_c_offset, s);
 }
 
+// Which form an SPP block takes: whole 64-channel lines in LDS where they fit (Tuning::spp_no_lines: never), the 8-channel form while
+// its four planes fit 64 KB, else three direct pools (same results, more L2 traffic).
+enum class SppForm { kLines, kEightChannels, kThreePools };
+struct SppPick {
+  SppForm form;
+  int threads;
+  unsigned grid;
+  size_t lds;
+};
+static SppPick choose_spp(int n, int h, int w, int c, const Tuning& t) {
+  const size_t lds_lines = (size_t)2 * h * w * 128, lds = (size_t)4 * h * w * 16;
+  if (c % 64 == 0 && lds_lines <= 128 * 1024 && !t.spp_no_lines) return {SppForm::kLines, 512, (unsigned)(n * (c / 64)), lds_lines};
+  if (lds <= 64 * 1024) return {SppForm::kEightChannels, 256, (unsigned)(n * (c / 8)), lds};
+  return {SppForm::kThreePools, 0, 0, 0};
+}
+
 extern "C" int yolo_spp_fwd(void* buf, int n, int h, int w, int c, yolo_stream_t s) {
   YOLO_REQUIRE(buf && n > 0 && h > 0 && w > 0 && c > 0 && c % 8 == 0, "spp: bad arguments");
-  const size_t lds_lines = (size_t)2 * h * w * 128;
-  static const bool no_lines = getenv("YOLO_SPP_NO_LINES") != nullptr;     // A/B knob: the 8-channel form for every shape
-  if (c % 64 == 0 && lds_lines <= 128 * 1024 && !no_lines) {
-    static std::atomic<uint64_t> lds_set{0};               // per device (common.h)
-    if (const int rc = yolo_max_dyn_lds((const void*)spp_lines_kernel, 128 * 1024, lds_set, "spp")) return rc;
-    hipLaunchKernelGGL(spp_lines_kernel, dim3((unsigned)(n * (c / 64))), dim3(512), lds_lines, (hipStream_t)s, (bf16_t*)buf, h, w, c);
-    return yolo_check_launch("yolo_spp_fwd");
+  const SppPick p = choose_spp(n, h, w, c, tuning());
+  switch (p.form) {
+    case SppForm::kLines: {
+      static std::atomic<uint64_t> lds_set{0};               // per device (common.h)
+      if (const int rc = yolo_max_dyn_lds((const void*)spp_lines_kernel, 128 * 1024, lds_set, "spp")) return rc;
+      hipLaunchKernelGGL(spp_lines_kernel, dim3(p.grid), dim3(p.threads), p.lds, (hipStream_t)s, (bf16_t*)buf, h, w, c);
+      break;
+    }
+    case SppForm::kEightChannels:
+      hipLaunchKernelGGL(spp_kernel, dim3(p.grid), dim3(p.threads), p.lds, (hipStream_t)s, (bf16_t*)buf, h, w, c);
+      break;
+    case SppForm::kThreePools:
+      for (int lvl = 0; lvl < 3; ++lvl) {
+        const int k = 5 + 4 * lvl;
+        int rc = yolo_maxpool_fwd(buf, buf, n, h, w, c, 4 * c, 3 * c, h, w, 4 * c, lvl * c, k, 1, k / 2, 1, s);
+        if (rc) return rc;
+      }
+      return 0;
   }
-  const size_t lds = (size_t)4 * h * w * 16;
-  if (lds <= 64 * 1024) {
-    hipLaunchKernelGGL(spp_kernel, dim3((unsigned)(n * (c / 8))), dim3(256), lds, (hipStream_t)s, (bf16_t*)buf, h, w, c);
-    return yolo_check_launch("yolo_spp_fwd");
-  }
-  // large feature maps: three direct pools (same results, more L2 traffic)
-  for (int lvl = 0; lvl < 3; ++lvl) {
-    const int k = 5 + 4 * lvl;
-    int rc = yolo_maxpool_fwd(buf, buf, n, h, w, c, 4 * c, 3 * c, h, w, 4 * c, lvl * c, k, 1, k / 2, 1, s);
-    if (rc) return rc;
-  }
-  return 0;
+  return yolo_check_launch("yolo_spp_fwd");
 }
 
 // Strip form: one thread = 8 channels of R vertically adjacent output pixels.  Its 72 weights are read once and stay in
@@ -527,10 +543,9 @@ static int launch_dw_strip(const bf16_t* x, const float* w, const float* bias, b
   return yolo_check_launch("yolo_dwconv3x3_fwd");
 }
 
-static const int dw_debug = [] {      // YOLO_DWCONV_DEBUG (tuning only: the kDw* bits of tuning.h)
-  const char* e = getenv("YOLO_DWCONV_DEBUG");
-  return e ? atoi(e) : 0;
-}();
+// Output rows per thread of the depthwise 3x3: strips of 8 as shipped (0.040 -> 0.028 ms on the 26x26x384 maps of 64 images, 4-row
+// strips 0.032; also on 13x13: 13 -> 16 rows), 4 under kDwFourRows, 1 = the one-pixel kernel under kDwOnePixel (tuning only)
+static int choose_dw_rows(const Tuning& t) { return (t.dwconv & kDwOnePixel) ? 1 : (t.dwconv & kDwFourRows) ? 4 : 8; }
 
 extern "C" int yolo_dwconv3x3_fwd(const void* x, const float* w, const float* bias, void* y, int n, int h, int w_, int c,
                                   int in_c_total, int in_c_offset, int ho, int wo, int out_c_total, int out_c_offset,
@@ -541,20 +556,20 @@ extern "C" int yolo_dwconv3x3_fwd(const void* x, const float* w, const float* bi
   YOLO_REQUIRE(ho == (h + 2 - 3) / stride + 1 && wo == (w_ + 2 - 3) / stride + 1, "dwconv: bad output size");
   YOLO_REQUIRE(in_c_total % 8 == 0 && in_c_offset % 8 == 0 && out_c_total % 8 == 0 && out_c_offset % 8 == 0,
                "dwconv: views must be 8-channel aligned");
-  if (!(dw_debug & kDwOnePixel)) {
-    const bf16_t* xb = (const bf16_t*)x;
-    bf16_t* yb = (bf16_t*)y;
-    hipStream_t st = (hipStream_t)s;
-    if (dw_debug & kDwFourRows)
+  const bf16_t* xb = (const bf16_t*)x;
+  bf16_t* yb = (bf16_t*)y;
+  hipStream_t st = (hipStream_t)s;
+  switch (choose_dw_rows(tuning())) {
+    case 8:
+      return stride == 1 ? launch_dw_strip<1, 8>(xb, w, bias, yb, n, h, w_, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, act, st)
+                         : launch_dw_strip<2, 8>(xb, w, bias, yb, n, h, w_, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, act, st);
+    case 4:
       return stride == 1 ? launch_dw_strip<1, 4>(xb, w, bias, yb, n, h, w_, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, act, st)
                          : launch_dw_strip<2, 4>(xb, w, bias, yb, n, h, w_, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, act, st);
-    // 8-row strips: 0.040 -> 0.028 ms on the 26x26x384 maps of 64 images (4-row strips 0.032), also on 13x13 (13 -> 16 rows)
-    return stride == 1 ? launch_dw_strip<1, 8>(xb, w, bias, yb, n, h, w_, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, act, st)
-                       : launch_dw_strip<2, 8>(xb, w, bias, yb, n, h, w_, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, act, st);
   }
   const long total = (long)n * ho * wo * (c / 8);
-  hipLaunchKernelGGL(dwconv3x3_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, w, bias,
-                     (bf16_t*)y, h, w_, c, in_c_total, in_c_offset, ho, wo, out_c_total, out_c_offset, stride, act, total);
+  hipLaunchKernelGGL(dwconv3x3_kernel, dim3(blocks_for(total)), dim3(256), 0, st, xb, w, bias, yb, h, w_, c, in_c_total, in_c_offset, ho,
+                     wo, out_c_total, out_c_offset, stride, act, total);
   return yolo_check_launch("yolo_dwconv3x3_fwd");
 }
 

@@ -11,6 +11,16 @@ int yolo_set_error(int code, const char* fmt, ...) {
   return code;
 }
 
+int yolo_device_cus() {
+  static const int n_cu = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+      v = 256;
+    return v;
+  }();
+  return n_cu;
+}
+
 extern "C" const char* yolo_last_error(void) { return g_err; }
 extern "C" int yolo_abi_version(void) { return 2; }   // 2 (round 5): YoloOp's former pad fields carry head_filter_conf / head_filter_min_wh, YoloPipeStep added
 extern "C" int yolo_abi_sizeof(int which) {

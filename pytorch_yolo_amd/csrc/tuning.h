@@ -1,35 +1,37 @@
 // Every tuning knob of libyolo_hip.so, in one place.  Knobs exist for tests, timing ablations and A/B runs; the shipped rules are
 // what the library does with all of them at their defaults.
 //
-// Five words are process-wide state: read from the environment at first use, changed afterwards by yolo_set_tuning(knob, value)
-// (include/yolo_hip.h), which returns the previous value.
-//   knob 0  YOLO_CONV_VARIANT   Tuning::variant      >= 0: tile configuration of the gather kernel by number (choose_igemm in
-//                                                    conv_igemm.hip), no other kernel family
-//   knob 1  YOLO_CONV_DEBUG     Tuning::conv_debug   kCd* bits
-//   knob 2  YOLO_CONV_PP        Tuning::families     kFam* bits
-//   knob 3  YOLO_RESUNIT_DEBUG  Tuning::resunit      kRu* bits
-//   knob 4  YOLO_MBCONV_DEBUG   Tuning::mbconv       kMb* bits
-// The others are read from the environment where they are used, once per process:
-//   YOLO_STEM_DEBUG       conv_stem.hip           kStem* bits
-//   YOLO_STEM_ONE_ROLE    conv_stem.hip           set: stem_kernel (every wave loads and computes) instead of stem2_kernel
-//   YOLO_MBWIDE_DEBUG     conv_mbwide.hip         kMbw* bits
-//   YOLO_MBWIDE_FORM      conv_mbwide.hip         1 = 13x13 tiles whenever they fit, 2 = 7x7 tiles always
-//   YOLO_DWCONV_DEBUG     pointwise.hip           kDw* bits
-//   YOLO_SPP_NO_LINES     pointwise.hip           set: the 8-channel SPP form for every shape
-//   YOLO_RESUNIT_STAGGER  conv_resunit_t20.hip    start offset between the workgroups of a CU (tuning only)
+// Twelve words are process-wide state: read from the environment at the first use of tuning(), changed afterwards by
+// yolo_set_tuning(knob, value) (include/yolo_hip.h), which returns the previous value.
+//   knob 0   YOLO_CONV_VARIANT     Tuning::variant          >= 0: tile configuration of the gather kernel by number (choose_igemm in
+//                                                           conv_igemm.hip), no other kernel family
+//   knob 1   YOLO_CONV_DEBUG       Tuning::conv_debug       kCd* bits
+//   knob 2   YOLO_CONV_PP          Tuning::families         kFam* bits
+//   knob 3   YOLO_RESUNIT_DEBUG    Tuning::resunit          kRu* bits
+//   knob 4   YOLO_MBCONV_DEBUG     Tuning::mbconv           kMb* bits
+//   knob 5   YOLO_STEM_DEBUG       Tuning::stem_debug       kStem* bits
+//   knob 6   YOLO_STEM_ONE_ROLE    Tuning::stem_one_role    != 0 (the variable: set): stem_kernel (every wave loads and computes) instead
+//                                                           of stem2_kernel
+//   knob 7   YOLO_MBWIDE_DEBUG     Tuning::mbwide_debug     kMbw* bits
+//   knob 8   YOLO_MBWIDE_FORM      Tuning::mbwide_form      1 = 13x13 tiles whenever they fit, 2 = 7x7 tiles always
+//   knob 9   YOLO_DWCONV_DEBUG     Tuning::dwconv           kDw* bits
+//   knob 10  YOLO_SPP_NO_LINES     Tuning::spp_no_lines     != 0 (the variable: set): the 8-channel SPP form for every shape
+//   knob 11  YOLO_RESUNIT_STAGGER  Tuning::resunit_stagger  start offset between the workgroups of a CU (tuning only)
 // A bit without a name below is tested nowhere.  Of the named ones, the recipes of tests/_exact_cases.py launch the gather-kernel
 // instances behind knob 0 (variants 0, 3, 5, 7, 8, 9, 10, 11) and behind kCdNoLdsEpilogue, kCdNoLoaderWaves, kCd256x256EightWaves,
 // kCdMfma32x32, kCdFourWaves, kCdLoadersTwoStages, kCd64x64TwoStages and kCdStreamFirstForm, and compare them bit for bit
 // (tests/test_conv_exact_gpu.py); kFamT20Always / kFamT20Never and kFamStreamAlways / kFamStreamNever have their cases there and in
 // tests/test_gpu_parity.py.  The form bits of knobs 3 and 4 (kRuGeneric64, kRuT20Always, kRuT20Never, kMbStripForm) select the fused
-// kernels of the chained bit-exact cases (tests/_exact_cases.py, tests/test_fused_exact_gpu.py); kMbStripForm also runs, with the
-// shipped rules of knob 3, on the real activation scales in tests/test_gpu_parity.py.  kDwOnePixel and kDwFourRows are read when the
-// library loads, so tests/test_pointwise_exact_gpu.py starts one fresh interpreter per value and compares the depthwise 3x3 table
-// of tests/_exact_cases.py bit for bit in each.  The ablation bits give wrong results by design and have no test.
+// kernels of the chained bit-exact cases (tests/_exact_cases.py, tests/test_fused_exact_gpu.py), which ask yolo_resunit_pick /
+// yolo_mbconv_pick for the kernel before every launch; kMbStripForm also runs, with the shipped rules of knob 3, on the real
+// activation scales in tests/test_gpu_parity.py.  tests/test_pointwise_exact_gpu.py sets kDwOnePixel and kDwFourRows in turn and
+// compares the depthwise 3x3 table of tests/_exact_cases.py bit for bit under each.  The ablation bits give wrong results by design
+// and have no test.
 #pragma once
 
 struct Tuning {
   int variant = -1, conv_debug = 0, families = 0, resunit = 0, mbconv = 0;
+  int stem_debug = 0, stem_one_role = 0, mbwide_debug = 0, mbwide_form = 0, dwconv = 0, spp_no_lines = 0, resunit_stagger = 0;
 };
 Tuning& tuning();   // conv_igemm.hip
 
@@ -92,7 +94,7 @@ enum : int {
   kMbFullBarriers = 256,           // tile form: __syncthreads() where the kernel waits for LDS only
 };
 
-// YOLO_STEM_DEBUG: timing ablations of the fused stem
+// YOLO_STEM_DEBUG / knob 5: timing ablations of the fused stem
 enum : int {
   kStemNoLoads = 1,                // no input loads
   kStemNoPhaseA = 2,               // no phase A
@@ -101,7 +103,7 @@ enum : int {
   kStemProducersOnly = 64,         // the producer waves alone (stem2_kernel only)
 };
 
-// YOLO_MBWIDE_DEBUG: timing ablations of the wide MBConv form
+// YOLO_MBWIDE_DEBUG / knob 7: timing ablations of the wide MBConv form
 enum : int {
   kMbwNoExpand = 2,                // no expand phase
   kMbwNoDepthwise = 4,             // no depthwise phase
@@ -109,7 +111,7 @@ enum : int {
   kMbwNoWeightDma = 16,            // no weight DMAs after chunk 0
 };
 
-// YOLO_DWCONV_DEBUG (tuning only): both forms give the bits of the shipped 8-row strips
+// YOLO_DWCONV_DEBUG / knob 9 (tuning only): both forms give the bits of the shipped 8-row strips
 enum : int {
   kDwOnePixel = 1,                 // the one-pixel form
   kDwFourRows = 2,                 // strips of 4 rows instead of 8

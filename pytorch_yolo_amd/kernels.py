@@ -13,7 +13,7 @@ from . import _lib
 from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU6, DT_BF16, DT_F16, DT_F32, YoloConvDesc, YoloMbconvDesc,
                    check, load)
 
-__all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pick", "stem", "resunit", "resunit_supported", "resunit_form", "maxpool", "spp", "dwconv3x3", "dwconv", "se", "se_workspace_bytes", "mbconv", "mbconv_supported", "mbconv_form", "pack_mbconv", "conv3x3_pool", "conv3x3_pool_supported", "conv2d_splitk", "conv2d_splitk_plan", "decode", "head_decode", "head_decode_supported",
+__all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pick", "stem", "stem_pick", "resunit", "resunit_supported", "resunit_form", "resunit_pick", "maxpool", "spp", "dwconv3x3", "dwconv", "se", "se_workspace_bytes", "mbconv", "mbconv_supported", "mbconv_form", "mbconv_pick", "pack_mbconv", "conv3x3_pool", "conv3x3_pool_supported", "conv2d_splitk", "conv2d_splitk_plan", "decode", "head_decode", "head_decode_supported",
            "nms_merge", "nms_styled", "nms_styled_compact", "loss_workspace_bytes", "build_targets_fwd", "loss_fwd", "loss_bwd", "LOSS_REC_WORDS", "coco_workspace_bytes", "coco_match_fwd", "coco_accumulate_fwd", "coco_sweep_chunk", "coco_max_gt",
            "COCO_T", "COCO_R", "COCO_A", "COCO_M", "pack_conv_weight", "roundup", "run_ops"]
 
@@ -298,6 +298,13 @@ def conv2d_splitk(x, w_packed, bias, y, desc: YoloConvDesc, splits, workspace, c
     return y
 
 
+def stem_pick(cin_real: int, desc: YoloConvDesc) -> str:
+    """Name + grid of the kernel yolo_stem_fwd would launch under the current tuning (no launch, works without a GPU)."""
+    buf = C.create_string_buffer(256)
+    check(load().yolo_stem_pick(cin_real, C.byref(desc), buf, 256), "stem_pick")
+    return buf.value.decode()
+
+
 def stem(x_nchw, cin_real, w1_packed, b1, kpad1, w2_packed, b2, y, desc: YoloConvDesc):
     """conv3x3/s1 (cin_real -> 32) + conv3x3/s2 (32 -> 64) straight from the float32 NCHW batch (yolo_stem_fwd)."""
     _need_cuda(x_nchw, w1_packed, b1, w2_packed, b2, y)
@@ -313,6 +320,13 @@ def resunit_supported(c: int, h: int, w: int) -> bool:
 def resunit_form(c: int, n: int, h: int, w: int) -> int:
     """0 not supported, 1 generic 16x16-tile kernel, 2 persistent 64-channel kernel, 3 the 20-pixel-wide tile kernels (yolo_resunit_form)."""
     return int(load().yolo_resunit_form(c, n, h, w))
+
+
+def resunit_pick(desc: YoloConvDesc, has_preadd=False) -> str:
+    """Name + grid of the kernel yolo_resunit_fwd would launch under the current tuning (no launch, works without a GPU)."""
+    buf = C.create_string_buffer(256)
+    check(load().yolo_resunit_pick(C.byref(desc), int(has_preadd), buf, 256), "resunit_pick")
+    return buf.value.decode()
 
 
 def resunit(x, w1_packed, b1, w2_packed, b2, y, desc: YoloConvDesc, kpad1: int, cout_pad1: int, y_preadd=None):
@@ -425,6 +439,19 @@ def pack_mbconv(w_exp, b_exp, w_dw, b_dw, w_proj, b_proj, stride: int = 1):
     bp = torch.zeros(cop, dtype=torch.float32)
     bp[:cout] = b_proj.detach().float().cpu()
     return we, be, wd.contiguous(), bd, wp.to(torch.bfloat16).contiguous(), bp
+
+
+def mbconv_pick(*, n, h, w, cin, hidden, cout, stride, in_view=None, out_view=None, has_res=None) -> str:
+    """Name + grid of the kernel yolo_mbconv_fwd would launch under the current tuning (no launch, works without a GPU); dense views
+    and the residual of a stride-1 block with cin == cout unless said otherwise."""
+    in_view, out_view = in_view or (cin, 0), out_view or (cout, 0)
+    has_res = (stride == 1 and cin == cout) if has_res is None else has_res
+    d = YoloMbconvDesc(n=n, h=h, w=w, cin=cin, in_c_total=in_view[0], in_c_offset=in_view[1], hidden=hidden, cout=cout,
+                       out_c_total=out_view[0], out_c_offset=out_view[1], stride=stride,
+                       has_expand=int(hidden != cin), has_res=int(has_res))
+    buf = C.create_string_buffer(256)
+    check(load().yolo_mbconv_pick(C.byref(d), buf, 256), "mbconv_pick")
+    return buf.value.decode()
 
 
 def mbconv(x, packed, y, *, n, h, w, cin, hidden, cout, in_view, out_view, stride, has_res):

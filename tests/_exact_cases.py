@@ -12,16 +12,16 @@ The second half holds the chained cases of the kernels that fuse several layers 
 their references' guards and sensitivity checks, tests/test_fused_exact_gpu.py launches them).  Forced-shape rules there:
   * fused residual units: every map passes yolo_resunit_supported (>= 80x80 pixels, 16x16 tiles covering >= 85 %).  The form bits of
     knob 3 only choose AMONG kernels that compute any supported unit: kRuT20Always drops the tile-count and cover conditions of
-    resunit_t20_applies (a speed rule), kRuT20Never / kRuGeneric64 fall back to the generic 16x16-tile kernel.  No bit lifts a host
-    check.  The library has no query that names the kernel a unit takes (the pick mode is reachable through yolo_conv2d_pick only), so
-    the cases rely on the knob; the default-rule case is checked against yolo_resunit_form.
-  * inverted residuals: knob 4 bit kMbStripForm ASKS for the row-strip form; launch_strip (csrc/conv_mbconv.hip) declines a block it
-    cannot hold and the tile form runs instead, silently.  strip_takes() below repeats its conditions, and every "strip" case must
-    pass it: at stride 1 the strip form holds at most 128 padded hidden channels, at stride 2 its LDS rings end at 128 as well - so the
-    144-hidden blocks of test_fused_inverted_residual never reach it, and the strip row "hidden not a multiple of 32" is a block of its
-    own (24-80-24).  The wide form's tiling follows from the shape alone (yolo_mbwide_launch): stride 2 -> 7x7; stride 1 -> 13x13 when
-    cin <= 96, cout <= 128 and there are >= 192 tiles of 13x13, else 7x7.
-  * the stem takes stem2_kernel for 3 input channels and stem_kernel otherwise; conv + pool has one kernel per (cin, cout) pair."""
+    choose_resunit (csrc/conv_resunit.hip; a speed rule), kRuT20Never / kRuGeneric64 fall back to the generic 16x16-tile kernel.  No
+    bit lifts a host check.
+  * inverted residuals: knob 4 bit kMbStripForm ASKS for the row-strip form; choose_mbconv (csrc/conv_mbconv.hip) gives a block the
+    strip form cannot hold to the tile form.  At stride 1 the strip form holds at most 128 padded hidden channels, at stride 2 its LDS
+    rings end at 128 as well - so the 144-hidden blocks of test_fused_inverted_residual never reach it, and the strip row "hidden not
+    a multiple of 32" is a block of its own (24-80-24).  The wide form's tiling follows from the shape (choose_mbwide): stride 2 ->
+    7x7; stride 1 -> 13x13 when cin <= 96, cout <= 128 and there are >= 192 tiles of 13x13, else 7x7.
+  * the stem takes stem2_kernel for 3 input channels and stem_kernel otherwise; conv + pool has one kernel per (cin, cout) pair.
+No case rests on these sentences: yolo_resunit_pick / yolo_mbconv_pick / yolo_stem_pick name the kernel, tile and grid a case takes under
+its knob, and both test files compare that with the row (*_pick_wanted below), the GPU one right before each launch."""
 import os
 import re
 
@@ -222,36 +222,45 @@ MBCONV_CASES = [
 MBCONV_SEED = 301
 
 
-def strip_takes(cin, hidden, cout, stride):
-    """launch_strip's conditions (csrc/conv_mbconv.hip, MbStrip<S>, strip_lds_bytes): does the row-strip form hold the block?
-    A copy BY HAND - the library has no query for it - of MbStrip's constants (25 output columns per segment, NE = 384, NDW = 512,
-    kXStride = 96, five x-ring rows), launch_strip's conditions and strip_lds_bytes' sum.  Whoever changes one of those in the C++
-    changes it here: if the two drift apart, a "strip" case can run the tile form and nothing will show it."""
-    expand = hidden != cin
-    ce, cop = (hidden + 31) // 32 * 32, (cout + 15) // 16 * 16
-    iw = 25 * stride + 3
-    iwf = (iw + 15) // 16
-    iws, iwe = iwf * 16, 40 if stride == 1 else (iw + 7) // 8 * 8
-    re_, rne, ne, ndw = 4 if stride == 1 else 5, 6 if stride == 1 else 8, 384, 512
-    npx = (3 * iw * 4 + ne - 1) // ne
-    if cin % 8 or cin > 32 or 3 * iw * (cin // 8) > npx * ne or cop > 64 or ((ce // 2) * 7 if stride == 1 else ce // 4) > ndw:
-        return False
-    dstride = ce * 2
-    while dstride % 256 not in (96, 160):
-        dstride += 16
-    estride = ce * 2 + (8 if expand else 0)
-    lds = (5 * iws * 96 if expand else 0) + (re_ if expand else rne) * iwe * estride + 2 * 32 * dstride + (ce * 96 if expand else 0) + \
-        cop * dstride + (ce + cop) * 4 + (3 * iwf * (ce // 16) * 4 if expand else 0)
-    return lds <= 160 * 1024
+# ---- what a chained case must launch: its descriptor, and the pick string (yolo_resunit_pick / _stem_pick / _mbconv_pick) up to the grid
+ACTS = {"leaky": 1, "relu6": 2}                                # YOLO_ACT_LEAKY01, YOLO_ACT_RELU6
 
 
-def wide_tiling(n, h, w, cin, cout, stride):
-    """yolo_mbwide_launch's choice (csrc/conv_mbwide.hip) up to its LDS condition, which every 13x13 case of the table meets.
-    A copy by hand as well (no query names the tiling): keep it in step with the C++ rule, LDS condition included if a 13x13 case
-    near that limit is ever added."""
-    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-    t13 = n * ((ho + 12) // 13) * ((wo + 12) // 13)
-    return "wide13" if stride == 1 and cin <= 96 and (cout + 15) // 16 * 16 <= 128 and t13 >= 192 else "wide7"
+def unit_desc(u, use_aux=False, kpad=None, cout_pad=None):
+    from pytorch_yolo_amd import kernels as K
+    n, h, w, c, act = u["shape"]
+    return K.conv_desc(n=n, h=h, w=w, cin=c // 2, in_c_total=c + 16, in_c_offset=8, cout=c, out_c_total=c + 16, out_c_offset=8, ksize=3, stride=1,
+                       act=ACTS[act], kpad=kpad or (9 * (c // 2) + 63) // 64 * 64, cout_pad=cout_pad or (c + 127) // 128 * 128,
+                       aux=(c + 16, 8) if use_aux else (0, 0))
+
+
+def unit_pick_wanted(u):
+    c, px = u["c"], u["tile"][0] * u["tile"][1]
+    return {"resunit64_persistent": "resunit64<%dpx x 64 couts, 8 waves, persistent> grid " % px, "resunit_generic16": "resunit<C %d, %dpx x %d couts, 8 waves> grid " % (c, px, c),
+            "resunit64_t20": "resunit64_t20<%dpx x 64 couts, 4 waves> grid " % px, "resunit_t20w": "resunit_t20w<C %d, %dpx x %d couts, 4 waves> grid " % (c, px, c)}[
+        u["kernel"].split("_c")[0].split("_w101")[0].split("_relu6")[0]]
+
+
+def stem_desc(shape, kpad=320, cout_pad=128):
+    from pytorch_yolo_amd import kernels as K
+    n, cin, h, w, act = shape
+    return K.conv_desc(n=n, h=h, w=w, cin=32, in_c_total=32, in_c_offset=0, cout=64, out_c_total=80, out_c_offset=8, ksize=3, stride=2,
+                       act=ACTS[act], kpad=kpad, cout_pad=cout_pad)
+
+
+def stem_pick_wanted(kernel, shape, tile):
+    return ("stem2<%s,%dx%d outputs> grid " if kernel == "stem2" else "stem<%s,CIN 0,%dx%d outputs> grid ") % (("leaky" if shape[4] == "leaky" else "any act",) + tile)
+
+
+def mbconv_pick(shape):
+    from pytorch_yolo_amd import kernels as K
+    n, h, w, cin, hidden, cout, stride = shape
+    return K.mbconv_pick(n=n, h=h, w=w, cin=cin, hidden=hidden, cout=cout, stride=stride, in_view=(cin + 16, 8), out_view=(cout + 8, 4))
+
+
+def mbconv_pick_wanted(form, shape, tile):
+    expand = "expand" if shape[4] != shape[3] else "no expand"
+    return {"tile": "mbconv<S %d,%dx%d," + expand + ",", "strip": "mbstrip<S %d," + expand + ",%d rows x %d> grid "}.get(form, "mbwide<S %d,%dx%d,") % ((shape[6],) + tile)
 
 
 # conv3x3 + MaxPool2d(2, 2) (csrc/conv_small.hip): every (cin, cout) pair with the pool, at odd sizes - the pool takes the floor, the

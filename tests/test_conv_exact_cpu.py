@@ -2,6 +2,8 @@
 words - that yolo_conv2d_pick answers with that instance, the test tables name exactly the instances csrc/conv_igemm.hip builds, and
 every exact case's reference determines every bit and exercises the rounding (tests/helpers.py::exact_conv_reference rejects it
 otherwise).  tests/test_conv_exact_gpu.py launches the same tables."""
+import contextlib
+
 import pytest
 import torch
 
@@ -28,21 +30,22 @@ def exact_desc(shape, view="v8", dtype=torch.bfloat16, in_place_res=False):
                        aux=(K.roundup(cout, 8) + 8, 8) if use_aux else (0, 0))
 
 
-class tuning:
+@contextlib.contextmanager
+def knob(i, value):
+    """with knob(i, value): yolo_set_tuning(i, value), and the previous value on the way out."""
+    old = load().yolo_set_tuning(i, value)
+    try:
+        yield
+    finally:
+        load().yolo_set_tuning(i, old)
+
+
+def tuning(knob0=-1, knob1=0, knob2=0):
     """with tuning(knob0, knob1, knob2): the three conv tuning words set, and restored on the way out."""
-
-    def __init__(self, knob0=-1, knob1=0, knob2=0):
-        self.want = (knob0, knob1, knob2)
-
-    def __enter__(self):
-        lib = load()
-        self.old = [lib.yolo_set_tuning(i, v) for i, v in enumerate(self.want)]
-
-    def __exit__(self, *exc):
-        lib = load()
-        for i, v in enumerate(self.old):
-            lib.yolo_set_tuning(i, v)
-        return False
+    stack = contextlib.ExitStack()
+    for i, v in enumerate((knob0, knob1, knob2)):
+        stack.enter_context(knob(i, v))
+    return stack
 
 
 def epilogue_of(name):

@@ -1,14 +1,16 @@
 """Host-side half of the bit-exact tests of the fused multi-conv kernels (no GPU): every chained case of tests/_exact_cases.py has a
 reference that determines every bit and exercises the rounding (tests/helpers.py::exact_chain_reference rejects it otherwise - the GPU
 file can then never meet a rejected case), the reference alone tells a subtly wrong kernel from a right one (one perturbed reference per
-failure class, each must differ from the true one in every case it applies to), and the cases reach the forms they name wherever a host
-rule can be asked without a GPU.  tests/test_fused_exact_gpu.py launches the same tables and takes the tensors from the same cache."""
+failure class, each must differ from the true one in every case it applies to), and every case takes the kernel it names, with the tile
+its row says: the library's pick functions answer that without a GPU.  tests/test_fused_exact_gpu.py launches the same tables and
+takes the tensors from the same cache."""
 import pytest
 import torch
 
 import _exact_cases as E
 from helpers import exact_chain, exact_chain_reference, exact_conv
 from pytorch_yolo_amd import kernels as K
+from test_conv_exact_cpu import knob
 
 UNIT_IDS = [u["kernel"] for u in E.UNIT_CASES]
 STEM_IDS = ["%s_n%d_c%d_%dx%d_%s" % ((k,) + s) for k, s, _, _ in E.STEM_CASES]
@@ -101,7 +103,7 @@ def test_reference_notices_an_intermediate_padded_with_the_activated_bias(cid, k
     assert bool(((bad[:, 2] == 0) | (bad[:, 2] == h - 1) | (bad[:, 3] == 0) | (bad[:, 3] == w - 1)).all())
 
 
-# ---- the forms the cases name, where a host rule answers without a GPU --------------------------------------------------------------
+# ---- the forms the cases name: the library's own answer (yolo_resunit_pick / yolo_stem_pick / yolo_mbconv_pick), no GPU ----------------
 def test_unit_cases_reach_their_forms():
     for u in E.UNIT_CASES:
         n, h, w, c, act = u["shape"]
@@ -114,6 +116,9 @@ def test_unit_cases_reach_their_forms():
             assert u["kernel"] == "resunit64_persistent" and n * -(-h // 16) * -(-w // 16) > 256
         assert ("t20" in u["kernel"]) == bool(u["knob3"] & E.RU_T20_ALWAYS)
         assert ("generic16" in u["kernel"]) == bool(u["knob3"] & (E.RU_T20_NEVER | E.RU_GENERIC64))
+        with knob(3, u["knob3"]):                        # the kernel the name says, with the tile the row says
+            for use_aux in (False, True):
+                assert K.resunit_pick(E.unit_desc(u, use_aux), use_aux).startswith(E.unit_pick_wanted(u)), u["kernel"]
     kernels = {(u["kernel"].split("_w101")[0].split("_relu6")[0]) for u in E.UNIT_CASES}
     assert kernels == {"resunit64_persistent", "resunit_generic16_c64", "resunit64_t20", "resunit_generic16_c128", "resunit_t20w_c128",
                        "resunit_generic16_c256", "resunit_t20w_c256"}
@@ -129,31 +134,35 @@ def test_stem_cases_cover_both_kernels_and_partial_tiles():
         assert kernel == ("stem2" if cin == 3 else "stem_one_role")
         ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         assert ho % tile[0] and wo % tile[1]
+        d = E.stem_desc((n, cin, h, w, act))
+        assert K.stem_pick(cin, d).startswith(E.stem_pick_wanted(kernel, (n, cin, h, w, act), tile))
+        with knob(6, 1):                                 # YOLO_STEM_ONE_ROLE: stem_kernel for three channels too
+            assert K.stem_pick(cin, d).startswith("stem<") and ",16x16 outputs>" in K.stem_pick(cin, d)
     assert any(s[4] == "relu6" for _, s, _, _ in E.STEM_CASES)
 
 
 def test_mbconv_cases_reach_their_forms():
     rows = {"tile": set(), "strip": set()}
-    for form, (n, h, w, cin, hidden, cout, stride), tile in E.MBCONV_CASES:
+    for form, shape, tile in E.MBCONV_CASES:
+        n, h, w, cin, hidden, cout, stride = shape
         assert K.mbconv_supported(cin, hidden, cout, stride)
-        want = K.mbconv_form(cin, hidden, cout, stride)
+        assert K.mbconv_form(cin, hidden, cout, stride) == (1 if form in ("tile", "strip") else 2)
+        with knob(4, E.MB_STRIP if form == "strip" else 0):          # the kernel the form says, with the tile the row says
+            assert E.mbconv_pick(shape).startswith(E.mbconv_pick_wanted(form, shape, tile)), (form, shape, E.mbconv_pick(shape))
         if form in ("tile", "strip"):
-            assert want == 1
-            assert form == "tile" or E.strip_takes(cin, hidden, cout, stride), (cin, hidden, cout, stride)
             rows[form] |= {name for name, hit in (("no expand", hidden == cin), ("stride 2", stride == 2), ("residual", stride == 1 and cin == cout),
                                                   ("hidden % 32", hidden % 32 != 0), ("cout % 16", cout % 16 != 0)) if hit}
-        else:
-            assert want == 2 and E.wide_tiling(n, h, w, cin, cout, stride) == form
         assert form.startswith("wide") or h * w * cin <= 100000
     assert rows["tile"] == rows["strip"] == {"no expand", "stride 2", "residual", "hidden % 32", "cout % 16"}
     assert {f for f, _, _ in E.MBCONV_CASES} == {"tile", "strip", "wide13", "wide7"}
-    # the strip form declines the 144-hidden blocks of the tolerance test (the reason the table has 24-80-24)
-    assert not E.strip_takes(24, 144, 24, 1) and not E.strip_takes(24, 144, 32, 2) and not E.strip_takes(32, 192, 32, 1)
-    # the tile form's persistent loop: launch_nt starts min(tiles, slots) workgroups, slots = 1024 / 512 / 256 for <= 40 / <= 80 / more
-    # KB of LDS.  24-144-24 at stride 1 takes 8x8 tiles (10x10 inputs, 112 padded; 160 padded hidden channels, 352-byte rows) and
-    # 112 * 96 + 112 * 328 + 64 * 352 + 160 * 96 + 32 * 352 + 352 * 4 = 98 048 bytes: 256 slots, one workgroup per CU
-    (n, h, w), = [s[:3] for f, s, _ in E.MBCONV_CASES if f == "tile" and s[3:] == (24, 144, 24, 1) and s[0] > 1]
-    assert n * -(-h // 8) * -(-w // 8) == 320 > 256
+    with knob(4, E.MB_STRIP):        # the 144- / 192-hidden blocks of the tolerance test take the tile form then too (hence 24-80-24)
+        for shape in ((1, 23, 19, 24, 144, 24, 1), (3, 33, 41, 24, 144, 32, 2), (2, 16, 24, 32, 192, 32, 1)):
+            assert E.mbconv_pick(shape).startswith("mbconv<"), shape
+    # the tile form's persistent loop: min(tiles, slots) workgroups, slots = 1024 / 512 / 256 for <= 40 / <= 80 / more KB of LDS.
+    # 24-144-24 at stride 1 takes 8x8 tiles (10x10 inputs, 112 padded; 160 padded hidden channels, 352-byte rows) and
+    # 112 * 96 + 112 * 328 + 64 * 352 + 160 * 96 + 32 * 352 + 352 * 4 = 98 048 bytes: 256 slots, one workgroup of 1024 threads per CU
+    shape, = [s for f, s, _ in E.MBCONV_CASES if f == "tile" and s[3:] == (24, 144, 24, 1) and s[0] > 1]
+    assert shape[0] * -(-shape[1] // 8) * -(-shape[2] // 8) == 320 > 256 and E.mbconv_pick(shape) == "mbconv<S 1,8x8,expand,1024 threads> grid 256"
 
 
 @pytest.mark.parametrize("case", E.POOL_CASES, ids=POOL_IDS)

@@ -12,14 +12,12 @@ and the real activation scales - tests/test_gpu_parity.py keeps those.
 
 Views as in test_conv_exact_gpu.py::run_exact: x sits at an 8-channel offset in a wider buffer whose other channels hold NaN, y and the
 pre-add copy sit at an offset among -77 values that must survive.  The forms are selected through yolo_set_tuning (knobs 3 and 4) and
-restored in finally; the library cannot print which fused kernel a unit or block takes, so the forms rest on the knobs and on the
-rules tests/test_fused_exact_cpu.py repeats (see the header of tests/_exact_cases.py).
+restored in finally; right before every launch yolo_resunit_pick / yolo_stem_pick / yolo_mbconv_pick must name the kernel the case
+stands for, under the very knob and descriptor of that launch (see the header of tests/_exact_cases.py).
 
 Along the pixel direction every operand (x - the unit's residual too -, y, the pre-add copy, the float32 NCHW batch of the stem, every
 packed weight and bias) sits between the poisoned margins of tests/_guard.py, and every case runs once per poison (0xFF, 0x7F): a
 read outside an operand shows in the comparison, a write in Guard.assert_intact() after it."""
-import contextlib
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -28,25 +26,10 @@ import _exact_cases as E
 import _guard as G
 from helpers import exact_chain, exact_conv
 from test_conv_exact_gpu import DEV, _assert_equal, _nhwc
-from test_fused_exact_cpu import MB_IDS, POOL_IDS, STEM_IDS, UNIT_IDS
+from test_fused_exact_cpu import MB_IDS, POOL_IDS, STEM_IDS, UNIT_IDS, knob
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
-
-
-@contextlib.contextmanager
-def knob(i, value):
-    from pytorch_yolo_amd._lib import load
-    old = load().yolo_set_tuning(i, value)
-    try:
-        yield
-    finally:
-        load().yolo_set_tuning(i, old)
-
-
-def _act_code(act):
-    from pytorch_yolo_amd._lib import ACT_LEAKY01, ACT_RELU6
-    return {"leaky": ACT_LEAKY01, "relu6": ACT_RELU6}[act]
 
 
 def _view_in(x, g, margin=8):
@@ -76,8 +59,7 @@ def test_fused_residual_unit_exact(u, use_aux):
     w1p, b1p, kpad1, cpad1 = K.pack_conv_weight(w1, b1, c)
     w2p, b2p, kpad2, cpad2 = K.pack_conv_weight(w2, b2, c // 2)
     assert torch.equal(w1p.float()[:c // 2, :c], w1.reshape(c // 2, c)) and torch.equal(b1p[:c // 2], b1)
-    d = K.conv_desc(n=n, h=h, w=w, cin=c // 2, in_c_total=c + 16, in_c_offset=8, cout=c, out_c_total=c + 16, out_c_offset=8, ksize=3, stride=1,
-                    act=_act_code(act), kpad=kpad2, cout_pad=cpad2, aux=(c + 16, 8) if use_aux else (0, 0))
+    d = E.unit_desc(u, use_aux, kpad2, cpad2)
     with knob(3, u["knob3"]):
         for run, poison in enumerate(G.POISONS):
             g = G.Guard(poison, DEV)
@@ -85,6 +67,7 @@ def test_fused_residual_unit_exact(u, use_aux):
             dev = [g.like(name, t) for name, t in (("w1", w1p), ("b1", b1p), ("w2", w2p), ("b2", b2p))]
             y = g.alloc("y", (n, h, w, c + 16), BF16, -77.0)
             aux = g.alloc("pre-add copy", (n, h, w, c + 16), BF16, -77.0) if use_aux else None
+            assert K.resunit_pick(d, use_aux).startswith(E.unit_pick_wanted(u)), K.resunit_pick(d, use_aux)
             K.resunit(xin, dev[0], dev[1], dev[2], dev[3], y, d, kpad1, cpad1, y_preadd=aux)
             torch.cuda.synchronize()
             _check_view(y, 8, c, y_ref, f"y (launch {run})")
@@ -104,13 +87,13 @@ def test_fused_stem_exact(kernel, shape, tile, seed):
     w2p, b2p, kpad2, cpad2 = K.pack_conv_weight(w2, b2, 32)
     ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
     assert y_ref.shape == (n, 64, ho, wo)
-    d = K.conv_desc(n=n, h=h, w=w, cin=32, in_c_total=32, in_c_offset=0, cout=64, out_c_total=80, out_c_offset=8, ksize=3, stride=2,
-                    act=_act_code(act), kpad=kpad2, cout_pad=cpad2)
+    d = E.stem_desc(shape, kpad2, cpad2)
     for run, poison in enumerate(G.POISONS):
         g = G.Guard(poison, DEV)
         xd = g.like("x (float32 NCHW)", x.contiguous())
         dev = [g.like(name, t) for name, t in (("w1", w1p), ("b1", b1p), ("w2", w2p), ("b2", b2p))]
         y = g.alloc("y", (n, ho, wo, 80), BF16, -77.0)
+        assert K.stem_pick(cin, d).startswith(E.stem_pick_wanted(kernel, shape, tile)), K.stem_pick(cin, d)
         K.stem(xd, cin, dev[0], dev[1], kpad1, dev[2], dev[3], y, d)
         torch.cuda.synchronize()
         _check_view(y, 8, 64, y_ref, f"y (launch {run})")
@@ -119,8 +102,7 @@ def test_fused_stem_exact(kernel, shape, tile, seed):
 
 @pytest.mark.parametrize("form,shape,tile", E.MBCONV_CASES, ids=MB_IDS)
 def test_fused_inverted_residual_exact(form, shape, tile):
-    """K.mbconv in the tile form, the row-strip form (knob 4 bit kMbStripForm; every strip case passes launch_strip's conditions,
-    tests/test_fused_exact_cpu.py) and the wide form's 13x13 and 7x7 tilings, on the ReLU6 chain: both intermediates clamped and
+    """K.mbconv in the tile form, the row-strip form (knob 4 bit kMbStripForm) and the wide form's 13x13 and 7x7 tilings, on the ReLU6 chain: both intermediates clamped and
     narrowed, the depthwise conv padding the EXPANDED map with zeros."""
     from pytorch_yolo_amd import kernels as K
     n, h, w, cin, hidden, cout, stride = shape
@@ -138,6 +120,7 @@ def test_fused_inverted_residual_exact(form, shape, tile):
         y = g.alloc("y", (n, ho, wo, cout + 8), BF16, -77.0)
         packed = tuple(None if t is None else g.like(name, t) for name, t in zip(("w expand", "b expand", "w depthwise", "b depthwise", "w project", "b project"), host))
         with knob(4, E.MB_STRIP if form == "strip" else 0):
+            assert E.mbconv_pick(shape).startswith(E.mbconv_pick_wanted(form, shape, tile)), E.mbconv_pick(shape)
             K.mbconv(xin, packed, y, n=n, h=h, w=w, cin=cin, hidden=hidden, cout=cout, in_view=(cin + 16, 8), out_view=(cout + 8, 4),
                      stride=stride, has_res=res is not None)
             torch.cuda.synchronize()
@@ -157,7 +140,7 @@ def test_small_cin_conv_with_maxpool_exact(case):
     assert y_ref.shape == (n, cout, ho, wo)
     wp, bp, kpad, cpad = K.pack_conv_weight(wt, bias, cin)
     d = K.conv_desc(n=n, h=h, w=w, cin=cin, in_c_total=cin + 16, in_c_offset=8, cout=cout, out_c_total=cout + 16, out_c_offset=8, ksize=3, stride=1,
-                    act=_act_code("leaky"), kpad=kpad, cout_pad=cpad)
+                    act=E.ACTS["leaky"], kpad=kpad, cout_pad=cpad)
     for poison in G.POISONS:
         g = G.Guard(poison, DEV)
         y = g.alloc("y", (n, ho, wo, cout + 16), BF16, -77.0)

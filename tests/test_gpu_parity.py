@@ -324,6 +324,8 @@ def test_fused_inverted_residual(n, h, w, cin, hidden, cout, stride, form):
         pytest.skip("the wide blocks have one form")
     old = load().yolo_set_tuning(4, 128 if form == "strip" else 0)    # YOLO_MBCONV_DEBUG bit 128: the row-strip form (opt-in, round 5)
     try:
+        pick = K.mbconv_pick(n=n, h=h, w=w, cin=cin, hidden=hidden, cout=cout, stride=stride, in_view=(cin + 16, 8), out_view=(cout + 8, 4))
+        assert pick.startswith("mbstrip<") == (form == "strip" and hidden <= 128), pick     # (the strip form holds <= 128 padded hidden channels)
         _check_fused_inverted_residual(n, h, w, cin, hidden, cout, stride)
     finally:
         load().yolo_set_tuning(4, old)

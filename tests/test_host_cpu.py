@@ -142,6 +142,13 @@ def test_planner_spp_fusions():
     kinds1 = [o.kind for o in _ops(_dry_plan(YOLOv3SPP(anchors=C.SPP_ANCHORS).eval(), 640, bs=1))]
     assert kinds1.count(OP_RESUNIT) == 1 and kinds1.count(OP_CONV) == 69 and K.resunit_form(128, 1, 160, 160) == 1
     assert K.resunit_form(128, 8, 160, 160) == 3 and K.resunit_form(256, 32, 80, 80) == 3 and K.resunit_form(64, 1, 320, 320) == 3
+    # the kernels and grids of the BASELINE launch list (32 images): what yolo_stem_pick / yolo_resunit_pick answer for these ops
+    at32 = [_lib.YoloConvDesc.from_buffer_copy(o.conv) for o in [ops[0]] + units]
+    for d in at32:
+        d.n = 32
+    assert K.stem_pick(ops[0].conv.res_c_total, at32[0]) == "stem2<leaky,8x16 outputs> grid 256"
+    assert [K.resunit_pick(d, bool(u.y_aux)) for d, u in zip(at32[1:], units)] == [
+        "resunit64_t20<400px x 64 couts, 4 waves> grid 8192"] + ["resunit_t20w<C 128, 400px x 128 couts, 4 waves> grid 2048"] * 2
     convs = [o for o in ops if o.kind == OP_CONV]
     assert sum(1 for o in convs if o.residual) == 20                                        # every other Add is an epilogue
     assert all(o.residual == o.y for o in convs if o.residual)                              # ... written in place
@@ -189,6 +196,12 @@ def test_planner_tiny_and_mobile():
         (96, 576, 96, 1, 26, True, 1), (96, 576, 96, 1, 26, True, 1), (96, 576, 160, 2, 26, True, 0),
         (160, 960, 160, 1, 13, True, 1), (160, 960, 160, 1, 13, True, 1), (160, 960, 320, 1, 13, True, 0)]
     assert [K.mbconv_form(o.conv.cin, o.kpad_pre, o.conv.cout, o.conv.stride) for o in mb] == [1] * 7 + [2] * 10
+    # the kernels and grids of the BASELINE launch list (64 images): yolo_mbconv_pick; no stem or fused unit here or in the tiny list
+    assert [K.mbconv_pick(n=64, h=o.conv.h, w=o.conv.w, cin=o.conv.cin, hidden=o.kpad_pre, cout=o.conv.cout, stride=o.conv.stride, has_res=bool(o.conv.res_c_total))
+            for o in mb] == ["mbconv<S 1,8x8,no expand,256 threads> grid 1024", "mbconv<S 2,4x8,expand,512 threads> grid 512"] + [
+        "mbconv<S %s,expand,%d threads> grid %d" % t for t in (("1,8x8", 1024, 256), ("2,4x8", 1024, 256), ("1,4x8", 512, 512), ("1,4x8", 512, 512), ("2,4x8", 1024, 256))] + [
+        "mbwide<S %s,512 threads,MC %d> grid 256" % t for t in [("1,13x13", 4)] * 6 + [("2,7x7", 10)] + [("1,7x7", 10)] * 3]
+    assert not [o for o in _ops(plan) + ops if o.kind in (OP_STEM, OP_RESUNIT)]
     # the wide form says "supported" only for shapes its launcher takes (stride 2, 96 -> 576 -> 320 needs 173 KB of LDS
     # for the 7x7 tile form - the planner must leave such a block as three launches instead of fusing it into a run-time error)
     assert K.mbconv_form(96, 576, 320, 2) == 0 and K.mbconv_form(96, 576, 256, 2) == 2 and K.mbconv_form(160, 960, 320, 1) == 2
@@ -658,7 +671,7 @@ def test_tile_rules_follow_the_cu_share_of_a_partitioned_stream():
 def test_tuning_table_names_single_bits_and_the_knobs_round_trip():
     """csrc/tuning.h is the one table of knobs: every named bit is a single bit, a value appears once per knob word (the fused
     units' bit 8 excepted: it is an ablation in both of their kernel families and has a name in each), and yolo_set_tuning(knob, v)
-    returns the previous value for knobs 0..4 and refuses any other knob."""
+    returns the previous value for knobs 0..11 and refuses any other knob."""
     text = open(os.path.join(ROOT, "pytorch_yolo_amd", "csrc", "tuning.h")).read()
     groups = re.findall(r"enum : int \{(.*?)\};", text, re.S)
     assert len(groups) == 7
@@ -667,11 +680,12 @@ def test_tuning_table_names_single_bits_and_the_knobs_round_trip():
         assert values and all(v > 0 and v & (v - 1) == 0 for v in values)
         assert len(set(values)) == len(values) - ("kRuT20NoEpilogue" in body)
     lib = _lib.load()
-    for knob in range(5):
+    assert len(re.findall(r"^//   knob +\d+ +YOLO_\w+ +Tuning::\w+", text, re.M)) == 12
+    for knob in range(12):
         old = lib.yolo_set_tuning(knob, 12345)
         try:
             assert lib.yolo_set_tuning(knob, 777) == 12345
         finally:
             assert lib.yolo_set_tuning(knob, old) == 777
-    assert lib.yolo_set_tuning(5, 0) != 0 and lib.yolo_set_tuning(-1, 0) != 0
+    assert lib.yolo_set_tuning(12, 0) == -1 and lib.yolo_set_tuning(-1, 0) == -1          # YOLO_E_ARG
     assert b"unknown knob" in lib.yolo_last_error()

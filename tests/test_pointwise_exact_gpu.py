@@ -4,18 +4,15 @@ that the reference alone notices each failure class):
   * yolo_conv1_nchw_f32_fwd (stride 1, cout 16 / 32, cin_real 3 / 1 / 8), its stride-2 form and yolo_conv1_pool_nchw_f32_fwd.  They
     narrow the caller's float32 pixels themselves: two thirds of x need rounding, a fifth are exact ties - a kernel that truncated
     x, multiplied the float32 values or rounded otherwise than yolo_pack_input_nchw_f32 would not reproduce the reference;
-  * yolo_dwconv3x3_fwd in its three forms (8-row strips in this process, the one-pixel form and 4-row strips in fresh interpreters:
-    YOLO_DWCONV_DEBUG is read when the library loads), yolo_dwconv_fwd and yolo_dwconv_f32_fwd, with every activation whose result is
-    determined (none, LeakyReLU, ReLU6, ReLU); swish keeps a tolerance;
+  * yolo_dwconv3x3_fwd in its three forms (8-row strips as shipped, the one-pixel form and 4-row strips under knob 9 of
+    yolo_set_tuning), yolo_dwconv_fwd and yolo_dwconv_f32_fwd, with every activation whose result is determined (none, LeakyReLU,
+    ReLU6, ReLU); swish keeps a tolerance;
   * yolo_se_fwd / yolo_se_f32_fwd stage by stage: the pooled means and the rescaled output bit for bit, the scales between them within
     a bound derived from the operands (helpers.se_scales_reference).
 Views as in test_conv_exact_gpu.py: bf16 / float32 NHWC inputs sit at a channel offset inside wider buffers whose other channels
 hold NaN, outputs among -77 values that must survive; every operand - the float32 NCHW batch, weights, biases and the workspace too -
 sits between the poisoned margins of tests/_guard.py, once per poison."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import pytest
 import torch
@@ -25,13 +22,12 @@ import _exact_cases as E
 import _guard as G
 from helpers import exact_dw, exact_first_layer, exact_se, se_rescale_reference, se_scales_reference
 from test_conv_exact_gpu import DEV, _assert_equal, _nhwc
-from test_fused_exact_gpu import _check_view
+from test_fused_exact_gpu import _check_view, knob
 from test_guard_bands_gpu import _act, _lib_call, _stream
 from test_pointwise_exact_cpu import DW3_IDS, DW_F32_IDS, DW_F32_ROWS, DW_IDS, DW_ROWS, FIRST_IDS, SE_IDS, SE_ROWS
 
 pytestmark = pytest.mark.gpu
 BF16, F32 = torch.bfloat16, torch.float32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- first-layer kernels ------------------------------------------------------------------------------------------------------------
@@ -100,7 +96,8 @@ def _dw3_launch(nchw, seed, stride, act, g):
 def test_dwconv3x3_exact(nchw, seed, stride):
     """yolo_dwconv3x3_fwd as shipped (8-row strips) with none, LeakyReLU, ReLU6 and ReLU.  (Before the kernels applied every activation
     the ReLU rows came back un-activated.)"""
-    assert os.environ.get("YOLO_DWCONV_DEBUG", "0") in ("", "0"), "this test is about the shipped form"
+    from pytorch_yolo_amd._lib import load
+    assert load().yolo_set_tuning(9, 0) == 0, "this test is about the shipped form (YOLO_DWCONV_DEBUG / knob 9 at 0)"
     for act in E.DW_ACTS:
         for poison in G.POISONS:
             g = G.Guard(poison, DEV)
@@ -109,38 +106,18 @@ def test_dwconv3x3_exact(nchw, seed, stride):
             g.assert_intact()
 
 
-def dw3_child(path):
-    """Body of the fresh interpreter test_dwconv3x3_debug_forms_exact starts: the whole table, every activation and poison, through
-    whatever form YOLO_DWCONV_DEBUG selected when the library loaded; the output views go to `path` for the parent to compare."""
-    out = {}
-    for (nchw, seed, stride), rid in zip(E.DW3_ROWS, DW3_IDS):
-        for act in E.DW_ACTS:
-            for poison in G.POISONS:
-                g = G.Guard(poison, DEV)
-                y, _ = _dw3_launch(nchw, seed, stride, act, g)
-                c = nchw[1]
-                assert torch.all(y[..., :8] == -77.0) and torch.all(y[..., 8 + c:] == -77.0), (rid, act, "channels outside the view were written")
-                g.assert_intact()
-                out[f"{rid}/{act}/{poison}"] = y[..., 8:8 + c].permute(0, 3, 1, 2).contiguous().cpu()
-    torch.save(out, path)
-
-
 @pytest.mark.parametrize("value", [1, 2], ids=["one_pixel", "four_rows"])
-def test_dwconv3x3_debug_forms_exact(value, tmp_path):
-    """kDwOnePixel and kDwFourRows (csrc/tuning.h) give the bits of the shipped form: the table runs in a fresh interpreter per value -
-    the variable is read when the library loads - and the parent compares what the child saved with the reference.  One attempt."""
-    path = str(tmp_path / "dw3.pt")
-    env = dict(os.environ, YOLO_DWCONV_DEBUG=str(value), PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")] + [p for p in os.environ.get("PYTHONPATH", "").split(os.pathsep) if p]))
-    code = "import test_pointwise_exact_gpu as t; t.dw3_child(%r)" % path
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, f"YOLO_DWCONV_DEBUG={value}: exit {r.returncode}\n{r.stdout[-1500:]}\n{r.stderr[-3000:]}"
-    got = torch.load(path)
-    assert len(got) == len(E.DW3_ROWS) * len(E.DW_ACTS) * len(G.POISONS)
-    for (nchw, seed, stride), rid in zip(E.DW3_ROWS, DW3_IDS):
-        for act in E.DW_ACTS:
-            y_ref = exact_dw(E.dw3_shape(nchw, stride, act), seed, BF16, "torch")[6]
-            for poison in G.POISONS:
-                _assert_equal(got[f"{rid}/{act}/{poison}"].permute(0, 2, 3, 1), y_ref, f"YOLO_DWCONV_DEBUG={value} {rid} {act} poison 0x{poison:02X}")
+def test_dwconv3x3_debug_forms_exact(value):
+    """kDwOnePixel and kDwFourRows (csrc/tuning.h, knob 9) give the bits of the shipped form: the whole table, every activation and
+    poison, with the knob set through yolo_set_tuning and restored afterwards."""
+    with knob(9, value):
+        for (nchw, seed, stride), rid in zip(E.DW3_ROWS, DW3_IDS):
+            for act in E.DW_ACTS:
+                for poison in G.POISONS:
+                    g = G.Guard(poison, DEV)
+                    y, y_ref = _dw3_launch(nchw, seed, stride, act, g)
+                    _check_view(y, 8, nchw[1], y_ref, f"YOLO_DWCONV_DEBUG={value} {rid} {act} poison 0x{poison:02X}")
+                    g.assert_intact()
 
 
 @pytest.mark.parametrize("stride", [1, 2])
