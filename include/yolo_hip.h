@@ -111,6 +111,40 @@ YOLO_API int yolo_conv2d_splitk_fwd(const void* x, const void* w_packed, const f
                                     void* y_preadd, const YoloConvDesc* d, int splits, void* workspace, size_t ws_bytes,
                                     int32_t* counters, yolo_stream_t s);
 
+/* ---- backward of ConvBlock.forward / the plain heads (models/yolo_base.py:19-44, models/yolov3_tiny.py:38,42; what torch autograd
+ *  does for the reference's nn.Conv2d + LeakyReLU), bf16 mode, STRIDE 1 (1x1 and 3x3 "same" convs): csrc/conv_bwd.hip.
+ *  Every entry takes the FORWARD's descriptor d of  y = act(conv(x, bf16(W)) + bias)  and returns YOLO_E_ARG for stride != 1, ksize not
+ *  in {1, 3}, pad != ksize / 2, upsample2x, a residual or pre-add view (res_* / aux_* non-zero), an act other than YOLO_ACT_NONE /
+ *  YOLO_ACT_LEAKY01, or misaligned views.  Arithmetic, cg = roundup(cout, 8):
+ *    g  = bf16_rne(fp32(dy) * (y > 0 ? 1 : 0.1f))  (act none: bf16_rne(dy)), bf16 NHWC [n,h,w,cg], channels cout..cg-1 zero;
+ *    dW[co][ci][kh][kw] = sum_{n,oh,ow} g[n,oh,ow,co] * x[n,oh+kh-pad,ow+kw-pad,ci]  (taps outside the image add nothing), bf16
+ *         operands, fp32 accumulation, fp32 in the parameter's OIHW layout [cout][cin][k][k];   db[co] = sum g, fp32;
+ *    dx = bf16_rne(conv(g, Wt)),  Wt[ci][co][kh][kw] = bf16(W)[co][ci][k-1-kh][k-1-kw], same pad, fp32 accumulation.
+ *  No atomics: two runs give the same bits.  Every element of g, dW, db and dx (its view) is written, never read-modify-written, and
+ *  nothing in the workspace needs initialising.
+ *  yolo_conv2d_bwd_workspace_bytes: splits * cout * (k*k*cin + 1) * 4 - the fp32 partial dW of each split of the pixel reduction, then
+ *    the partial db rows (0 with a message for a descriptor the backward does not take).
+ *  yolo_conv2d_bwd_pick: "wgrad<128x128,BK64,tr_b16> grid 9x2 splits 29" - tile, grid (column tiles x cout tiles) and split count of
+ *    yolo_conv2d_bwd_weight; no launch, no GPU.
+ *  yolo_conv2d_bwd_prepare: dy is DENSE [n,h,w,cout] of dy_dtype (YOLO_DT_BF16 | YOLO_DT_F32; any cout); y is the forward's output
+ *    in d's output view and d->out_dtype (may be NULL for act none); writes g.
+ *  yolo_conv2d_bwd_weight: x through d's input view; dbias may be NULL; the second pass adds the splits in split order.
+ *  yolo_conv2d_bwd_data: runs yolo_conv2d_fwd's dispatcher on g with w_packed_t = yolo_pack_conv_weight_dev(..., transposed = 1, ...)
+ *    of shape [roundup(cin,128)][roundup(k*k*cg,64)], act none, zero bias; dx = d's INPUT view (in_c_total / in_c_offset), the other
+ *    channels of that buffer are left alone.
+ *  yolo_pack_conv_weight_dev: device twin of yolo_pack_conv_weight_f32 - w_oihw f32 [cout][cin_w][k][k] ON THE DEVICE -> bf16
+ *    [cout_pad][kpad], RNE, zero padding.  transposed = 0: row co, k = (kh*ks+kw)*cin + ci (cin_w <= cin, cout <= cout_pad);
+ *    transposed = 1: the data gradient's matrix, row ci, k = (kh*ks+kw)*cin + co holding W[co][ci][ks-1-kh][ks-1-kw] - cin is then the
+ *    channel count of g (cout <= cin), cout_pad >= cin_w. */
+YOLO_API size_t yolo_conv2d_bwd_workspace_bytes(const YoloConvDesc* d);
+YOLO_API int yolo_conv2d_bwd_pick(const YoloConvDesc* d, char* out, int out_len);
+YOLO_API int yolo_conv2d_bwd_prepare(const void* dy, int dy_dtype, const void* y, void* g, const YoloConvDesc* d, yolo_stream_t s);
+YOLO_API int yolo_conv2d_bwd_weight(const void* x, const void* g, float* dw_oihw, float* dbias, void* workspace, size_t ws_bytes,
+                                    const YoloConvDesc* d, yolo_stream_t s);
+YOLO_API int yolo_conv2d_bwd_data(const void* g, const void* w_packed_t, void* dx, const YoloConvDesc* d, yolo_stream_t s);
+YOLO_API int yolo_pack_conv_weight_dev(const float* w_oihw, int cout, int cin_w, int ksize, int cin, int cout_pad, int kpad,
+                                       int transposed, void* out, yolo_stream_t s);
+
 /* First layer fused with the input packing: x is the caller's f32 NCHW batch [n,cin_real,h,w] (cin_real <= 8),
  * w_packed / bias as for yolo_conv2d_fwd with d->cin = 8; 3x3 / pad 1, bf16 NHWC output: stride 1 with cout 16 or 32
  * (Darknet), or stride 2 with cout 32 (MobileNetV2's first layer). */

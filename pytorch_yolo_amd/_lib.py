@@ -73,6 +73,12 @@ SIGNATURES = {
                                           C.POINTER(C.c_int)]),
     "yolo_conv2d_splitk_fwd": (C.c_int, [C.c_void_p] * 6 + [C.POINTER(YoloConvDesc), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                          C.c_void_p]),
+    "yolo_conv2d_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(YoloConvDesc)]),
+    "yolo_conv2d_bwd_pick": (C.c_int, [C.POINTER(YoloConvDesc), C.c_char_p, C.c_int]),
+    "yolo_conv2d_bwd_prepare": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(YoloConvDesc), C.c_void_p]),
+    "yolo_conv2d_bwd_weight": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(YoloConvDesc), C.c_void_p]),
+    "yolo_conv2d_bwd_data": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YoloConvDesc), C.c_void_p]),
+    "yolo_pack_conv_weight_dev": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
     "yolo_conv1_nchw_f32_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(YoloConvDesc), C.c_void_p]),
     "yolo_conv1_pool_nchw_f32_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

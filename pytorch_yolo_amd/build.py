@@ -30,6 +30,7 @@ SOURCES = {
     "conv_small.hip": [],
     "conv_f32.hip": ["-ffp-contract=off"],
     "conv1x1_stream.hip": [],
+    "conv_bwd.hip": [],
     "pointwise.hip": [],
     "efficient.hip": ["-ffp-contract=off"],
     "preprocess.hip": ["-ffp-contract=off"],

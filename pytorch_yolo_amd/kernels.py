@@ -15,7 +15,8 @@ from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU6, DT_BF16, DT_F16, DT_F32, Yo
 
 __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pick", "stem", "stem_pick", "resunit", "resunit_supported", "resunit_form", "resunit_pick", "maxpool", "spp", "dwconv3x3", "dwconv", "se", "se_workspace_bytes", "mbconv", "mbconv_supported", "mbconv_form", "mbconv_pick", "pack_mbconv", "conv3x3_pool", "conv3x3_pool_supported", "conv2d_splitk", "conv2d_splitk_plan", "decode", "head_decode", "head_decode_supported",
            "nms_merge", "nms_styled", "nms_styled_compact", "loss_workspace_bytes", "build_targets_fwd", "loss_fwd", "loss_bwd", "LOSS_REC_WORDS", "coco_workspace_bytes", "coco_match_fwd", "coco_accumulate_fwd", "coco_sweep_chunk", "coco_max_gt",
-           "COCO_T", "COCO_R", "COCO_A", "COCO_M", "pack_conv_weight", "roundup", "run_ops"]
+           "COCO_T", "COCO_R", "COCO_A", "COCO_M", "pack_conv_weight", "roundup", "run_ops",
+           "conv2d_bwd_workspace_bytes", "conv2d_bwd_pick", "conv2d_bwd_prepare", "conv2d_bwd_weight", "conv2d_bwd_data", "pack_conv_weight_dev"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -279,6 +280,83 @@ def conv2d(x, w_packed, bias, y, desc: YoloConvDesc, residual=None, y_preadd=Non
     check(load().yolo_conv2d_fwd(_ptr(x), _ptr(w_packed), _ptr(bias), _ptr(residual), _ptr(y), _ptr(y_preadd),
                                  C.byref(desc), stream_ptr()), "conv2d")
     return y
+
+
+def conv2d_bwd_workspace_bytes(desc: YoloConvDesc) -> int:
+    """Bytes of caller-owned workspace yolo_conv2d_bwd_weight needs for the forward's ``desc`` (no launch, works without a GPU)."""
+    n = load().yolo_conv2d_bwd_workspace_bytes(C.byref(desc))
+    if n == 0:
+        check(-1, "conv2d_bwd_workspace_bytes")
+    return int(n)
+
+
+def conv2d_bwd_pick(desc: YoloConvDesc) -> str:
+    """Tile, grid and split count of the weight-gradient launch for the forward's ``desc`` (no launch, works without a GPU)."""
+    buf = C.create_string_buffer(256)
+    check(load().yolo_conv2d_bwd_pick(C.byref(desc), buf, 256), "conv2d_bwd_pick")
+    return buf.value.decode()
+
+
+def _dt_of(t, what):
+    if t.dtype == torch.bfloat16:
+        return DT_BF16
+    if t.dtype == torch.float32:
+        return DT_F32
+    raise RuntimeError(f"{what} must be bfloat16 or float32, not {t.dtype}")
+
+
+def conv2d_bwd_prepare(dy, y, g, desc: YoloConvDesc):
+    """g = bf16(dy * act'(y)): ``dy`` dense [n,h,w,cout] (bf16 or f32), ``y`` the forward's output in ``desc``'s output view (None is
+    allowed for act none), ``g`` bf16 [n,h,w,roundup(cout,8)] - every element written."""
+    _need_cuda(dy, y, g)
+    pixels, cg = desc.n * desc.h * desc.w, roundup(desc.cout, 8)
+    if not dy.is_contiguous() or dy.numel() != pixels * desc.cout:
+        raise RuntimeError("conv2d_bwd_prepare: dy must be dense [n,h,w,cout]")
+    if g.dtype != torch.bfloat16 or not g.is_contiguous() or g.numel() != pixels * cg:
+        raise RuntimeError("conv2d_bwd_prepare: g must be contiguous bf16 [n,h,w,roundup(cout,8)]")
+    if y is not None and _dt_of(y, "y") != desc.out_dtype:
+        raise RuntimeError("conv2d_bwd_prepare: y must be the forward's output (desc.out_dtype, read through desc's output view)")
+    check(load().yolo_conv2d_bwd_prepare(_ptr(dy), _dt_of(dy, "dy"), _ptr(y), _ptr(g), C.byref(desc), stream_ptr()), "conv2d_bwd_prepare")
+    return g
+
+
+def conv2d_bwd_weight(x, g, dw, dbias, workspace, desc: YoloConvDesc):
+    """dW (f32 OIHW [cout,cin,k,k]) and, unless ``dbias`` is None, db (f32 [cout]) of the forward ``desc``; ``workspace``: a tensor of at
+    least conv2d_bwd_workspace_bytes(desc) bytes whose content does not matter."""
+    _need_cuda(x, g, dw, dbias, workspace)
+    if dw.dtype != torch.float32 or not dw.is_contiguous() or tuple(dw.shape) != (desc.cout, desc.cin, desc.ksize, desc.ksize):
+        raise RuntimeError("conv2d_bwd_weight: dw must be contiguous float32 [cout,cin,k,k]")
+    if dbias is not None and (dbias.dtype != torch.float32 or not dbias.is_contiguous() or dbias.numel() != desc.cout):
+        raise RuntimeError("conv2d_bwd_weight: dbias must be contiguous float32 [cout]")
+    check(load().yolo_conv2d_bwd_weight(_ptr(x), _ptr(g), _ptr(dw), _ptr(dbias), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                        C.byref(desc), stream_ptr()), "conv2d_bwd_weight")
+    return dw, dbias
+
+
+def conv2d_bwd_data(g, w_packed_t, dx, desc: YoloConvDesc):
+    """dx (bf16, ``desc``'s INPUT view of the buffer ``dx``) = conv(g, transposed flipped W) through the forward dispatcher;
+    ``w_packed_t`` from pack_conv_weight_dev(..., transposed=True)."""
+    _need_cuda(g, w_packed_t, dx)
+    check(load().yolo_conv2d_bwd_data(_ptr(g), _ptr(w_packed_t), _ptr(dx), C.byref(desc), stream_ptr()), "conv2d_bwd_data")
+    return dx
+
+
+def pack_conv_weight_dev(w_oihw: torch.Tensor, cin: int, transposed: bool = False, out: torch.Tensor | None = None):
+    """Device twin of pack_conv_weight: f32 OIHW [cout,cin_w,k,k] on the device -> bf16 [cout_pad, kpad], no host copy.
+    ``transposed``: the data gradient's matrix [roundup(cin_w,128), roundup(k*k*cin,64)] with ``cin`` = the channel count of g
+    (roundup(cout, 8)).  Returns (packed, kpad, cout_pad)."""
+    _need_cuda(w_oihw, out)
+    if w_oihw.dtype != torch.float32 or not w_oihw.is_contiguous() or w_oihw.dim() != 4 or w_oihw.shape[2] != w_oihw.shape[3]:
+        raise RuntimeError("pack_conv_weight_dev: w must be contiguous float32 [cout,cin,k,k]")
+    cout, cin_w, k, _ = w_oihw.shape
+    kpad, cout_pad = roundup(k * k * cin, 64), roundup(cin_w if transposed else cout, 128)
+    if out is None:
+        out = torch.empty((cout_pad, kpad), dtype=torch.bfloat16, device=w_oihw.device)
+    elif out.dtype != torch.bfloat16 or not out.is_contiguous() or out.numel() != cout_pad * kpad:
+        raise RuntimeError("pack_conv_weight_dev: out must be contiguous bf16 [cout_pad, kpad]")
+    check(load().yolo_pack_conv_weight_dev(_ptr(w_oihw), cout, cin_w, k, cin, cout_pad, kpad, int(transposed), _ptr(out), stream_ptr()),
+          "pack_conv_weight_dev")
+    return out, kpad, cout_pad
 
 
 def conv2d_splitk_plan(desc: YoloConvDesc, has_residual=False, has_preadd=False):

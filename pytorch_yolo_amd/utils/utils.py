@@ -451,9 +451,9 @@ def compute_loss(p, targets, model, class_weight=None, check=True):
     ``p[i].requires_grad``, ``loss`` carries a ``grad_fn`` and ``loss.backward()`` runs the gradient kernels of csrc/loss.hip
     (``loss_grad_raw``): ``p[i].grad`` is what the reference's ``loss.backward()`` leaves there within 5e-6 of each word group's
     largest element, bit-identical from run to run; a ``p[i]`` that does not require grad gets none.  The forward value has the same
-    bits either way; ``items`` is always detached (``:157``).  WHAT IS NOT: nothing propagates through this package's convolutions -
-    the ``p`` of ``io, p = model(x)`` has no ``grad_fn``, so the chain ends at ``p`` unless ``p`` comes from torch code of the caller's
-    (``p = [t.detach().requires_grad_() for t in p]``, heads computed in torch) -, a training-mode forward keeps raising, targets and
+    bits either way; ``items`` is always detached (``:157``).  WHAT IS NOT: nothing propagates through the MODEL's forward -
+    the ``p`` of ``io, p = model(x)`` has no ``grad_fn``, so the chain ends at ``p`` unless ``p`` comes from code of the caller's
+    (``p = [t.detach().requires_grad_() for t in p]``, heads computed in torch or with ``pytorch_yolo_amd.conv_block``) -, a training-mode forward keeps raising, targets and
     class weights get no gradient, and a double backward raises.  Otherwise (``torch.no_grad()``, or no ``p[i]`` requiring grad)
     ``loss.grad_fn is None`` and nothing can be back-propagated.
 
