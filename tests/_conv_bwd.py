@@ -18,34 +18,47 @@ import torch.nn.functional as F
 F64 = torch.float64
 U24 = 2.0 ** -24
 
-# (n, h, w, cin, cout, k, act, dtype of y and dy, view of x: None or (channels of the buffer, offset))
+# (n, h, w, cin, cout, k, act, dtype of y and dy, view of x: None or (channels of the buffer, offset), view of y: None or the same)
 CASES = [
-    (2, 13, 17, 24, 40, 3, "leaky", torch.bfloat16, None),      # 1 odd map, 442 pixels, ragged channel counts below one tile
-    (1, 1, 9, 8, 8, 3, "none", torch.bfloat16, None),           # 2 one-row map: only centre-row taps are in bounds
-    (2, 20, 20, 64, 128, 1, "leaky", torch.bfloat16, None),     # 3 1x1
-    (2, 8, 8, 32, 255, 1, "none", torch.float32, None),         # 4 head: g padded 255 -> 256, fp32 y and dy
-    (1, 4, 4, 16, 18, 1, "none", torch.float32, None),          # 5 nc = 1 head, padded 18 -> 24
-    (2, 80, 80, 16, 32, 3, "leaky", torch.bfloat16, None),      # 6 12,800 pixels: the split path
-    (3, 5, 7, 136, 8, 3, "none", torch.bfloat16, None),         # 7 1224 columns: ten 128-wide tiles, the last ragged; cout below a tile
-    (2, 13, 17, 24, 40, 3, "leaky", torch.bfloat16, (48, 16)),  # 8 case 1 with x as the view [16, 40) of a 48-channel buffer
+    (2, 13, 17, 24, 40, 3, "leaky", torch.bfloat16, None, None),      # 1 odd map, 442 pixels, ragged channel counts below one tile
+    (1, 1, 9, 8, 8, 3, "none", torch.bfloat16, None, None),           # 2 one-row map: only centre-row taps are in bounds
+    (2, 20, 20, 64, 128, 1, "leaky", torch.bfloat16, None, None),     # 3 1x1
+    (2, 8, 8, 32, 255, 1, "none", torch.float32, None, None),         # 4 head: g padded 255 -> 256, fp32 y and dy
+    (1, 4, 4, 16, 18, 1, "none", torch.float32, None, None),          # 5 nc = 1 head, padded 18 -> 24
+    (2, 80, 80, 16, 32, 3, "leaky", torch.bfloat16, None, None),      # 6 12,800 pixels: the split path
+    (3, 5, 7, 136, 8, 3, "none", torch.bfloat16, None, None),         # 7 1224 columns: ten 128-wide tiles, the last ragged; cout below a tile
+    (2, 13, 17, 24, 40, 3, "leaky", torch.bfloat16, (48, 16), None),  # 8 case 1 with x as the view [16, 40) of a 48-channel buffer
+    # the 128x128 tile (cout > 64) on the grids the neck layers take
+    (2, 6, 7, 16, 136, 3, "leaky", torch.bfloat16, None, None),       # 9 2x2 tiles, both edges ragged (144 columns, 136 couts); 84 pixels = one full + one partial stage
+    (2, 9, 9, 32, 72, 3, "leaky", torch.bfloat16, None, None),        # 10 ragged 128-tile (72 couts: no g chunk from chunk 9 on), three column tiles
+    (1, 10, 13, 256, 128, 1, "none", torch.bfloat16, None, None),     # 11 1x1 with two FULL column tiles: all four waves of the tile in range
+    (5, 20, 20, 32, 136, 3, "leaky", torch.bfloat16, None, None),     # 12 the split path in the 128-wide tile: 32 stages, 3x2 tiles, 4 splits, with db
+    (2, 5, 6, 16, 24, 1, "none", torch.float32, None, None),          # 13 fp32 head with cout % 8 == 0: whole 8-channel loads of fp32 dy
+    (1, 7, 9, 16, 100, 3, "leaky", torch.bfloat16, None, None),       # 14 bf16 output with cout % 8 != 0 (element loads of bf16); dx is a conv with 104 input channels
+    (1, 7, 9, 16, 100, 3, "leaky", torch.bfloat16, None, (112, 4)),   # 15 case 14 with y as the view [4, 104) of a 112-channel buffer (the "v4" view of _exact_cases.py; the forward accepts it as it is)
 ]
 SPLIT_CASE = 5          # index of case 6 in CASES
+WIDE_SPLIT_CASE = 11    # index of case 12
+# compute-unit shares (yolo_set_launch_cus) the two split cases also run under: 8 gives case 6 eight splits instead of 25 and case 12
+# three (11, 11 and 10 stages) instead of 4; 64 leaves both counts as they are (CPU test: test_split_count_follows_the_cu_share)
+CU_SHARES = (8, 64)
 
 
 def case_id(c):
-    n, h, w, cin, cout, k, act, dt, view = c
-    return f"{n}x{h}x{w}_{cin}to{cout}_k{k}_{act}_{'bf16' if dt == torch.bfloat16 else 'f32'}" + ("_view" if view else "")
+    n, h, w, cin, cout, k, act, dt, view, oview = c
+    return f"{n}x{h}x{w}_{cin}to{cout}_k{k}_{act}_{'bf16' if dt == torch.bfloat16 else 'f32'}" + ("_view" if view else "") + ("_yview" if oview else "")
 
 
 def fwd_desc(case, **over):
     """The FORWARD's descriptor of a case (what every backward entry point takes); ``over`` replaces conv_desc arguments."""
     from pytorch_yolo_amd import kernels as K
     from pytorch_yolo_amd._lib import ACT_LEAKY01, ACT_NONE, DT_BF16, DT_F32
-    n, h, w, cin, cout, k, act, dt, view = case
+    n, h, w, cin, cout, k, act, dt, view, oview = case
     total, off = view or (cin, 0)
     f32 = dt == torch.float32
-    kw = dict(n=n, h=h, w=w, cin=cin, in_c_total=total, in_c_offset=off, cout=cout, out_c_total=K.roundup(cout, 4) if f32 else cout,
-              out_c_offset=0, ksize=k, stride=1, act=ACT_LEAKY01 if act == "leaky" else ACT_NONE, kpad=K.roundup(k * k * cin, 64),
+    ototal, ooff = oview or (K.roundup(cout, 4) if f32 else cout, 0)
+    kw = dict(n=n, h=h, w=w, cin=cin, in_c_total=total, in_c_offset=off, cout=cout, out_c_total=ototal,
+              out_c_offset=ooff, ksize=k, stride=1, act=ACT_LEAKY01 if act == "leaky" else ACT_NONE, kpad=K.roundup(k * k * cin, 64),
               cout_pad=K.roundup(cout, 128), out_dtype=DT_F32 if f32 else DT_BF16)
     kw.update(over)
     return K.conv_desc(**kw)
@@ -137,7 +150,7 @@ def exact_operands(case, seed=0):
     with random signs u, v, a and random magnitudes m, m' - so that the terms of dx[p, ci] share the sign a_p v_ci and dx grows to
     ~2.9 cout k^2 and beyond 256, where bf16 has to round; x is plain random, so y, dW and db see random signs.
     Returns x [n,cin,h,w], w, b, dy [n,cout,h,w] as float64 tensors of integers."""
-    n, h, wd, cin, cout, k, act, dt, view = case
+    n, h, wd, cin, cout, k, act, dt, view, oview = case
     gen = _gen(1000 + seed)
     r = lambda *s: torch.randint(-3, 4, s, generator=gen).to(F64)
     sign = lambda *s: (torch.randint(0, 2, s, generator=gen) * 2 - 1).to(F64)
@@ -152,7 +165,7 @@ def exact_operands(case, seed=0):
 def random_operands(case, seed=0):
     """x, dy ~ N(0, 1) rounded to their storage types, w ~ N(0, 1 / fan_in) fp32 (it is NOT bf16-representable: the pack rounds it),
     b ~ N(0, 1) fp32; float64 tensors."""
-    n, h, wd, cin, cout, k, act, dt, view = case
+    n, h, wd, cin, cout, k, act, dt, view, oview = case
     gen = _gen(2000 + seed)
     x = torch.randn((n, cin, h, wd), generator=gen).to(torch.bfloat16).to(F64)
     w = (torch.randn((cout, cin, k, k), generator=gen) / (cin * k * k) ** 0.5).to(F64)
@@ -170,7 +183,7 @@ def exact_conditions(case, seed=0):
     """What makes an exact case a test (asserted by the CPU tests, relied on by the GPU ones): the float64 witnesses of exactness -
     every operand an integer, every sum of |terms| below 2^24 -, the share of y that is non-positive and the share of dx that needs
     rounding to bf16."""
-    n, h, wd, cin, cout, k, act, dt, view = case
+    n, h, wd, cin, cout, k, act, dt, view, oview = case
     x, w, b, dy = exact_operands(case, seed)
     y = forward(x, w, b, k, act)
     r = grads(x, w, dy, y, k, act)
@@ -184,3 +197,95 @@ def exact_conditions(case, seed=0):
 # dx can only leave the bf16 integers (|v| <= 256) where it has terms to grow on: with |g w| <= 9 and a mean of ~2.9 per term the
 # rounding guard binds from 128 terms on; below that (cases 2, 5, 7: 24, 18 and 72 terms) dx is exact in bf16 whatever the operands.
 DX_ROUNDING_FROM_TERMS = 128
+
+
+# ---- a chain of conv_blocks (torch's max-pool, upsample and concat between the layers) -------------------------------------
+#   f  = conv(x0 [2,32,8,10], W1)      a = conv(f, W2)      c = cat([upsample2x(a), r [2,48,16,20]], 1)      m = conv(c, W3)
+#   h1 = conv(m, W4)                   h2 = conv(max_pool2d(f, 2, 2), W5)          loss = sum(h1 R1) + sum(h2 R2)
+# f has two consumers (its gradient is a bf16 sum), the gradient of c arrives at a and r as channel slices, every dx is the next dy.
+CHAIN_BS, CHAIN_HW, CHAIN_SKIP = 2, (8, 10), 48
+CHAIN_LAYERS = [                         # cin, cout, k, act, dtype of y
+    (32, 64, 3, "leaky", torch.bfloat16),
+    (64, 32, 1, "leaky", torch.bfloat16),
+    (80, 136, 3, "leaky", torch.bfloat16),
+    (136, 21, 1, "none", torch.float32),
+    (64, 21, 1, "none", torch.float32),
+]
+
+
+def chain_operands(seed=0):
+    """x0, r: N(0, 1) bf16 values; W1..W5 ~ N(0, 1 / fan_in) fp32 master weights, b1..b5 ~ N(0, 1/4) fp32; R1, R2 ~ N(0, 1) fp32.
+    float64 NCHW tensors: dict(x0, r, R=[R1, R2], W=[...], b=[...])."""
+    gen = _gen(3000 + seed)
+    h, w = CHAIN_HW
+    rn = lambda *s: torch.randn(s, generator=gen)
+    ops = dict(x0=rn(CHAIN_BS, 32, h, w).to(torch.bfloat16).to(F64), r=rn(CHAIN_BS, CHAIN_SKIP, 2 * h, 2 * w).to(torch.bfloat16).to(F64), W=[], b=[])
+    for cin, cout, k, act, dt in CHAIN_LAYERS:
+        ops["W"].append((rn(cout, cin, k, k) / (cin * k * k) ** 0.5).to(F64))
+        ops["b"].append((rn(cout) * 0.5).to(F64))
+    ops["R"] = [rn(CHAIN_BS, 21, 2 * h, 2 * w).to(F64), rn(CHAIN_BS, 21, h // 2, w // 2).to(F64)]
+    return ops
+
+
+def chain_autograd64(ops):
+    """The network in float64 torch without any rounding: (dW list, db list, gradient of x0, gradient of r)."""
+    x0, r = ops["x0"].clone().requires_grad_(), ops["r"].clone().requires_grad_()
+    W = [t.clone().requires_grad_() for t in ops["W"]]
+    b = [t.clone().requires_grad_() for t in ops["b"]]
+
+    def conv(i, x):
+        y = F.conv2d(x, W[i], b[i], padding=CHAIN_LAYERS[i][2] // 2)
+        return F.leaky_relu(y, 0.1) if CHAIN_LAYERS[i][3] == "leaky" else y
+    f = conv(0, x0)
+    a = conv(1, f)
+    m = conv(2, torch.cat([F.interpolate(a, scale_factor=2, mode="nearest"), r], 1))
+    loss = (conv(3, m) * ops["R"][0]).sum() + (conv(4, F.max_pool2d(f, 2, 2)) * ops["R"][1]).sum()
+    loss.backward()
+    return [t.grad for t in W], [t.grad for t in b], x0.grad, r.grad
+
+
+def _pool_backward(x, dy):
+    """Gradient of max_pool2d(x, 2, 2) in float64: dy at the maximum of each window (torch's choice among equal values)."""
+    leaf = x.clone().requires_grad_()
+    return torch.autograd.grad(F.max_pool2d(leaf, 2, 2), leaf, dy)[0]
+
+
+def chain_restated(ops, rounding=True):
+    """The same network from forward() / grads(): float64 sums with every rounding point of the device chain - bf16 weights in the
+    product, y rounded to its storage type, g and dx rounded to bf16 by grads(), the upsample's 2x2 sum and the sum of f's two
+    gradients rounded once to bf16 (torch's bf16 kernels add in fp32 and round once).  Returns dict(calls=[per layer: x, y, dy and
+    the result of grads()], dw, db, x0_grad, r_grad, f_grads=(the two consumers' gradients of f))."""
+    W, b = ops["W"], ops["b"]
+
+    def store(y, dt):
+        if not rounding:
+            return y
+        return bf16(y) if dt == torch.bfloat16 else y.to(torch.float32).to(F64)
+
+    def fwd(i, x):
+        cin, cout, k, act, dt = CHAIN_LAYERS[i]
+        return store(forward(x, W[i], b[i], k, act, rounding), dt)
+
+    def bwd(i, x, y, dy):
+        cin, cout, k, act, dt = CHAIN_LAYERS[i]
+        return dict(x=x, y=y, dy=dy, r=grads(x, W[i], dy, y, k, act, rounding))
+    f = fwd(0, ops["x0"])
+    a = fwd(1, f)
+    c = torch.cat([F.interpolate(a, scale_factor=2, mode="nearest"), ops["r"]], 1)
+    m = fwd(2, c)
+    pooled = F.max_pool2d(f, 2, 2)
+    h1, h2 = fwd(3, m), fwd(4, pooled)
+    calls = [None] * 5
+    calls[3] = bwd(3, m, h1, ops["R"][0])
+    calls[4] = bwd(4, pooled, h2, ops["R"][1])
+    calls[2] = bwd(2, c, m, calls[3]["r"]["dx"])
+    dc = calls[2]["r"]["dx"]
+    calls[1] = bwd(1, f, a, bf16(F.avg_pool2d(dc[:, :32], 2) * 4, rounding))
+    f_grads = (calls[1]["r"]["dx"], _pool_backward(f, calls[4]["r"]["dx"]))
+    calls[0] = bwd(0, ops["x0"], f, bf16(f_grads[0] + f_grads[1], rounding))
+    return dict(calls=calls, dw=[c_["r"]["dw"] for c_ in calls], db=[c_["r"]["db"] for c_ in calls], x0_grad=calls[0]["r"]["dx"],
+                r_grad=dc[:, 32:], f_grads=f_grads)
+
+
+def rel_l2(got, want):
+    return float((got.to(F64) - want).norm() / want.norm())

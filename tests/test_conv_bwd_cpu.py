@@ -28,7 +28,7 @@ fwd_desc = B.fwd_desc
 def test_restatement_equals_float64_autograd(case):
     """Rounding off: dx, dW and db of the restatement - dx being a FORWARD conv with the flipped, transposed weights - equal float64
     torch autograd of leaky_relu(conv2d(x, w, b, padding=k//2), 0.1) (act none: of the conv) to 1e-11."""
-    n, h, w_, cin, cout, k, act, dt, view = case
+    n, h, w_, cin, cout, k, act, dt, view, oview = case
     x, w, b, dy = B.random_operands(case)
     xa, wa, ba = (t.clone().requires_grad_() for t in (x, w, b))
     y = F.conv2d(xa, wa, ba, padding=k // 2)
@@ -46,10 +46,34 @@ def test_restatement_equals_float64_autograd(case):
         assert not r["dw"][:, :, 0].any() and not r["dw"][:, :, 2].any() and r["dw"][:, :, 1].any()    # only centre-row taps are in bounds
 
 
+def test_chain_restatement_equals_float64_autograd():
+    """The five-layer chain of tests/_conv_bwd.py (max-pool, upsample, concat and a two-consumer tensor between the layers): with
+    rounding off, chain_restated - forward() / grads() per layer, the glue written out - equals float64 autograd of the whole network
+    to 1e-11 in every parameter, x0 and r.  With rounding on it is the yardstick of the GPU chain test, so its own distance from float64
+    autograd has to be a rounding-sized one.  Two parts: a gradient passes at most eight bf16 roundings of 2^-9 each (<= 2^-6 even if
+    they added up linearly), and a LeakyReLU whose y the roundings moved across zero changes its g by 0.9 dy - with a share p of such
+    elements in a layer that is 0.9 sqrt(p) / sqrt(0.505) = 1.27 sqrt(p) of the norm of g (half the slopes are 1, half 0.1).  The test
+    counts p (below 0.4 %: |dy| 2^-9-sized against y of order one) and asserts 2^-6 + 1.27 sqrt(largest p) <= 0.1 as the ceiling; a
+    dropped tensor or a wrong slice is off by order one."""
+    ops = B.chain_operands()
+    dw, db, gx0, gr = B.chain_autograd64(ops)
+    exact = B.chain_restated(ops, rounding=False)
+    for got, want in list(zip(exact["dw"], dw)) + list(zip(exact["db"], db)) + [(exact["x0_grad"], gx0), (exact["r_grad"], gr)]:
+        assert want.any() and float((got - want).abs().max()) <= 1e-11 * max(float(want.abs().max()), 1.0)
+    rounded = B.chain_restated(ops)
+    errs = [B.rel_l2(g, w_) for g, w_ in list(zip(rounded["dw"], dw)) + list(zip(rounded["db"], db))]
+    print("chain, float64 with the rounding points vs float64 autograd, relative L2 of dW1..5, db1..5: " + " ".join(f"{e:.2e}" for e in errs))
+    flipped = [float(((cr["y"] > 0) != (ce["y"] > 0)).double().mean()) for cr, ce in zip(rounded["calls"][:3], exact["calls"][:3])]
+    print("share of LeakyReLU outputs on the other side of zero, layers 1-3: " + " ".join(f"{100 * p:.3f} %" for p in flipped))
+    assert max(flipped) < 0.004 and 2.0 ** -6 + 1.27 * max(flipped) ** 0.5 <= 0.1
+    assert all(0 < e <= 0.1 for e in errs), errs
+    assert all(c["r"]["dx"].any() for c in rounded["calls"]) and rounded["f_grads"][0].any() and rounded["f_grads"][1].any()
+
+
 def test_rounding_points():
     """With rounding on, g is the fp32 product rounded to bf16 (slope 0.1f at y <= 0, torch's convention at y == 0) and dx a bf16 value."""
     case = B.CASES[0]
-    n, h, w_, cin, cout, k, act, dt, view = case
+    n, h, w_, cin, cout, k, act, dt, view, oview = case
     x, w, b, dy = B.random_operands(case)
     y = B.forward(x, w, b, k, act)
     y[0, 0, 0, 0] = 0.0
@@ -147,7 +171,7 @@ def test_library_refuses_what_the_backward_does_not_cover():
 def test_pick_and_workspace(case):
     """The split rule is a pure function of the descriptor: the pick names tile, grid and splits, and the workspace is
     splits x cout x (k k cin + 1) floats.  Case 6 (12,800 pixels, 2 tiles) splits its reduction."""
-    n, h, w, cin, cout, k, act, dt, view = case
+    n, h, w, cin, cout, k, act, dt, view, oview = case
     d = fwd_desc(case)
     pick = K.conv2d_bwd_pick(d)
     m = re.fullmatch(r"wgrad<(\d+)x128,BK64,tr_b16> grid (\d+)x(\d+) splits (\d+)", pick)
@@ -157,16 +181,53 @@ def test_pick_and_workspace(case):
     assert K.conv2d_bwd_workspace_bytes(d) == 4 * splits * cout * (k * k * cin + 1)
     steps = -(-n * h * w // 64)
     assert 1 <= splits <= max(1, steps // 8) and K.conv2d_bwd_pick(d) == pick
-    if case is B.CASES[B.SPLIT_CASE]:
+    if case is B.CASES[B.SPLIT_CASE] or case is B.CASES[B.WIDE_SPLIT_CASE]:
         assert splits >= 2
+
+
+def test_picks_of_the_wide_tile_cases():
+    """Cases 9-15 by name (256 compute units): the 128x128 tile on a 2x2 grid, with three and with two full column tiles, with a
+    split reduction, and the two heads' 64- and 128-row tiles."""
+    wide = "wgrad<128x128,BK64,tr_b16> "
+    want = [wide + "grid 2x2 splits 1", wide + "grid 3x1 splits 1", wide + "grid 2x1 splits 1", wide + "grid 3x2 splits 4",
+            "wgrad<64x128,BK64,tr_b16> grid 1x1 splits 1", wide + "grid 2x1 splits 1", wide + "grid 2x1 splits 1"]
+    assert [K.conv2d_bwd_pick(fwd_desc(c)) for c in B.CASES[8:]] == want
+    assert B.CASES[B.WIDE_SPLIT_CASE][:6] == (5, 20, 20, 32, 136, 3)
+    assert int(K.conv2d_bwd_pick(fwd_desc(B.CASES[B.WIDE_SPLIT_CASE])).rsplit(" ", 1)[1]) == min(-(-512 // 6), 32 // 8) >= 2
+
+
+def _splits(case):
+    return int(K.conv2d_bwd_pick(fwd_desc(case)).rsplit(" ", 1)[1])
+
+
+@pytest.mark.parametrize("index", [B.SPLIT_CASE, B.WIDE_SPLIT_CASE], ids=lambda i: B.case_id(B.CASES[i]))
+def test_split_count_follows_the_cu_share(index):
+    """The split count is sized against the thread's compute-unit share: under B.CU_SHARES (the values the GPU test runs) at least one
+    count differs from the 256-CU one, the workspace follows it, and the old share comes back."""
+    case = B.CASES[index]
+    n, h, w, cin, cout, k, act, dt, view, oview = case
+    d = fwd_desc(case)
+    base = _splits(case)
+    counts = []
+    for cus in B.CU_SHARES:
+        old = K.set_launch_cus(cus)
+        try:
+            counts.append(_splits(case))
+            assert K.conv2d_bwd_workspace_bytes(d) == 4 * counts[-1] * cout * (k * k * cin + 1)
+        finally:
+            assert K.set_launch_cus(old) == cus
+    assert old == 256 and _splits(case) == base
+    assert any(c != base for c in counts) and all(c >= 1 for c in counts), (base, counts)
+    if index == B.WIDE_SPLIT_CASE:       # 32 stages over 3 splits: 11, 11 and a short last split of 10 stages, the very last one partial
+        assert (base, counts[0]) == (4, 3) and n * h * w % 64
 
 
 def test_split_rule_on_the_measured_shapes():
     """SPP-640 x 32: the 80x80 128 -> 256 3x3 layer has 18 tiles and 204,800 pixels and splits; the 20x20 512 -> 1024 3x3 layer has
     288 tiles and does not need to."""
-    big = (32, 80, 80, 128, 256, 3, "leaky", torch.bfloat16, None)
+    big = (32, 80, 80, 128, 256, 3, "leaky", torch.bfloat16, None, None)
     assert K.conv2d_bwd_pick(fwd_desc(big)) == "wgrad<128x128,BK64,tr_b16> grid 9x2 splits 29"
-    deep = (32, 20, 20, 512, 1024, 3, "leaky", torch.bfloat16, None)
+    deep = (32, 20, 20, 512, 1024, 3, "leaky", torch.bfloat16, None, None)
     assert K.conv2d_bwd_pick(fwd_desc(deep)) == "wgrad<128x128,BK64,tr_b16> grid 36x8 splits 2"
 
 
@@ -187,17 +248,25 @@ def test_exact_case_guards(case):
 def test_injected_faults_show(case):
     """One wrong tap, or one dropped stretch of pixels (a 64-pixel stage; for the split case one whole split), changes at least 1 % of
     the elements of the exact dW: the comparison the GPU tests make is not vacuous."""
-    n, h, w_, cin, cout, k, act, dt, view = case
+    n, h, w_, cin, cout, k, act, dt, view, oview = case
     x, w, b, dy = B.exact_operands(case)
     y = B.forward(x, w, b, k, act)
     good = B.grads(x, w, dy, y, k, act)["dw"]
     pixels = n * h * w_
     lo, hi = (0, min(64, pixels))
-    if case is B.CASES[B.SPLIT_CASE]:
-        splits = int(K.conv2d_bwd_pick(fwd_desc(case)).rsplit(" ", 1)[1])
+    splits = int(K.conv2d_bwd_pick(fwd_desc(case)).rsplit(" ", 1)[1])
+    assert (splits >= 2) == (case is B.CASES[B.SPLIT_CASE] or case is B.CASES[B.WIDE_SPLIT_CASE])
+    if splits >= 2:
         per = -(-(-(-pixels // 64)) // splits) * 64
         lo, hi = per, min(2 * per, pixels)
     faults = [("pixels", lo, hi)] + [("tap", t) for t in ((0, k * k - 1) if k == 3 and h > 1 else (k * k // 2,))]
     for inject in faults:
         bad = B.grads(x, w, dy, y, k, act, inject=inject)["dw"]
         assert float((bad != good).double().mean()) >= 0.01, inject
+    # one dropped 16-byte chunk column of one wave - 8 columns (tap, ci .. ci + 7) of 32 rows of D - would zero a block of the exact dW:
+    # every such block holds a non-zero element (a one-row map has taps with no term at all)
+    if h > 1:
+        d2 = good.permute(0, 2, 3, 1).reshape(cout, k * k * cin)                 # the kernel's column order: tap, then channel
+        rows = -(-cout // 32) * 32
+        blocks = F.pad(d2, (0, 0, 0, rows - cout)).reshape(rows // 32, 32, k * k * cin // 8, 8)
+        assert bool(blocks.ne(0).any(3).any(1).all())
