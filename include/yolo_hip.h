@@ -145,6 +145,43 @@ YOLO_API int yolo_conv2d_bwd_data(const void* g, const void* w_packed_t, void* d
 YOLO_API int yolo_pack_conv_weight_dev(const float* w_oihw, int cout, int cin_w, int ksize, int cin, int cout_pad, int kpad,
                                        int transposed, void* out, yolo_stream_t s);
 
+/* ---- training-mode ConvBlock: the BatchNorm2d between the conv and the LeakyReLU(0.1) (models/yolo_base.py:19-44, Conv2d(bias=False)
+ *  -> BatchNorm2d -> LeakyReLU(0.1)) with batch or running statistics, and its backward; bf16 mode: csrc/batchnorm.hip, DESIGN.md 3.6d.
+ *  z = bf16(conv(x, bf16(W))) (yolo_conv2d_fwd with act none and a zero bias) is DENSE [pixels][c], pixels = n h w, c % 8 == 0.  Every
+ *  fp32 and fp64 operation below is rounded on its own (no contraction):
+ *    training statistics: S1 = sum z, S2 = sum z z over the pixels in float64; mean64 = S1 / pixels; var64 = max(S2 / pixels -
+ *      mean64 mean64, 0); mean = f32(mean64); invstd = f32(1 / sqrt(var64 + (double)eps)); scale = gamma invstd; shift = beta - mean
+ *      scale; running_mean <- running_mean (1 - momentum) + momentum mean; running_var <- running_var (1 - momentum) + momentum
+ *      f32(var64 pixels / (pixels - 1))  (torch's unbiased form), both in fp32, in place, each only where its pointer is given.
+ *    eval statistics: mean = running_mean, invstd = f32(1 / sqrt((double)running_var + (double)eps)), scale and shift as above.
+ *    saved: f32 [4][c] = mean, invstd, scale, shift.
+ *    forward: a = f32(z) scale + shift;  y = bf16_rne(a > 0 ? a : 0.1f a)  (act none: bf16_rne(a)).
+ *    backward: slope = a > 0 ? 1 : 0.1f (act none: 1); ga = f32(dy) slope; xh = (f32(z) - mean) invstd; B = sum ga, G = sum ga xh
+ *      (fp32 terms, float64 sums); dbeta = f32(B); dgamma = f32(G); c1 = f32(B / pixels), c2 = f32(G / pixels) (batch_stats = 0: both
+ *      0); g = bf16_rne(scale ((ga - c1) - xh c2)), dense [pixels][c]: the operand yolo_conv2d_bwd_weight (dbias = NULL) and
+ *      yolo_conv2d_bwd_data take with the act-none descriptor of the conv.
+ *  The two reductions split the pixels over workgroups that write float64 partials into the caller's workspace; one thread per channel
+ *  adds them in split order.  No atomics: two runs give the same bits; every output and every used workspace byte is written, never
+ *  read-modify-written (running_mean / running_var are the one in-place update), and nothing in the workspace needs initialising.
+ *  yolo_bn_workspace_bytes: 2 c floats (c1 | c2, written by yolo_bn_act_bwd and readable after it) followed by splits * 2 * c doubles;
+ *    0 with a message for a shape the entries do not take.  The split count follows yolo_set_launch_cus.
+ *  yolo_bn_pick: "bn_reduce<8x32> grid 256x1 passes 100 last 100" - rows x chunk columns of a pass, grid (row splits x column tiles of 2048
+ *    channels), passes per split and those of the last split; no launch, no GPU.
+ *  yolo_bn_train_stats: pixels >= 2; running_mean / running_var may be NULL.    yolo_bn_eval_stats: nothing is reduced or updated.
+ *  yolo_bn_act_bwd: dy dense [pixels][c] of dy_dtype (YOLO_DT_BF16 | YOLO_DT_F32); batch_stats = 1 after yolo_bn_train_stats, 0 after
+ *    yolo_bn_eval_stats; g, dgamma and dbeta may each be NULL (not wanted).
+ *  YOLO_E_ARG (YOLO_E_WORKSPACE for a small workspace) before any launch for c % 8, an act other than YOLO_ACT_NONE / YOLO_ACT_LEAKY01,
+ *  pixels < 2 with batch statistics, a null or misaligned pointer (z, y, dy, g, saved, ws: 16 bytes; the fp32 vectors: 4). */
+YOLO_API size_t yolo_bn_workspace_bytes(long long pixels, int c);
+YOLO_API int yolo_bn_pick(long long pixels, int c, char* out, int out_len);
+YOLO_API int yolo_bn_train_stats(const void* z, long long pixels, int c, const float* gamma, const float* beta, float eps, float momentum,
+                                 float* running_mean, float* running_var, float* saved, void* ws, size_t ws_bytes, yolo_stream_t s);
+YOLO_API int yolo_bn_eval_stats(const float* gamma, const float* beta, const float* running_mean, const float* running_var, int c,
+                                float eps, float* saved, yolo_stream_t s);
+YOLO_API int yolo_bn_act_fwd(const void* z, const float* saved, void* y, long long pixels, int c, int act, yolo_stream_t s);
+YOLO_API int yolo_bn_act_bwd(const void* dy, int dy_dtype, const void* z, const float* saved, long long pixels, int c, int act,
+                             int batch_stats, void* g, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, yolo_stream_t s);
+
 /* First layer fused with the input packing: x is the caller's f32 NCHW batch [n,cin_real,h,w] (cin_real <= 8),
  * w_packed / bias as for yolo_conv2d_fwd with d->cin = 8; 3x3 / pad 1, bf16 NHWC output: stride 1 with cout 16 or 32
  * (Darknet), or stride 2 with cout 32 (MobileNetV2's first layer). */

@@ -37,6 +37,7 @@ SOURCES = {
     "nms.hip": ["-ffp-contract=off"],
     "loss.hip": ["-ffp-contract=off"],
     "coco_eval.hip": ["-ffp-contract=off"],
+    "batchnorm.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
           "-Wall", "-Wno-unused-function"]

@@ -16,7 +16,8 @@ from ._lib import (ACT_LEAKY01, ACT_NONE, ACT_RELU6, DT_BF16, DT_F16, DT_F32, Yo
 __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pick", "stem", "stem_pick", "resunit", "resunit_supported", "resunit_form", "resunit_pick", "maxpool", "spp", "dwconv3x3", "dwconv", "se", "se_workspace_bytes", "mbconv", "mbconv_supported", "mbconv_form", "mbconv_pick", "pack_mbconv", "conv3x3_pool", "conv3x3_pool_supported", "conv2d_splitk", "conv2d_splitk_plan", "decode", "head_decode", "head_decode_supported",
            "nms_merge", "nms_styled", "nms_styled_compact", "loss_workspace_bytes", "build_targets_fwd", "loss_fwd", "loss_bwd", "LOSS_REC_WORDS", "coco_workspace_bytes", "coco_match_fwd", "coco_accumulate_fwd", "coco_sweep_chunk", "coco_max_gt",
            "COCO_T", "COCO_R", "COCO_A", "COCO_M", "pack_conv_weight", "roundup", "run_ops",
-           "conv2d_bwd_workspace_bytes", "conv2d_bwd_pick", "conv2d_bwd_prepare", "conv2d_bwd_weight", "conv2d_bwd_data", "pack_conv_weight_dev"]
+           "conv2d_bwd_workspace_bytes", "conv2d_bwd_pick", "conv2d_bwd_prepare", "conv2d_bwd_weight", "conv2d_bwd_data", "pack_conv_weight_dev",
+           "bn_workspace_bytes", "bn_pick", "bn_train_stats", "bn_eval_stats", "bn_act_fwd", "bn_act_bwd"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -357,6 +358,93 @@ def pack_conv_weight_dev(w_oihw: torch.Tensor, cin: int, transposed: bool = Fals
     check(load().yolo_pack_conv_weight_dev(_ptr(w_oihw), cout, cin_w, k, cin, cout_pad, kpad, int(transposed), _ptr(out), stream_ptr()),
           "pack_conv_weight_dev")
     return out, kpad, cout_pad
+
+
+# ---- batch norm between the conv and its backward (csrc/batchnorm.hip) ----------------------------------------------
+def bn_workspace_bytes(pixels: int, c: int) -> int:
+    """Bytes of caller-owned workspace bn_train_stats / bn_act_bwd need for a dense [pixels, c] map (no launch, works without a GPU):
+    the c1 | c2 vector (2 c floats), then the splits' float64 partials."""
+    n = load().yolo_bn_workspace_bytes(int(pixels), int(c))
+    if n == 0:
+        check(-1, "bn_workspace_bytes")
+    return int(n)
+
+
+def bn_pick(pixels: int, c: int) -> str:
+    """Pass shape, grid and passes per split of the two batch-norm reductions (no launch, works without a GPU)."""
+    buf = C.create_string_buffer(256)
+    check(load().yolo_bn_pick(int(pixels), int(c), buf, 256), "bn_pick")
+    return buf.value.decode()
+
+
+def _bn_map(t, pixels, c, what, dtypes=(torch.bfloat16,)):
+    if t.dtype not in dtypes or not t.is_contiguous() or t.numel() != pixels * c:
+        raise RuntimeError(f"{what} must be dense [pixels, c] ({' or '.join(str(d) for d in dtypes)})")
+
+
+def _bn_vec(t, c, what, rows=1):
+    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != rows * c):
+        raise RuntimeError(f"{what} must be contiguous float32 [{'%d, ' % rows if rows > 1 else ''}c]")
+
+
+def bn_train_stats(z, gamma, beta, eps, momentum, running_mean, running_var, saved, workspace):
+    """Batch statistics of ``z`` (bf16, dense [..., c]) -> ``saved`` f32 [4, c] = mean, invstd, scale, shift; ``running_mean`` /
+    ``running_var`` (each may be None) are updated in place.  ``workspace``: at least bn_workspace_bytes bytes, content irrelevant."""
+    _need_cuda(z, gamma, beta, running_mean, running_var, saved, workspace)
+    c = z.shape[-1]
+    pixels = z.numel() // c
+    _bn_map(z, pixels, c, "bn_train_stats: z")
+    for t, what in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _bn_vec(t, c, f"bn_train_stats: {what}")
+    _bn_vec(saved, c, "bn_train_stats: saved", 4)
+    check(load().yolo_bn_train_stats(_ptr(z), pixels, c, _ptr(gamma), _ptr(beta), float(eps), float(momentum), _ptr(running_mean),
+                                     _ptr(running_var), _ptr(saved), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                     stream_ptr()), "bn_train_stats")
+    return saved
+
+
+def bn_eval_stats(gamma, beta, running_mean, running_var, eps, saved):
+    """``saved`` f32 [4, c] from the running statistics; nothing is reduced or updated."""
+    _need_cuda(gamma, beta, running_mean, running_var, saved)
+    c = gamma.numel()
+    for t, what in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _bn_vec(t, c, f"bn_eval_stats: {what}")
+    _bn_vec(saved, c, "bn_eval_stats: saved", 4)
+    check(load().yolo_bn_eval_stats(_ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var), c, float(eps), _ptr(saved), stream_ptr()),
+          "bn_eval_stats")
+    return saved
+
+
+def bn_act_fwd(z, saved, y, act):
+    """y = bf16(act(f32(z) scale + shift)) on dense [..., c] bf16 maps; ``act``: ACT_NONE or ACT_LEAKY01."""
+    _need_cuda(z, saved, y)
+    c = z.shape[-1]
+    pixels = z.numel() // c
+    _bn_map(z, pixels, c, "bn_act_fwd: z")
+    _bn_map(y, pixels, c, "bn_act_fwd: y")
+    _bn_vec(saved, c, "bn_act_fwd: saved", 4)
+    check(load().yolo_bn_act_fwd(_ptr(z), _ptr(saved), _ptr(y), pixels, c, int(act), stream_ptr()), "bn_act_fwd")
+    return y
+
+
+def bn_act_bwd(dy, z, saved, act, batch_stats, g, dgamma, dbeta, workspace):
+    """The batch-norm + activation backward: ``g`` (bf16, the conv backward's operand), ``dgamma``, ``dbeta`` (f32 [c]); each of the
+    three may be None.  ``dy`` dense [..., c] bf16 or f32; ``batch_stats``: saved came from bn_train_stats.  After the call the first
+    2 c floats of ``workspace`` hold c1 | c2."""
+    _need_cuda(dy, z, saved, g, dgamma, dbeta, workspace)
+    c = z.shape[-1]
+    pixels = z.numel() // c
+    _bn_map(z, pixels, c, "bn_act_bwd: z")
+    _bn_map(dy, pixels, c, "bn_act_bwd: dy", (torch.bfloat16, torch.float32))
+    if g is not None:
+        _bn_map(g, pixels, c, "bn_act_bwd: g")
+    _bn_vec(saved, c, "bn_act_bwd: saved", 4)
+    _bn_vec(dgamma, c, "bn_act_bwd: dgamma")
+    _bn_vec(dbeta, c, "bn_act_bwd: dbeta")
+    check(load().yolo_bn_act_bwd(_ptr(dy), _dt_of(dy, "dy"), _ptr(z), _ptr(saved), pixels, c, int(act), int(bool(batch_stats)), _ptr(g),
+                                 _ptr(dgamma), _ptr(dbeta), _ptr(workspace), workspace.numel() * workspace.element_size(), stream_ptr()),
+          "bn_act_bwd")
+    return g, dgamma, dbeta
 
 
 def conv2d_splitk_plan(desc: YoloConvDesc, has_residual=False, has_preadd=False):

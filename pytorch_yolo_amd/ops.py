@@ -4,6 +4,12 @@
 ``out_dtype=torch.float32`` the plain nn.Conv2d heads of models/yolov3_tiny.py:38,42) at stride 1, 1x1 or 3x3, in bf16 mode, WITH a
 backward: the forward is the launch the models use (yolo_conv2d_fwd), the backward runs csrc/conv_bwd.hip.  The
 models' own forward stays inference-only: ``io, p = model(x)`` has no ``grad_fn``.
+
+``conv_bn_block`` is the same ConvBlock with its BatchNorm2d NOT folded: conv -> batch norm on batch statistics -> LeakyReLU(0.1), the
+layer as the reference trains it.  The conv and its two gradients are conv_block's launches; the statistics, the normalise-and-activate
+pass and the batch-norm backward run csrc/batchnorm.hip.  With ``training=False`` the running statistics are frozen
+numbers and the layer IS conv_block on the folded weights: that is what runs, with the fold written in torch so that autograd carries
+the gradients on to weight, gamma and beta.
 """
 from __future__ import annotations
 
@@ -12,7 +18,7 @@ import torch
 from . import kernels as K
 from ._lib import ACT_LEAKY01, ACT_NONE, DT_BF16, DT_F32
 
-__all__ = ["conv_block"]
+__all__ = ["conv_block", "conv_bn_block"]
 
 _ACTS = {"leaky": ACT_LEAKY01, "none": ACT_NONE}
 
@@ -126,3 +132,131 @@ def conv_block(x, weight, bias=None, *, act="leaky", out_dtype=torch.bfloat16, s
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
         return _ConvBlockFunction.apply(x, weight, bias, act_id, out_f32)
     return _forward(x.detach(), weight.detach(), None if bias is None else bias.detach(), act_id, out_f32)[0]
+
+
+def _bn_forward(x, weight, gamma, beta, running, momentum, eps, act_id):
+    """conv (act none, zero bias) -> batch statistics -> normalise and activate.  Returns the NCHW-shaped result, the conv's descriptor, the
+    dense NHWC z and the saved [4, cout] vectors."""
+    z, d = _forward(x, weight, None, ACT_NONE, False)
+    z = z.permute(0, 2, 3, 1)                                             # the dense [n, h, w, cout] buffer the conv wrote
+    with torch.cuda.device(x.device):
+        saved = torch.empty((4, d.cout), dtype=torch.float32, device=x.device)
+        ws = torch.empty((K.bn_workspace_bytes(d.n * d.h * d.w, d.cout),), dtype=torch.uint8, device=x.device)
+        K.bn_train_stats(z, gamma, beta, eps, momentum, running[0], running[1], saved, ws)
+        y = torch.empty_like(z)
+        K.bn_act_fwd(z, saved, y, act_id)
+    return y.permute(0, 3, 1, 2), d, z, saved
+
+
+class _ConvBnBlockFunction(torch.autograd.Function):
+    """_bn_forward (training=True) with a backward: the batch-norm backward (g, dgamma, dbeta), then conv_block's weight and data gradients on g, each
+    only where asked.  z and saved are kept, y is not.  ``running`` is a tuple, so autograd does not track the in-place update."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, running, momentum, eps, act_id):
+        out, d, z, saved = _bn_forward(x, weight, gamma.detach(), beta.detach(), running, momentum, eps, act_id)
+        ctx.desc, ctx.act_id = d, act_id
+        ctx.save_for_backward(x, weight, z, saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, z, saved = ctx.saved_tensors
+        d = ctx.desc
+        need_x, need_w, need_g, need_b = ctx.needs_input_grad[:4]
+        dx = dw = dgamma = dbeta = g = None
+        with torch.cuda.device(x.device):
+            dy = dy.permute(0, 2, 3, 1).contiguous()                    # dense [n, h, w, cout]; no copy for a channels-last dy
+            if need_x or need_w:
+                g = torch.empty_like(z)
+            if need_g:
+                dgamma = torch.empty((d.cout,), dtype=torch.float32, device=x.device)
+            if need_b:
+                dbeta = torch.empty((d.cout,), dtype=torch.float32, device=x.device)
+            ws = torch.empty((K.bn_workspace_bytes(d.n * d.h * d.w, d.cout),), dtype=torch.uint8, device=x.device)
+            K.bn_act_bwd(dy, z, saved, ctx.act_id, True, g, dgamma, dbeta, ws)
+            if need_w:
+                dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)
+                ws = torch.empty((K.conv2d_bwd_workspace_bytes(d),), dtype=torch.uint8, device=x.device)
+                K.conv2d_bwd_weight(x, g, dw, None, ws, d)
+            if need_x:
+                packed_t, _, _ = K.pack_conv_weight_dev(weight, d.cout, transposed=True)
+                buf = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=x.device)
+                K.conv2d_bwd_data(g, packed_t, buf, d)
+                dx = buf.permute(0, 3, 1, 2)
+        return dx, dw, dgamma, dbeta, None, None, None, None
+
+
+def conv_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *, training=True, momentum=0.1, eps=1e-5, act="leaky",
+                  stride=1):
+    """``act(batch_norm(conv2d(x, bf16(weight), padding=k // 2)))`` at stride 1 on the device, differentiable once: the reference's
+    ConvBlock (Conv2d(bias=False) -> BatchNorm2d -> LeakyReLU(0.1)) as it trains.
+
+    x, weight   as in conv_block (the same conversions by torch outside the Function); ``cout % 8 == 0``.
+    gamma, beta float32 [cout] on the device: BatchNorm2d's weight and bias.
+    running_mean, running_var   float32 [cout] on the device or None.  ``training=True``: the batch's statistics normalise, and the
+                running tensors that are given are updated in place (momentum; running_var takes the unbiased variance, as torch).
+                ``training=False``: both are required, they normalise, and nothing is updated: the call is
+                ``conv_block(x, weight * s, beta - running_mean * s, act=act)`` with ``s = gamma / sqrt(running_var + eps)`` folded by
+                torch in float32 (one launch, one rounding of the result; autograd differentiates the fold).
+                ``num_batches_tracked`` is the caller's, as with torch.nn.functional.batch_norm.
+    momentum    a number in [0, 1]; None (torch's cumulative average) raises ValueError.
+    act         "leaky" (LeakyReLU(0.1)) or "none".
+    Returns an NCHW-shaped channels-last bfloat16 tensor.  Under ``torch.no_grad()``, or when no input requires grad, only the forward
+    runs.  Gradients: x bf16, weight, gamma and beta float32, each computed only where asked; two runs give the same bits.
+    Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no CPU fallback)."""
+    if not isinstance(x, torch.Tensor) or not isinstance(weight, torch.Tensor) or x.dim() != 4 or weight.dim() != 4:
+        raise ValueError("conv_bn_block: x must be [n, cin, h, w] and weight [cout, cin, k, k]")
+    if stride != 1:
+        raise ValueError(f"conv_bn_block: stride {stride} unsupported (the backward covers stride 1)")
+    if act not in _ACTS:
+        raise ValueError(f"conv_bn_block: act must be 'leaky' or 'none', not {act!r}")
+    if momentum is None or isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0.0 <= momentum <= 1.0:
+        raise ValueError(f"conv_bn_block: momentum must be a number in [0, 1], not {momentum!r} (the cumulative average is unsupported)")
+    if not isinstance(eps, (int, float)) or not eps >= 0.0:
+        raise ValueError(f"conv_bn_block: eps must be a non-negative number, not {eps!r}")
+    cout, cin, k, k2 = weight.shape
+    if k != k2 or k not in (1, 3):
+        raise ValueError(f"conv_bn_block: kernel {k}x{k2} unsupported (1x1 or 3x3)")
+    if x.shape[1] != cin:
+        raise ValueError(f"conv_bn_block: x has {x.shape[1]} channels, weight expects {cin}")
+    if min(x.shape) < 1 or cout < 1:
+        raise ValueError("conv_bn_block: empty tensor")
+    if cout % 8:
+        raise ValueError(f"conv_bn_block: cout % 8 == 0 is required (cout {cout})")
+    if weight.dtype != torch.float32:
+        raise ValueError("conv_bn_block: weight must be float32 [cout, cin, k, k]")
+    vectors = (("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var))
+    for name, t in vectors:
+        if t is None and name.startswith("running"):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (cout,):
+            raise ValueError(f"conv_bn_block: {name} must be float32 [cout]")
+    training = bool(training)
+    if not training and (running_mean is None or running_var is None):
+        raise ValueError("conv_bn_block: training=False needs running_mean and running_var")
+    if training and x.shape[0] * x.shape[2] * x.shape[3] < 2:
+        raise ValueError("conv_bn_block: expected more than 1 value per channel when training")
+    if not (x.is_cuda and weight.is_cuda and all(t is None or t.is_cuda for _, t in vectors)):
+        raise RuntimeError("pytorch_yolo_amd.conv_bn_block runs on a ROCm device only (no CPU fallback)")
+    if not training:        # frozen statistics: the folded layer, as the models run it
+        s = gamma / torch.sqrt(running_var.detach() + eps)
+        return conv_block(x, weight * s.reshape(-1, 1, 1, 1), beta - running_mean.detach() * s, act=act)
+    # conversions outside the Function: torch differentiates them
+    if cin % 8:
+        padc = 8 - cin % 8
+        x = torch.nn.functional.pad(x, (0, 0, 0, 0, 0, padc))
+        weight = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, padc))
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    weight, gamma, beta = weight.contiguous(), gamma.contiguous(), beta.contiguous()
+    running = (None if running_mean is None else running_mean.detach(), None if running_var is None else running_var.detach())
+    if any(t is not None and not t.is_contiguous() for t in running):
+        raise ValueError("conv_bn_block: the running tensors must be contiguous (they are updated in place)")
+    act_id = _ACTS[act]
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or gamma.requires_grad or beta.requires_grad):
+        return _ConvBnBlockFunction.apply(x, weight, gamma, beta, running, float(momentum), float(eps), act_id)
+    return _bn_forward(x.detach(), weight.detach(), gamma.detach(), beta.detach(), running, float(momentum), float(eps), act_id)[0]
