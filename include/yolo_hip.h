@@ -145,6 +145,38 @@ YOLO_API int yolo_conv2d_bwd_data(const void* g, const void* w_packed_t, void* d
 YOLO_API int yolo_pack_conv_weight_dev(const float* w_oihw, int cout, int cin_w, int ksize, int cin, int cout_pad, int kpad,
                                        int transposed, void* out, yolo_stream_t s);
 
+/* ---- backward of the downsample: ConvBlock(3x3, stride 2, pad 1), the five stride-2 layers of Darknet-53 (models/yolo_base.py:19-44;
+ *  what torch autograd does for the reference's nn.Conv2d(k=3, s=2, p=1) + LeakyReLU), bf16 mode: csrc/conv_down_bwd.hip, DESIGN.md 3.6e.
+ *  Every entry takes the FORWARD's stride-2 descriptor d of  y = act(conv(x, bf16(W)) + bias)  (yolo_conv2d_fwd; ho = (h - 1) / 2 + 1,
+ *  wo likewise: torch's output size for even and odd maps) and returns YOLO_E_ARG with a message for anything else: stride 1 (that is
+ *  yolo_conv2d_bwd_*), ksize 1 or 5, pad != 1, the "one more row" ho of Conv2dSamePadding, upsample2x, a residual or pre-add view, an
+ *  fp32 output, an act other than YOLO_ACT_NONE / YOLO_ACT_LEAKY01, cin % 8, cout % 8 or misaligned views.  Arithmetic:
+ *    g  = bf16_rne(fp32(dy) * (y > 0 ? 1 : 0.1f)), dense bf16 [n,ho,wo,cout]: yolo_conv2d_bwd_prepare with the STRIDE-1 descriptor of the
+ *         output map (h = ho, w = wo, ksize 1 or 3, the same output view and act) - there is no prepare entry here;
+ *    dW[co][ci][kh][kw] = sum_{n,oh,ow} g[n,oh,ow,co] * x[n, 2 oh + kh - 1, 2 ow + kw - 1, ci]  (taps outside the image add nothing), bf16
+ *         operands, fp32 accumulation, fp32 OIHW [cout][cin][3][3];   db[co] = sum g, fp32;
+ *    dx[n,ih,iw,ci] = bf16_rne(sum g[n,oh,ow,co] * bf16(W)[co][ci][kh][kw]) over co and the (kh, kw) with ih + 1 - kh = 2 oh and
+ *         iw + 1 - kw = 2 ow, 0 <= oh < ho, 0 <= ow < wo; fp32 accumulation.  By the parity of (ih, iw) a pixel has 1, 2 or 4 taps.
+ *  No atomics: two runs give the same bits.  Every element of dW, db and dx (its view) is written exactly once, never
+ *  read-modify-written, and nothing in the workspace needs initialising.
+ *  yolo_conv2d_down_bwd_workspace_bytes: splits * cout * (9 cin + 1) * 4, the split rule of yolo_conv2d_bwd_weight applied to the n ho wo
+ *    OUTPUT pixels (0 with a message for a descriptor these entries do not take).
+ *  yolo_conv2d_down_bwd_pick: "wgrad<128x128,BK64,tr_b16,s2> grid 9x2 splits 29; dgrad<128x128,BK64,parity> grid 6400x1 tiles
+ *    1600+1600+1600+1600" - the weight gradient's tile, grid and splits, then the data gradient's tile (pixels x channels), grid (pixel
+ *    tiles of all classes x channel tiles) and the pixel tiles of the parity classes (ih, iw) = (odd, odd), (odd, even), (even, odd),
+ *    (even, even) in launch order; no launch, no GPU.
+ *  yolo_conv2d_down_bwd_weight: x through d's input view; dbias may be NULL; the second pass adds the splits in split order.
+ *  yolo_conv2d_down_bwd_data: one launch for the four parity classes; w_packed_d from yolo_pack_conv_weight_down_dev; dx = d's INPUT
+ *    view (in_c_total / in_c_offset), the other channels of that buffer are left alone.
+ *  yolo_pack_conv_weight_down_dev: w_oihw f32 [cout][cin][3][3] ON THE DEVICE -> bf16 [3][3][cin][cout], RNE (the rounding of
+ *    yolo_pack_conv_weight_f32): out holds exactly 9 * cin * cout bf16 = 18 * cin * cout bytes, no padding; cout % 8 == cin % 8 == 0. */
+YOLO_API size_t yolo_conv2d_down_bwd_workspace_bytes(const YoloConvDesc* d);
+YOLO_API int yolo_conv2d_down_bwd_pick(const YoloConvDesc* d, char* out, int out_len);
+YOLO_API int yolo_conv2d_down_bwd_weight(const void* x, const void* g, float* dw_oihw, float* dbias, void* workspace, size_t ws_bytes,
+                                         const YoloConvDesc* d, yolo_stream_t s);
+YOLO_API int yolo_conv2d_down_bwd_data(const void* g, const void* w_packed_d, void* dx, const YoloConvDesc* d, yolo_stream_t s);
+YOLO_API int yolo_pack_conv_weight_down_dev(const float* w_oihw, int cout, int cin, void* out, yolo_stream_t s);
+
 /* ---- training-mode ConvBlock: the BatchNorm2d between the conv and the LeakyReLU(0.1) (models/yolo_base.py:19-44, Conv2d(bias=False)
  *  -> BatchNorm2d -> LeakyReLU(0.1)) with batch or running statistics, and its backward; bf16 mode: csrc/batchnorm.hip, DESIGN.md 3.6d.
  *  z = bf16(conv(x, bf16(W))) (yolo_conv2d_fwd with act none and a zero bias) is DENSE [pixels][c], pixels = n h w, c % 8 == 0.  Every

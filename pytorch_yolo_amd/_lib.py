@@ -78,6 +78,11 @@ SIGNATURES = {
     "yolo_conv2d_bwd_prepare": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(YoloConvDesc), C.c_void_p]),
     "yolo_conv2d_bwd_weight": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(YoloConvDesc), C.c_void_p]),
     "yolo_conv2d_bwd_data": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YoloConvDesc), C.c_void_p]),
+    "yolo_conv2d_down_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(YoloConvDesc)]),
+    "yolo_conv2d_down_bwd_pick": (C.c_int, [C.POINTER(YoloConvDesc), C.c_char_p, C.c_int]),
+    "yolo_conv2d_down_bwd_weight": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(YoloConvDesc), C.c_void_p]),
+    "yolo_conv2d_down_bwd_data": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(YoloConvDesc), C.c_void_p]),
+    "yolo_pack_conv_weight_down_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "yolo_bn_workspace_bytes": (C.c_size_t, [C.c_longlong, C.c_int]),
     "yolo_bn_pick": (C.c_int, [C.c_longlong, C.c_int, C.c_char_p, C.c_int]),
     "yolo_bn_train_stats": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float] + [C.c_void_p] * 4 +

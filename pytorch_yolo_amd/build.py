@@ -31,6 +31,7 @@ SOURCES = {
     "conv_f32.hip": ["-ffp-contract=off"],
     "conv1x1_stream.hip": [],
     "conv_bwd.hip": [],
+    "conv_down_bwd.hip": [],
     "pointwise.hip": [],
     "efficient.hip": ["-ffp-contract=off"],
     "preprocess.hip": ["-ffp-contract=off"],
@@ -52,7 +53,7 @@ def _stale(out: str, deps) -> bool:
 
 def build(force: bool = False, verbose: bool = False) -> str:
     headers = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv3x3_t20.h"), os.path.join(CSRC, "nms_common.h"),
-               os.path.join(CSRC, "head_epilogue.h"), os.path.join(CSRC, "tuning.h"),
+               os.path.join(CSRC, "head_epilogue.h"), os.path.join(CSRC, "tuning.h"), os.path.join(CSRC, "conv_wgrad.h"),
                os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "yolo_hip.h"),
                os.path.abspath(__file__)]        # per-file flags live here: a flag change rebuilds too
     objs, jobs = [], []

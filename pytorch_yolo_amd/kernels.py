@@ -17,6 +17,7 @@ __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pic
            "nms_merge", "nms_styled", "nms_styled_compact", "loss_workspace_bytes", "build_targets_fwd", "loss_fwd", "loss_bwd", "LOSS_REC_WORDS", "coco_workspace_bytes", "coco_match_fwd", "coco_accumulate_fwd", "coco_sweep_chunk", "coco_max_gt",
            "COCO_T", "COCO_R", "COCO_A", "COCO_M", "pack_conv_weight", "roundup", "run_ops",
            "conv2d_bwd_workspace_bytes", "conv2d_bwd_pick", "conv2d_bwd_prepare", "conv2d_bwd_weight", "conv2d_bwd_data", "pack_conv_weight_dev",
+           "conv2d_down_bwd_workspace_bytes", "conv2d_down_bwd_pick", "conv2d_down_bwd_weight", "conv2d_down_bwd_data", "pack_conv_weight_down_dev",
            "bn_workspace_bytes", "bn_pick", "bn_train_stats", "bn_eval_stats", "bn_act_fwd", "bn_act_bwd"]
 
 
@@ -358,6 +359,66 @@ def pack_conv_weight_dev(w_oihw: torch.Tensor, cin: int, transposed: bool = Fals
     check(load().yolo_pack_conv_weight_dev(_ptr(w_oihw), cout, cin_w, k, cin, cout_pad, kpad, int(transposed), _ptr(out), stream_ptr()),
           "pack_conv_weight_dev")
     return out, kpad, cout_pad
+
+
+# ---- backward of the 3x3 stride-2 downsample (csrc/conv_down_bwd.hip) ---------------------------------------------------
+def conv2d_down_bwd_workspace_bytes(desc: YoloConvDesc) -> int:
+    """Bytes of caller-owned workspace yolo_conv2d_down_bwd_weight needs for the forward's stride-2 ``desc`` (no launch, works without a GPU)."""
+    n = load().yolo_conv2d_down_bwd_workspace_bytes(C.byref(desc))
+    if n == 0:
+        check(-1, "conv2d_down_bwd_workspace_bytes")
+    return int(n)
+
+
+def conv2d_down_bwd_pick(desc: YoloConvDesc) -> str:
+    """Tile, grid and split count of the weight-gradient launch and tile, grid and per-class pixel tiles of the parity data-gradient launch
+    for the forward's stride-2 ``desc`` (no launch, works without a GPU)."""
+    buf = C.create_string_buffer(256)
+    check(load().yolo_conv2d_down_bwd_pick(C.byref(desc), buf, 256), "conv2d_down_bwd_pick")
+    return buf.value.decode()
+
+
+def conv2d_down_bwd_weight(x, g, dw, dbias, workspace, desc: YoloConvDesc):
+    """dW (f32 OIHW [cout,cin,3,3]) and, unless ``dbias`` is None, db (f32 [cout]) of the stride-2 forward ``desc``; ``g`` dense bf16
+    [n,ho,wo,cout]; ``workspace``: a tensor of at least conv2d_down_bwd_workspace_bytes(desc) bytes whose content does not matter."""
+    _need_cuda(x, g, dw, dbias, workspace)
+    if dw.dtype != torch.float32 or not dw.is_contiguous() or tuple(dw.shape) != (desc.cout, desc.cin, desc.ksize, desc.ksize):
+        raise RuntimeError("conv2d_down_bwd_weight: dw must be contiguous float32 [cout,cin,3,3]")
+    if dbias is not None and (dbias.dtype != torch.float32 or not dbias.is_contiguous() or dbias.numel() != desc.cout):
+        raise RuntimeError("conv2d_down_bwd_weight: dbias must be contiguous float32 [cout]")
+    if g.dtype != torch.bfloat16 or not g.is_contiguous() or g.numel() != desc.n * desc.ho * desc.wo * desc.cout:
+        raise RuntimeError("conv2d_down_bwd_weight: g must be contiguous bf16 [n,ho,wo,cout]")
+    check(load().yolo_conv2d_down_bwd_weight(_ptr(x), _ptr(g), _ptr(dw), _ptr(dbias), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                             C.byref(desc), stream_ptr()), "conv2d_down_bwd_weight")
+    return dw, dbias
+
+
+def conv2d_down_bwd_data(g, w_packed_d, dx, desc: YoloConvDesc):
+    """dx (bf16, ``desc``'s INPUT view of the buffer ``dx``) of the stride-2 forward ``desc``: the parity kernel, one launch;
+    ``w_packed_d`` from pack_conv_weight_down_dev."""
+    _need_cuda(g, w_packed_d, dx)
+    if g.dtype != torch.bfloat16 or not g.is_contiguous() or g.numel() != desc.n * desc.ho * desc.wo * desc.cout:
+        raise RuntimeError("conv2d_down_bwd_data: g must be contiguous bf16 [n,ho,wo,cout]")
+    if w_packed_d.dtype != torch.bfloat16 or not w_packed_d.is_contiguous() or w_packed_d.numel() != 9 * desc.cin * desc.cout:
+        raise RuntimeError("conv2d_down_bwd_data: w_packed_d must be contiguous bf16 [3,3,cin,cout]")
+    if dx.dtype != torch.bfloat16 or not dx.is_contiguous() or dx.numel() != desc.n * desc.h * desc.w * desc.in_c_total:
+        raise RuntimeError("conv2d_down_bwd_data: dx must be contiguous bf16 [n,h,w,in_c_total]")
+    check(load().yolo_conv2d_down_bwd_data(_ptr(g), _ptr(w_packed_d), _ptr(dx), C.byref(desc), stream_ptr()), "conv2d_down_bwd_data")
+    return dx
+
+
+def pack_conv_weight_down_dev(w_oihw: torch.Tensor, out: torch.Tensor | None = None):
+    """The data gradient's operand of the downsample: f32 OIHW [cout,cin,3,3] on the device -> bf16 [3,3,cin,cout], no host copy."""
+    _need_cuda(w_oihw, out)
+    if w_oihw.dtype != torch.float32 or not w_oihw.is_contiguous() or w_oihw.dim() != 4 or tuple(w_oihw.shape[2:]) != (3, 3):
+        raise RuntimeError("pack_conv_weight_down_dev: w must be contiguous float32 [cout,cin,3,3]")
+    cout, cin = w_oihw.shape[:2]
+    if out is None:
+        out = torch.empty((3, 3, cin, cout), dtype=torch.bfloat16, device=w_oihw.device)
+    elif out.dtype != torch.bfloat16 or not out.is_contiguous() or out.numel() != 9 * cin * cout:
+        raise RuntimeError("pack_conv_weight_down_dev: out must be contiguous bf16 [3,3,cin,cout]")
+    check(load().yolo_pack_conv_weight_down_dev(_ptr(w_oihw), cout, cin, _ptr(out), stream_ptr()), "pack_conv_weight_down_dev")
+    return out
 
 
 # ---- batch norm between the conv and its backward (csrc/batchnorm.hip, DESIGN.md 3.6d) ----------------------------------------------

@@ -10,6 +10,10 @@ layer as the reference trains it.  The conv and its two gradients are conv_block
 pass and the batch-norm backward run csrc/batchnorm.hip.  With ``training=False`` the running statistics are frozen
 numbers and the layer IS conv_block on the folded weights: that is what runs, with the fold written in torch so that autograd carries
 the gradients on to weight, gamma and beta.
+
+``down_block`` and ``down_bn_block`` are the same two contracts for the downsample, ConvBlock(3x3, stride 2, pad 1) - the five stride-2
+layers of Darknet-53: the forward is again yolo_conv2d_fwd, the two gradients run csrc/conv_down_bwd.hip, the batch
+norm is conv_bn_block's (yolo_bn_* take the n ho wo output pixels).
 """
 from __future__ import annotations
 
@@ -18,29 +22,29 @@ import torch
 from . import kernels as K
 from ._lib import ACT_LEAKY01, ACT_NONE, DT_BF16, DT_F32
 
-__all__ = ["conv_block", "conv_bn_block"]
+__all__ = ["conv_block", "conv_bn_block", "down_block", "down_bn_block"]
 
 _ACTS = {"leaky": ACT_LEAKY01, "none": ACT_NONE}
 
 
-def _desc(x, weight, act_id, out_f32):
+def _desc(x, weight, act_id, out_f32, stride=1):
     n, c, h, w = x.shape
     cout, _, k, _ = weight.shape
     ct = K.roundup(cout, 4) if out_f32 else cout
-    return K.conv_desc(n=n, h=h, w=w, cin=c, in_c_total=c, in_c_offset=0, cout=cout, out_c_total=ct, out_c_offset=0, ksize=k, stride=1,
+    return K.conv_desc(n=n, h=h, w=w, cin=c, in_c_total=c, in_c_offset=0, cout=cout, out_c_total=ct, out_c_offset=0, ksize=k, stride=stride,
                        act=act_id, kpad=K.roundup(k * k * c, 64), cout_pad=K.roundup(cout, 128), out_dtype=DT_F32 if out_f32 else DT_BF16)
 
 
-def _forward(x, weight, bias, act_id, out_f32):
+def _forward(x, weight, bias, act_id, out_f32, stride=1):
     """The forward launch on a device-packed weight.  x: bf16, NCHW-shaped, dense channels-last.  Returns the NCHW-shaped
-    channels-last result (a view of the [n, h, w, out_c_total] buffer the kernel wrote) and the descriptor."""
-    d = _desc(x, weight, act_id, out_f32)
+    channels-last result (a view of the [n, ho, wo, out_c_total] buffer the kernel wrote) and the descriptor."""
+    d = _desc(x, weight, act_id, out_f32, stride)
     with torch.cuda.device(x.device):
         packed, _, cout_pad = K.pack_conv_weight_dev(weight, d.cin)
         b = torch.zeros((cout_pad,), dtype=torch.float32, device=x.device)
         if bias is not None:
             b[:d.cout] = bias
-        y = torch.empty((d.n, d.h, d.w, d.out_c_total), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+        y = torch.empty((d.n, d.ho, d.wo, d.out_c_total), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
         K.conv2d(x, packed, b, y, d)
     return y[..., :d.cout].permute(0, 3, 1, 2), d
 
@@ -118,30 +122,21 @@ def conv_block(x, weight, bias=None, *, act="leaky", out_dtype=torch.bfloat16, s
         raise ValueError(f"conv_block: a bfloat16 output needs cout % 8 == 0 (cout {cout}); use out_dtype=torch.float32")
     if not (x.is_cuda and weight.is_cuda and (bias is None or bias.is_cuda)):
         raise RuntimeError("pytorch_yolo_amd.conv_block runs on a ROCm device only (no CPU fallback)")
-    # conversions outside the Function: torch differentiates them
-    if cin % 8:
-        padc = 8 - cin % 8
-        x = torch.nn.functional.pad(x, (0, 0, 0, 0, 0, padc))
-        weight = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, padc))
-    if x.dtype != torch.bfloat16:
-        x = x.to(torch.bfloat16)
-    if not x.permute(0, 2, 3, 1).is_contiguous():
-        x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    weight = weight.contiguous()
+    x, weight = _to_kernel_layout(x, weight)
     act_id, out_f32 = _ACTS[act], out_dtype == torch.float32
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
         return _ConvBlockFunction.apply(x, weight, bias, act_id, out_f32)
     return _forward(x.detach(), weight.detach(), None if bias is None else bias.detach(), act_id, out_f32)[0]
 
 
-def _bn_forward(x, weight, gamma, beta, running, momentum, eps, act_id):
+def _bn_forward(x, weight, gamma, beta, running, momentum, eps, act_id, stride=1):
     """conv (act none, zero bias) -> batch statistics -> normalise and activate.  Returns the NCHW-shaped result, the conv's descriptor, the
     dense NHWC z and the saved [4, cout] vectors."""
-    z, d = _forward(x, weight, None, ACT_NONE, False)
-    z = z.permute(0, 2, 3, 1)                                             # the dense [n, h, w, cout] buffer the conv wrote
+    z, d = _forward(x, weight, None, ACT_NONE, False, stride)
+    z = z.permute(0, 2, 3, 1)                                             # the dense [n, ho, wo, cout] buffer the conv wrote
     with torch.cuda.device(x.device):
         saved = torch.empty((4, d.cout), dtype=torch.float32, device=x.device)
-        ws = torch.empty((K.bn_workspace_bytes(d.n * d.h * d.w, d.cout),), dtype=torch.uint8, device=x.device)
+        ws = torch.empty((K.bn_workspace_bytes(d.n * d.ho * d.wo, d.cout),), dtype=torch.uint8, device=x.device)
         K.bn_train_stats(z, gamma, beta, eps, momentum, running[0], running[1], saved, ws)
         y = torch.empty_like(z)
         K.bn_act_fwd(z, saved, y, act_id)
@@ -188,6 +183,48 @@ class _ConvBnBlockFunction(torch.autograd.Function):
         return dx, dw, dgamma, dbeta, None, None, None, None
 
 
+def _check_momentum_eps(name, momentum, eps):
+    if momentum is None or isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0.0 <= momentum <= 1.0:
+        raise ValueError(f"{name}: momentum must be a number in [0, 1], not {momentum!r} (the cumulative average is unsupported)")
+    if not isinstance(eps, (int, float)) or not eps >= 0.0:
+        raise ValueError(f"{name}: eps must be a non-negative number, not {eps!r}")
+
+
+def _check_bn_vectors(name, cout, gamma, beta, running_mean, running_var, training):
+    """The batch-norm vectors of ``name`` (conv_bn_block / down_bn_block): float32 [cout]; training=False needs both running tensors."""
+    vectors = (("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var))
+    for what, t in vectors:
+        if t is None and what.startswith("running"):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (cout,):
+            raise ValueError(f"{name}: {what} must be float32 [cout]")
+    if not training and (running_mean is None or running_var is None):
+        raise ValueError(f"{name}: training=False needs running_mean and running_var")
+    return vectors
+
+
+def _to_kernel_layout(x, weight):
+    """The conversions of an op's x and weight, outside the Function so that torch differentiates them: cin zero-padded to a multiple of
+    8, x bfloat16 and dense channels-last, weight contiguous."""
+    cin = weight.shape[1]
+    if cin % 8:
+        padc = 8 - cin % 8
+        x = torch.nn.functional.pad(x, (0, 0, 0, 0, 0, padc))
+        weight = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, padc))
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    return x, weight.contiguous()
+
+
+def _running(name, running_mean, running_var):
+    running = (None if running_mean is None else running_mean.detach(), None if running_var is None else running_var.detach())
+    if any(t is not None and not t.is_contiguous() for t in running):
+        raise ValueError(f"{name}: the running tensors must be contiguous (they are updated in place)")
+    return running
+
+
 def conv_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *, training=True, momentum=0.1, eps=1e-5, act="leaky",
                   stride=1):
     """``act(batch_norm(conv2d(x, bf16(weight), padding=k // 2)))`` at stride 1 on the device, differentiable once: the reference's
@@ -212,10 +249,7 @@ def conv_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *
         raise ValueError(f"conv_bn_block: stride {stride} unsupported (the backward covers stride 1)")
     if act not in _ACTS:
         raise ValueError(f"conv_bn_block: act must be 'leaky' or 'none', not {act!r}")
-    if momentum is None or isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0.0 <= momentum <= 1.0:
-        raise ValueError(f"conv_bn_block: momentum must be a number in [0, 1], not {momentum!r} (the cumulative average is unsupported)")
-    if not isinstance(eps, (int, float)) or not eps >= 0.0:
-        raise ValueError(f"conv_bn_block: eps must be a non-negative number, not {eps!r}")
+    _check_momentum_eps("conv_bn_block", momentum, eps)
     cout, cin, k, k2 = weight.shape
     if k != k2 or k not in (1, 3):
         raise ValueError(f"conv_bn_block: kernel {k}x{k2} unsupported (1x1 or 3x3)")
@@ -227,15 +261,8 @@ def conv_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *
         raise ValueError(f"conv_bn_block: cout % 8 == 0 is required (cout {cout})")
     if weight.dtype != torch.float32:
         raise ValueError("conv_bn_block: weight must be float32 [cout, cin, k, k]")
-    vectors = (("gamma", gamma), ("beta", beta), ("running_mean", running_mean), ("running_var", running_var))
-    for name, t in vectors:
-        if t is None and name.startswith("running"):
-            continue
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (cout,):
-            raise ValueError(f"conv_bn_block: {name} must be float32 [cout]")
     training = bool(training)
-    if not training and (running_mean is None or running_var is None):
-        raise ValueError("conv_bn_block: training=False needs running_mean and running_var")
+    vectors = _check_bn_vectors("conv_bn_block", cout, gamma, beta, running_mean, running_var, training)
     if training and x.shape[0] * x.shape[2] * x.shape[3] < 2:
         raise ValueError("conv_bn_block: expected more than 1 value per channel when training")
     if not (x.is_cuda and weight.is_cuda and all(t is None or t.is_cuda for _, t in vectors)):
@@ -243,20 +270,158 @@ def conv_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *
     if not training:        # frozen statistics: the folded layer, as the models run it
         s = gamma / torch.sqrt(running_var.detach() + eps)
         return conv_block(x, weight * s.reshape(-1, 1, 1, 1), beta - running_mean.detach() * s, act=act)
-    # conversions outside the Function: torch differentiates them
-    if cin % 8:
-        padc = 8 - cin % 8
-        x = torch.nn.functional.pad(x, (0, 0, 0, 0, 0, padc))
-        weight = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, padc))
-    if x.dtype != torch.bfloat16:
-        x = x.to(torch.bfloat16)
-    if not x.permute(0, 2, 3, 1).is_contiguous():
-        x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
-    weight, gamma, beta = weight.contiguous(), gamma.contiguous(), beta.contiguous()
-    running = (None if running_mean is None else running_mean.detach(), None if running_var is None else running_var.detach())
-    if any(t is not None and not t.is_contiguous() for t in running):
-        raise ValueError("conv_bn_block: the running tensors must be contiguous (they are updated in place)")
+    x, weight = _to_kernel_layout(x, weight)
+    gamma, beta = gamma.contiguous(), beta.contiguous()
+    running = _running("conv_bn_block", running_mean, running_var)
     act_id = _ACTS[act]
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or gamma.requires_grad or beta.requires_grad):
         return _ConvBnBlockFunction.apply(x, weight, gamma, beta, running, float(momentum), float(eps), act_id)
     return _bn_forward(x.detach(), weight.detach(), gamma.detach(), beta.detach(), running, float(momentum), float(eps), act_id)[0]
+
+
+# ---- the downsample: ConvBlock(3x3, stride 2, pad 1) ---------------------------------------------------------------------------------------
+def _down_grads(x, weight, g, d, need_x, need_w, need_b):
+    """The two gradients of the stride-2 conv ``d`` on the dense bf16 g [n, ho, wo, cout], each only where asked: (dx, dw, db)."""
+    dx = dw = db = None
+    if need_w or need_b:
+        dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)
+        db = torch.empty((d.cout,), dtype=torch.float32, device=x.device) if need_b else None
+        ws = torch.empty((K.conv2d_down_bwd_workspace_bytes(d),), dtype=torch.uint8, device=x.device)
+        K.conv2d_down_bwd_weight(x, g, dw, db, ws, d)
+        if not need_w:
+            dw = None
+    if need_x:
+        packed_d = K.pack_conv_weight_down_dev(weight)
+        buf = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=x.device)
+        K.conv2d_down_bwd_data(g, packed_d, buf, d)
+        dx = buf.permute(0, 3, 1, 2)
+    return dx, dw, db
+
+
+class _DownBlockFunction(torch.autograd.Function):
+    """_forward at stride 2 with a backward: prepare (g) on the stride-1 descriptor of the output map, then _down_grads."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act_id):
+        out, d = _forward(x, weight, None if bias is None else bias.detach(), act_id, False, 2)
+        ctx.desc = d
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x, weight, out if act_id != ACT_NONE else None)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        d = ctx.desc
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        need_b = need_b and ctx.has_bias
+        with torch.cuda.device(x.device):
+            dy = dy.permute(0, 2, 3, 1).contiguous()                    # dense [n, ho, wo, cout]; no copy for a channels-last dy
+            g = torch.empty((d.n, d.ho, d.wo, d.cout), dtype=torch.bfloat16, device=x.device)
+            od = K.conv_desc(n=d.n, h=d.ho, w=d.wo, cin=d.cout, in_c_total=d.cout, in_c_offset=0, cout=d.cout, out_c_total=d.cout,
+                             out_c_offset=0, ksize=1, stride=1, act=d.act, kpad=K.roundup(d.cout, 64), cout_pad=d.cout_pad)
+            K.conv2d_bwd_prepare(dy, y, g, od)
+            dx, dw, db = _down_grads(x, weight, g, d, need_x, need_w, need_b)
+        return dx, dw, db, None
+
+
+class _DownBnBlockFunction(torch.autograd.Function):
+    """_bn_forward at stride 2 (training=True) with a backward: conv_bn_block's batch-norm backward (g, dgamma, dbeta), then _down_grads."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, running, momentum, eps, act_id):
+        out, d, z, saved = _bn_forward(x, weight, gamma.detach(), beta.detach(), running, momentum, eps, act_id, 2)
+        ctx.desc, ctx.act_id = d, act_id
+        ctx.save_for_backward(x, weight, z, saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, z, saved = ctx.saved_tensors
+        d = ctx.desc
+        need_x, need_w, need_g, need_b = ctx.needs_input_grad[:4]
+        dgamma = dbeta = g = None
+        with torch.cuda.device(x.device):
+            dy = dy.permute(0, 2, 3, 1).contiguous()
+            if need_x or need_w:
+                g = torch.empty_like(z)
+            if need_g:
+                dgamma = torch.empty((d.cout,), dtype=torch.float32, device=x.device)
+            if need_b:
+                dbeta = torch.empty((d.cout,), dtype=torch.float32, device=x.device)
+            ws = torch.empty((K.bn_workspace_bytes(d.n * d.ho * d.wo, d.cout),), dtype=torch.uint8, device=x.device)
+            K.bn_act_bwd(dy, z, saved, ctx.act_id, True, g, dgamma, dbeta, ws)
+            dx, dw, _ = _down_grads(x, weight, g, d, need_x, need_w, False)
+        return dx, dw, dgamma, dbeta, None, None, None, None
+
+
+def _down_check(name, x, weight, act):
+    """The argument checks the two downsample ops share (ValueError before any launch)."""
+    if not isinstance(x, torch.Tensor) or not isinstance(weight, torch.Tensor) or x.dim() != 4 or weight.dim() != 4:
+        raise ValueError(f"{name}: x must be [n, cin, h, w] and weight [cout, cin, 3, 3]")
+    if act not in _ACTS:
+        raise ValueError(f"{name}: act must be 'leaky' or 'none', not {act!r}")
+    cout, cin, k, k2 = weight.shape
+    if k != 3 or k2 != 3:
+        raise ValueError(f"{name}: kernel {k}x{k2} unsupported (the downsample is 3x3, stride 2, pad 1)")
+    if x.shape[1] != cin:
+        raise ValueError(f"{name}: x has {x.shape[1]} channels, weight expects {cin}")
+    if min(x.shape) < 1 or cout < 1:
+        raise ValueError(f"{name}: empty tensor")
+    if cout % 8:
+        raise ValueError(f"{name}: cout % 8 == 0 is required (cout {cout})")
+    if weight.dtype != torch.float32:
+        raise ValueError(f"{name}: weight must be float32 [cout, cin, 3, 3]")
+
+
+def down_block(x, weight, bias=None, *, act="leaky"):
+    """``act(conv2d(x, bf16(weight), stride=2, padding=1) + bias)`` on the device, differentiable once: conv_block's contract for the
+    3x3 stride-2 downsample of Darknet-53 (ConvBlock(3x3, stride 2) with its BN folded).  The output map is
+    ``((h - 1) // 2 + 1, (w - 1) // 2 + 1)``, torch's for even and odd maps.
+
+    x       [n, cin, h, w]; zero-copy for bfloat16 dense channels-last with ``cin % 8 == 0``, otherwise converted by torch as in conv_block.
+    weight  float32 [cout, cin, 3, 3] on the device, ``cout % 8 == 0``.      bias  float32 [cout] or None.
+    act     "leaky" (LeakyReLU(0.1)) or "none".
+    Returns an NCHW-shaped channels-last bfloat16 tensor.  Under ``torch.no_grad()``, or when no input requires grad, only the forward
+    runs.  Gradients: x bf16 (rounded once), weight and bias float32, each computed only where asked; two runs give the same bits.
+    Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no CPU fallback)."""
+    _down_check("down_block", x, weight, act)
+    cout = weight.shape[0]
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (cout,)):
+        raise ValueError("down_block: bias must be float32 [cout]")
+    if not (x.is_cuda and weight.is_cuda and (bias is None or bias.is_cuda)):
+        raise RuntimeError("pytorch_yolo_amd.down_block runs on a ROCm device only (no CPU fallback)")
+    x, weight = _to_kernel_layout(x, weight)
+    act_id = _ACTS[act]
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return _DownBlockFunction.apply(x, weight, bias, act_id)
+    return _forward(x.detach(), weight.detach(), None if bias is None else bias.detach(), act_id, False, 2)[0]
+
+
+def down_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *, training=True, momentum=0.1, eps=1e-5, act="leaky"):
+    """``act(batch_norm(conv2d(x, bf16(weight), stride=2, padding=1)))`` on the device, differentiable once: conv_bn_block's contract
+    for the 3x3 stride-2 downsample (Conv2d(3x3, stride 2, bias=False) -> BatchNorm2d -> LeakyReLU(0.1)) as the reference trains it.
+
+    Arguments, running statistics, ``training=False`` (down_block on the weights folded by torch) and errors are conv_bn_block's; the
+    statistics run over the ``n ho wo`` output pixels."""
+    _down_check("down_bn_block", x, weight, act)
+    _check_momentum_eps("down_bn_block", momentum, eps)
+    training = bool(training)
+    vectors = _check_bn_vectors("down_bn_block", weight.shape[0], gamma, beta, running_mean, running_var, training)
+    ho, wo = (x.shape[2] - 1) // 2 + 1, (x.shape[3] - 1) // 2 + 1
+    if training and x.shape[0] * ho * wo < 2:
+        raise ValueError("down_bn_block: expected more than 1 value per channel when training")
+    if not (x.is_cuda and weight.is_cuda and all(t is None or t.is_cuda for _, t in vectors)):
+        raise RuntimeError("pytorch_yolo_amd.down_bn_block runs on a ROCm device only (no CPU fallback)")
+    if not training:        # frozen statistics: the folded layer
+        s = gamma / torch.sqrt(running_var.detach() + eps)
+        return down_block(x, weight * s.reshape(-1, 1, 1, 1), beta - running_mean.detach() * s, act=act)
+    x, weight = _to_kernel_layout(x, weight)
+    gamma, beta = gamma.contiguous(), beta.contiguous()
+    running = _running("down_bn_block", running_mean, running_var)
+    act_id = _ACTS[act]
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or gamma.requires_grad or beta.requires_grad):
+        return _DownBnBlockFunction.apply(x, weight, gamma, beta, running, float(momentum), float(eps), act_id)
+    return _bn_forward(x.detach(), weight.detach(), gamma.detach(), beta.detach(), running, float(momentum), float(eps), act_id, 2)[0]
