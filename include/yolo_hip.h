@@ -214,6 +214,35 @@ YOLO_API int yolo_bn_act_fwd(const void* z, const float* saved, void* y, long lo
 YOLO_API int yolo_bn_act_bwd(const void* dy, int dy_dtype, const void* z, const float* saved, long long pixels, int c, int act,
                              int batch_stats, void* g, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, yolo_stream_t s);
 
+/* ---- the layers between the convs of a training step of YOLOv3 / YOLOv3-SPP, each with its backward; bf16 mode: csrc/route.hip and one
+ *  entry of csrc/batchnorm.hip, DESIGN.md 3.6f.  Every map is bf16, DENSE NHWC, every channel count % 8 == 0 (16-byte accesses).  No
+ *  atomics, no workspace; every output element is written exactly once and every sum has a fixed order, so two runs give the same bits.
+ *  Every fp32 operation below is rounded on its own (no contraction).
+ *  yolo_bn_act_add_fwd: yolo_bn_act_fwd's pass with the residual unit's add (models/yolov3_spp.py:12-14,42-46) fused in:
+ *      a = f32(z) scale + shift;  t = a > 0 ? a : 0.1f a  (act none: t = a);  y_preadd = bf16_rne(t) (only where the pointer is given: the
+ *      tensor the reference routes to the FPN from the last unit of down3 / down4);  y = bf16_rne(t + f32(residual)).
+ *    The backward needs no entry of its own: dy (plus the gradient of y_preadd where it was routed) goes to yolo_bn_act_bwd, and dy
+ *    unchanged is the residual's gradient.
+ *  yolo_spp_train_fwd: y [n,h,w,4c] = cat([maxpool5(x), maxpool9(x), maxpool13(x), x], channel) of x [n,h,w,c] (models/yolov3_spp.py:75-77,
+ *    129: stride 1, pad k / 2 with -inf), and idx [n,h,w,3c] uint8: the argmax of each window as (row offset) k + (column offset) inside
+ *    the window (0 .. k k - 1; the centre is (k k - 1) / 2).  The argmax is the window's FIRST maximum in row-major order (torch's rule);
+ *    a NaN is never greater, so x must hold no NaN.  Any h, w >= 1 (a map smaller than the windows included).
+ *  yolo_spp_bwd: dx [n,h,w,c] from dy [n,h,w,4c] and idx, as a gather: acc = 0; for k = 5, 9, 13 in turn, for the window centres q within
+ *    k / 2 of the pixel p in row-major order: acc = acc + f32(dy_k[q]) where idx_k[q] names p; dx[p] = bf16_rne(acc + f32(dy_pass[p])).
+ *    Maps of up to 1600 pixels (40 x 40) are staged in LDS per (image, 8 channels); larger maps run the same code on global memory.
+ *  yolo_upsample2_concat_fwd: y [n,2h,2w,ca+cb] = cat([nearest_x2(a), b], channel) of a [n,h,w,ca] and b [n,2h,2w,cb]
+ *    (models/yolo_layer.py:6-22).
+ *  yolo_upsample2_concat_bwd: da [n,h,w,ca] = bf16_rne(((f32(dy00) + f32(dy01)) + f32(dy10)) + f32(dy11)) over each 2x2 block of
+ *    dy[..., :ca] (row-major), db [n,2h,2w,cb] = dy[..., ca:]; da or db may be NULL (not wanted), not both.
+ *  YOLO_E_ARG before any launch for an empty shape, a channel count that is no positive multiple of 8, an act other than YOLO_ACT_NONE /
+ *  YOLO_ACT_LEAKY01, a null or misaligned pointer (the bf16 maps and saved: 16 bytes; idx: 8). */
+YOLO_API int yolo_bn_act_add_fwd(const void* z, const float* saved, const void* residual, void* y, void* y_preadd, long long pixels, int c,
+                                 int act, yolo_stream_t s);
+YOLO_API int yolo_spp_train_fwd(const void* x, void* y, void* idx, int n, int h, int w, int c, yolo_stream_t s);
+YOLO_API int yolo_spp_bwd(const void* dy, const void* idx, void* dx, int n, int h, int w, int c, yolo_stream_t s);
+YOLO_API int yolo_upsample2_concat_fwd(const void* a, const void* b, void* y, int n, int h, int w, int ca, int cb, yolo_stream_t s);
+YOLO_API int yolo_upsample2_concat_bwd(const void* dy, void* da, void* db, int n, int h, int w, int ca, int cb, yolo_stream_t s);
+
 /* First layer fused with the input packing: x is the caller's f32 NCHW batch [n,cin_real,h,w] (cin_real <= 8),
  * w_packed / bias as for yolo_conv2d_fwd with d->cin = 8; 3x3 / pad 1, bf16 NHWC output: stride 1 with cout 16 or 32
  * (Darknet), or stride 2 with cout 32 (MobileNetV2's first layer). */

@@ -39,6 +39,7 @@ SOURCES = {
     "loss.hip": ["-ffp-contract=off"],
     "coco_eval.hip": ["-ffp-contract=off"],
     "batchnorm.hip": ["-ffp-contract=off"],
+    "route.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
           "-Wall", "-Wno-unused-function"]

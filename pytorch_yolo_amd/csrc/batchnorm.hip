@@ -3,6 +3,7 @@
 //   stats_kernel + stats_finalize_kernel   S1 = sum z, S2 = sum z z in float64 -> saved = {mean, invstd, scale, shift}, running stats
 //   eval_stats_kernel                      the same four vectors from the running statistics
 //   act_fwd_kernel                         y = bf16(act(f32(z) scale + shift))
+//   act_add_fwd_kernel                     the same with the residual add: y = bf16(act(..) + f32(residual)), y_preadd = bf16(act(..))
 //   bwd_reduce_kernel + bwd_finalize_kernel  B = sum ga, G = sum ga xh in float64 -> dgamma, dbeta, c1, c2
 //   act_bwd_kernel                         g = bf16(scale ((ga - c1) - xh c2)), the operand of yolo_conv2d_bwd_weight / _data
 // Every pass is a stream of 16-byte loads; a thread owns one chunk of 8 channels.  The two reductions split the rows over blockIdx.x
@@ -286,6 +287,29 @@ __global__ __launch_bounds__(256) void act_fwd_kernel(const bf16_t* __restrict__
   *reinterpret_cast<bf16x8*>(y + idx * 8) = out;
 }
 
+// the same pass with the residual unit's add: t = act(a); y_preadd = bf16(t) (where wanted); y = bf16(t + f32(residual))
+template <bool PREADD>
+__global__ __launch_bounds__(256) void act_add_fwd_kernel(const bf16_t* __restrict__ z, const float* __restrict__ saved,
+                                                          const bf16_t* __restrict__ res, bf16_t* __restrict__ y, bf16_t* __restrict__ y_preadd,
+                                                          long total, int c, int chunks, int leaky) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c0 = (int)(idx % chunks) * 8;
+  float zv[8], rv[8], scale[8], shift[8];
+  load8(z + idx * 8, zv), load8(res + idx * 8, rv);
+  load8f(saved + 2 * (size_t)c + c0, scale), load8f(saved + 3 * (size_t)c + c0, shift);
+  bf16x8 out, pre;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float a = zv[j] * scale[j] + shift[j];
+    const float t = (!leaky || a > 0.f) ? a : 0.1f * a;
+    pre[j] = (bf16_t)t;
+    out[j] = (bf16_t)(t + rv[j]);
+  }
+  *reinterpret_cast<bf16x8*>(y + idx * 8) = out;
+  if (PREADD) *reinterpret_cast<bf16x8*>(y_preadd + idx * 8) = pre;
+}
+
 template <typename TDY>
 __global__ __launch_bounds__(256) void act_bwd_kernel(const TDY* __restrict__ dy, const bf16_t* __restrict__ z, const float* __restrict__ saved,
                                                       const float* __restrict__ c12, bf16_t* __restrict__ g, long total, int c, int chunks,
@@ -390,6 +414,23 @@ extern "C" int yolo_bn_act_fwd(const void* z, const float* saved, void* y, long 
   hipLaunchKernelGGL(act_fwd_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)z, saved, (bf16_t*)y, total, c, c / 8,
                      act == YOLO_ACT_LEAKY01);
   return yolo_check_launch("bn_act_fwd");
+}
+
+extern "C" int yolo_bn_act_add_fwd(const void* z, const float* saved, const void* residual, void* y, void* y_preadd, long long pixels, int c,
+                                   int act, yolo_stream_t s) {
+  if (const int rc = bn_check(pixels, c, "bn_act_add_fwd")) return rc;
+  if (const int rc = act_check(act, "bn_act_add_fwd")) return rc;
+  YOLO_REQUIRE(z && saved && residual && y, "bn_act_add_fwd: null pointer");
+  YOLO_REQUIRE(al(z, 16) && al(saved, 16) && al(residual, 16) && al(y, 16) && al(y_preadd, 16), "bn_act_add_fwd: misaligned pointer");
+  const long total = (long)pixels * (c / 8);
+  const int leaky = act == YOLO_ACT_LEAKY01;
+  if (y_preadd)
+    hipLaunchKernelGGL(act_add_fwd_kernel<true>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)z, saved,
+                       (const bf16_t*)residual, (bf16_t*)y, (bf16_t*)y_preadd, total, c, c / 8, leaky);
+  else
+    hipLaunchKernelGGL(act_add_fwd_kernel<false>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)z, saved,
+                       (const bf16_t*)residual, (bf16_t*)y, (bf16_t*)nullptr, total, c, c / 8, leaky);
+  return yolo_check_launch("bn_act_add_fwd");
 }
 
 extern "C" int yolo_bn_act_bwd(const void* dy, int dy_dtype, const void* z, const float* saved, long long pixels, int c, int act, int batch_stats,

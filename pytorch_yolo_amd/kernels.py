@@ -18,7 +18,8 @@ __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pic
            "COCO_T", "COCO_R", "COCO_A", "COCO_M", "pack_conv_weight", "roundup", "run_ops",
            "conv2d_bwd_workspace_bytes", "conv2d_bwd_pick", "conv2d_bwd_prepare", "conv2d_bwd_weight", "conv2d_bwd_data", "pack_conv_weight_dev",
            "conv2d_down_bwd_workspace_bytes", "conv2d_down_bwd_pick", "conv2d_down_bwd_weight", "conv2d_down_bwd_data", "pack_conv_weight_down_dev",
-           "bn_workspace_bytes", "bn_pick", "bn_train_stats", "bn_eval_stats", "bn_act_fwd", "bn_act_bwd"]
+           "bn_workspace_bytes", "bn_pick", "bn_train_stats", "bn_eval_stats", "bn_act_fwd", "bn_act_bwd",
+           "bn_act_add_fwd", "spp_train_fwd", "spp_bwd", "upsample2_concat_fwd", "upsample2_concat_bwd"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -506,6 +507,81 @@ def bn_act_bwd(dy, z, saved, act, batch_stats, g, dgamma, dbeta, workspace):
                                  _ptr(dgamma), _ptr(dbeta), _ptr(workspace), workspace.numel() * workspace.element_size(), stream_ptr()),
           "bn_act_bwd")
     return g, dgamma, dbeta
+
+
+# ---- the layers between the convs of a training step (csrc/route.hip, one entry of csrc/batchnorm.hip) ---------------
+def bn_act_add_fwd(z, saved, residual, y, y_preadd, act):
+    """bn_act_fwd with the residual add: y = bf16(t + f32(residual)), y_preadd (may be None) = bf16(t), t = act(f32(z) scale + shift)."""
+    _need_cuda(z, saved, residual, y, y_preadd)
+    c = z.shape[-1]
+    pixels = z.numel() // c
+    _bn_map(z, pixels, c, "bn_act_add_fwd: z")
+    _bn_map(residual, pixels, c, "bn_act_add_fwd: residual")
+    _bn_map(y, pixels, c, "bn_act_add_fwd: y")
+    if y_preadd is not None:
+        _bn_map(y_preadd, pixels, c, "bn_act_add_fwd: y_preadd")
+    _bn_vec(saved, c, "bn_act_add_fwd: saved", 4)
+    check(load().yolo_bn_act_add_fwd(_ptr(z), _ptr(saved), _ptr(residual), _ptr(y), _ptr(y_preadd), pixels, c, int(act), stream_ptr()),
+          "bn_act_add_fwd")
+    return y, y_preadd
+
+
+def _nhwc(t, shape, what, dtype=torch.bfloat16):
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{what} must be contiguous {dtype} {list(shape)}")
+
+
+def spp_train_fwd(x, y, idx):
+    """y [n,h,w,4c] = cat([maxpool5(x), maxpool9(x), maxpool13(x), x]) of the dense bf16 x [n,h,w,c]; idx uint8 [n,h,w,3c]: the windows'
+    argmax offsets (first maximum in row-major order)."""
+    _need_cuda(x, y, idx)
+    if x.dim() != 4:
+        raise RuntimeError("spp_train_fwd: x must be [n, h, w, c]")
+    n, h, w, c = x.shape
+    _nhwc(x, (n, h, w, c), "spp_train_fwd: x")
+    _nhwc(y, (n, h, w, 4 * c), "spp_train_fwd: y")
+    _nhwc(idx, (n, h, w, 3 * c), "spp_train_fwd: idx", torch.uint8)
+    check(load().yolo_spp_train_fwd(_ptr(x), _ptr(y), _ptr(idx), n, h, w, c, stream_ptr()), "spp_train_fwd")
+    return y, idx
+
+
+def spp_bwd(dy, idx, dx):
+    """dx [n,h,w,c] from dy [n,h,w,4c] and spp_train_fwd's idx: a gather with a fixed fp32 summation order, rounded once."""
+    _need_cuda(dy, idx, dx)
+    if dx.dim() != 4:
+        raise RuntimeError("spp_bwd: dx must be [n, h, w, c]")
+    n, h, w, c = dx.shape
+    _nhwc(dx, (n, h, w, c), "spp_bwd: dx")
+    _nhwc(dy, (n, h, w, 4 * c), "spp_bwd: dy")
+    _nhwc(idx, (n, h, w, 3 * c), "spp_bwd: idx", torch.uint8)
+    check(load().yolo_spp_bwd(_ptr(dy), _ptr(idx), _ptr(dx), n, h, w, c, stream_ptr()), "spp_bwd")
+    return dx
+
+
+def upsample2_concat_fwd(a, b, y):
+    """y [n,2h,2w,ca+cb] = cat([nearest_x2(a), b]) of the dense bf16 a [n,h,w,ca] and b [n,2h,2w,cb]."""
+    _need_cuda(a, b, y)
+    if a.dim() != 4 or b.dim() != 4:
+        raise RuntimeError("upsample2_concat_fwd: a must be [n, h, w, ca] and b [n, 2h, 2w, cb]")
+    n, h, w, ca = a.shape
+    cb = b.shape[3]
+    _nhwc(a, (n, h, w, ca), "upsample2_concat_fwd: a")
+    _nhwc(b, (n, 2 * h, 2 * w, cb), "upsample2_concat_fwd: b")
+    _nhwc(y, (n, 2 * h, 2 * w, ca + cb), "upsample2_concat_fwd: y")
+    check(load().yolo_upsample2_concat_fwd(_ptr(a), _ptr(b), _ptr(y), n, h, w, ca, cb, stream_ptr()), "upsample2_concat_fwd")
+    return y
+
+
+def upsample2_concat_bwd(dy, da, db, *, n, h, w, ca, cb):
+    """da [n,h,w,ca] = the fp32 2x2 block sums of dy[..., :ca] rounded once, db [n,2h,2w,cb] = dy[..., ca:]; either may be None."""
+    _need_cuda(dy, da, db)
+    _nhwc(dy, (n, 2 * h, 2 * w, ca + cb), "upsample2_concat_bwd: dy")
+    if da is not None:
+        _nhwc(da, (n, h, w, ca), "upsample2_concat_bwd: da")
+    if db is not None:
+        _nhwc(db, (n, 2 * h, 2 * w, cb), "upsample2_concat_bwd: db")
+    check(load().yolo_upsample2_concat_bwd(_ptr(dy), _ptr(da), _ptr(db), n, h, w, ca, cb, stream_ptr()), "upsample2_concat_bwd")
+    return da, db
 
 
 def conv2d_splitk_plan(desc: YoloConvDesc, has_residual=False, has_preadd=False):

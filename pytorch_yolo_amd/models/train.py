@@ -1,0 +1,120 @@
+"""Training-mode forward of the Darknet-53 models (YOLOv3, YOLOv3-SPP): the reference's ``model.train()(x)`` - batch-statistics BN, the
+raw ``p`` list with a ``grad_fn`` - wired from the differentiable ops of pytorch_yolo_amd.ops.
+
+The wiring (``model._train_wiring``) takes every op from a table, a namespace with the six functions of ``DEVICE_OPS``: the default
+table runs the package's kernels; the tests run the same Python wiring on the CPU with float64 torch restatements of the ops, which is
+how it is compared with the reference without a GPU.  A table function has the signature of the op it stands for.
+"""
+from __future__ import annotations
+
+from types import SimpleNamespace
+
+import torch
+from torch import nn
+
+from .. import ops as _ops
+from .yolo_base import ConvBlock
+
+DEVICE_OPS = SimpleNamespace(conv_block=_ops.conv_block, conv_bn_block=_ops.conv_bn_block, down_bn_block=_ops.down_bn_block,
+                             res_bn_block=_ops.res_bn_block, spp_concat=_ops.spp_concat, upsample_concat=_ops.upsample_concat)
+
+
+def conv_bn(ops, block, x, residual=None, want_preadd=False):
+    """One ConvBlock as it trains (Conv2d(bias=False) -> BatchNorm2d on batch statistics -> LeakyReLU(0.1)), with the residual unit's add
+    where ``residual`` is given.  momentum and eps are the BatchNorm2d's own; its running statistics are updated in place and
+    num_batches_tracked counts the call.  A cout that is no multiple of 8 (the 3 (5 + nc) channels of a ConvBlock head) is padded by
+    torch: zero weights, gamma 1, beta 0 and temporaries of the running tensors; the padded channels have z = 0 and give 0."""
+    conv, bn = block.sequence.conv, block.sequence.batch_norm
+    kw = dict(momentum=bn.momentum, eps=bn.eps)
+    with torch.no_grad():
+        bn.num_batches_tracked += 1
+    w, gamma, beta, rm, rv = conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var
+    if residual is not None:
+        return ops.res_bn_block(x, w, gamma, beta, rm, rv, residual, want_preadd=want_preadd, **kw)
+    if block.stride == 2:
+        return ops.down_bn_block(x, w, gamma, beta, rm, rv, **kw)
+    cout = w.shape[0]
+    pad = -cout % 8
+    if not pad:
+        return ops.conv_bn_block(x, w, gamma, beta, rm, rv, **kw)
+    w = nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, pad))
+    gamma = torch.cat([gamma, gamma.new_ones(pad)])
+    beta = torch.cat([beta, beta.new_zeros(pad)])
+    rm_t, rv_t = torch.cat([rm.detach(), rm.new_zeros(pad)]), torch.cat([rv.detach(), rv.new_ones(pad)])
+    y = ops.conv_bn_block(x, w, gamma, beta, rm_t, rv_t, **kw)[:, :cout]
+    with torch.no_grad():
+        rm.copy_(rm_t[:cout]), rv.copy_(rv_t[:cout])
+    return y
+
+
+def chain(ops, x, modules):
+    """The ConvBlocks of a Sequential in order (its Concat / Upsample markers are wired by the caller)."""
+    for m in modules:
+        if isinstance(m, ConvBlock):
+            x = conv_bn(ops, m, x)
+    return x
+
+
+def head(ops, x, module):
+    """The last layer of a head as float32: a ConvBlock (YOLOv3-SPP's three heads, YOLOv3's third) or a plain biased nn.Conv2d."""
+    if isinstance(module, nn.Conv2d):
+        return ops.conv_block(x, module.weight, module.bias, act="none", out_dtype=torch.float32)
+    y = conv_bn(ops, module, x)
+    return y.float() if y.dtype == torch.bfloat16 else y         # (a table that works in float32 / float64 keeps its dtype)
+
+
+def down_stage(ops, stage, x, need_sub):
+    """One Darknet-53 stage (reference models/yolov3_spp.py:38-46): (x, sub), sub the last unit's branch output before its add."""
+    x = conv_bn(ops, stage.conv0, x)
+    sub = None
+    for i in range(stage.n_units):
+        squeeze, expand = getattr(stage, f"seq{i}")
+        last = need_sub and i == stage.n_units - 1
+        out = conv_bn(ops, expand, conv_bn(ops, squeeze, x), residual=x, want_preadd=last)
+        x, sub = out if last else (out, None)
+    return x, sub
+
+
+def encoder(ops, model, x):
+    """conv1 and the five stages: (x, subs); only downs[2] and downs[3] are routed (reference models/yolov3_spp.py:133,137)."""
+    x = conv_bn(ops, model.conv1, x)
+    subs = []
+    for i, stage in enumerate(model.down):
+        x, sub = down_stage(ops, stage, x, need_sub=i in (2, 3))
+        subs.append(sub)
+    return x, subs
+
+
+def forward_train(model, x, ops=None):
+    """``[p1, p2, p3]``, each ``[bs, 3, ny, nx, 5 + nc]`` contiguous with a grad_fn, as the reference's training-mode forward returns.
+    With the default table: float32 on the device; x float32 NCHW, H and W multiples of 32, bf16 mode, BN not fused."""
+    if not hasattr(model, "_train_wiring"):
+        raise NotImplementedError(
+            "training-mode forward (batch-statistics BN, raw p list) is outside the inference hot path; "
+            "call .eval() first")
+    if model.precision != "bf16":
+        raise NotImplementedError(f"the training-mode forward runs in bf16 mode only (model.precision is {model.precision!r})")
+    if any(getattr(m, "is_fused", False) for m in model.modules()):
+        raise NotImplementedError("the training-mode forward needs the BatchNorm2d layers: this model was fuse()d")
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != model.in_channels or x.shape[0] < 1:
+        raise ValueError(f"expected input [bs,{model.in_channels},H,W], got {tuple(getattr(x, 'shape', ()))}")
+    if x.shape[2] % 32 or x.shape[3] % 32 or min(x.shape[2:]) < 32:
+        raise ValueError(f"the training-mode forward needs H and W to be multiples of 32, got {tuple(x.shape[2:])}")
+    if ops is None:
+        if x.dtype != torch.float32:
+            raise ValueError(f"the training-mode forward takes a float32 NCHW batch, got {x.dtype}")
+        if not x.is_cuda:
+            raise RuntimeError("pytorch_yolo_amd runs on a ROCm device only: move the input to cuda "
+                               "(there is no CPU fallback)")
+        ops = DEVICE_OPS
+    branches = model._train_wiring(ops, x)
+    img_size = max(x.shape[-2:])
+    out = []
+    for b, layer in zip(branches, model.yolo_layers):
+        bs, _, ny, nx = b.shape
+        layer._sync_grid_attrs(ny, nx, img_size, b.device)
+        out.append(b.reshape(bs, layer.n_anchors, layer.n_classes + 5, ny, nx).permute(0, 1, 3, 4, 2).contiguous())
+    # the kernels updated the running statistics through raw pointers: torch's version counters did not move, so a cached eval plan
+    # would keep its stale folded weights
+    model.invalidate()
+    return out

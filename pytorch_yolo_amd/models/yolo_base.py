@@ -220,11 +220,11 @@ class YOLOBase(nn.Module):
 
     def forward(self, x):
         """eval: (io [bs, sum(3*ny*nx), 5+nc], (p_k [bs,3,ny,nx,5+nc], ...)) like the reference
-        (yolov3_spp.py:141-164, yolov3_tiny.py:79-100)."""
+        (yolov3_spp.py:141-164, yolov3_tiny.py:79-100).  training (YOLOv3 and YOLOv3-SPP, the classes with a ``_train_wiring``; every
+        other class raises): the raw list [p_k] with a grad_fn (models/train.py)."""
         if self.training:
-            raise NotImplementedError(
-                "training-mode forward (batch-statistics BN, raw p list) is outside the inference hot path; "
-                "call .eval() first")
+            from .train import forward_train
+            return forward_train(self, x)
         if x.dtype != torch.float32:
             x = x.float()
         x = x.contiguous()

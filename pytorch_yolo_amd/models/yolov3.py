@@ -7,6 +7,7 @@ from __future__ import annotations
 from torch import nn
 
 from .. import engine
+from . import train as T
 from .yolo_base import ConvBlock, YOLOBase
 from .yolo_layer import Concat, Upsample
 from .yolov3_spp import DownSample
@@ -76,3 +77,16 @@ class YOLOv3(YOLOBase):
         g.head(plain_head(g, b2, self.seqy2_3.conv7), self.yolo2)
         z = g.concat([g.upsample2(self.seqy3_1.conv._trace(g, y)), subs[2]])
         g.head(_chain(g, z, self.seqy3_2, f32_last=True), self.yolo3)
+
+    def _train_wiring(self, ops, x):
+        """The same wiring in training mode on the ops of a table (models/train.py): the three raw head maps [bs, 3 (5 + nc), ny, nx]."""
+        x, subs = T.encoder(ops, self, x)
+        x = T.chain(ops, x, self.seq)
+        b1 = T.head(ops, T.conv_bn(ops, self.seq_y1.conv1, x), self.seq_y1.conv2)
+        y = ops.upsample_concat(T.conv_bn(ops, self.seqy2_1.conv, x), subs[3])
+        y = T.chain(ops, y, self.seqy2_2)
+        b2 = T.head(ops, T.conv_bn(ops, self.seqy2_3.conv6, y), self.seqy2_3.conv7)
+        z = ops.upsample_concat(T.conv_bn(ops, self.seqy3_1.conv, y), subs[2])
+        blocks = [m for m in self.seqy3_2 if isinstance(m, ConvBlock)]
+        b3 = T.head(ops, T.chain(ops, z, blocks[:-1]), blocks[-1])
+        return b1, b2, b3

@@ -10,6 +10,7 @@ from __future__ import annotations
 from torch import nn
 
 from .. import engine
+from . import train as T
 from .yolo_base import ConvBlock, MaxPool, YOLOBase
 from .yolo_layer import Concat, Upsample
 
@@ -136,3 +137,17 @@ class YOLOv3SPP(YOLOBase):
 
         z = g.concat([g.upsample2(self.branch3_1[0]._trace(g, y)), subs[2]])       # :136-137
         g.head(self._chain(g, z, self.branch3_2, head_last=True), self.yolo3)
+
+    def _train_wiring(self, ops, x):
+        """The same wiring in training mode on the ops of a table (models/train.py): the three raw head maps [bs, 3 (5 + nc), ny, nx]."""
+        x, subs = T.encoder(ops, self, x)
+        x = T.chain(ops, x, self.sequence_spp)
+        x = T.chain(ops, ops.spp_concat(x), self.branch1_1)                                   # :129
+        b1 = T.head(ops, T.conv_bn(ops, self.branch1_2.conv1, x), self.branch1_2.conv2)
+        y = ops.upsample_concat(T.conv_bn(ops, self.branch2_1[0], x), subs[3])                # :132-133
+        y = T.chain(ops, y, self.branch2_2)
+        b2 = T.head(ops, T.conv_bn(ops, self.branch2_3.conv6, y), self.branch2_3.conv7)
+        z = ops.upsample_concat(T.conv_bn(ops, self.branch3_1[0], y), subs[2])                # :136-137
+        blocks = [m for m in self.branch3_2 if isinstance(m, ConvBlock)]
+        b3 = T.head(ops, T.chain(ops, z, blocks[:-1]), blocks[-1])
+        return b1, b2, b3

@@ -3,7 +3,7 @@
 ``conv_block`` is ConvBlock.forward of the reference (models/yolo_base.py:19-44, BN folded; with ``act="none"`` and
 ``out_dtype=torch.float32`` the plain nn.Conv2d heads of models/yolov3_tiny.py:38,42) at stride 1, 1x1 or 3x3, in bf16 mode, WITH a
 backward: the forward is the launch the models use (yolo_conv2d_fwd), the backward runs csrc/conv_bwd.hip.  The
-models' own forward stays inference-only: ``io, p = model(x)`` has no ``grad_fn``.
+models' eval forward stays inference-only: ``io, p = model(x)`` has no ``grad_fn``.
 
 ``conv_bn_block`` is the same ConvBlock with its BatchNorm2d NOT folded: conv -> batch norm on batch statistics -> LeakyReLU(0.1), the
 layer as the reference trains it.  The conv and its two gradients are conv_block's launches; the statistics, the normalise-and-activate
@@ -14,6 +14,10 @@ the gradients on to weight, gamma and beta.
 ``down_block`` and ``down_bn_block`` are the same two contracts for the downsample, ConvBlock(3x3, stride 2, pad 1) - the five stride-2
 layers of Darknet-53: the forward is again yolo_conv2d_fwd, the two gradients run csrc/conv_down_bwd.hip, the batch
 norm is conv_bn_block's (yolo_bn_* take the n ho wo output pixels).
+
+``res_bn_block``, ``spp_concat`` and ``upsample_concat`` are the layers between those convs in YOLOv3 / YOLOv3-SPP - the residual unit's
+closing ConvBlock with its add, the SPP pyramid, the FPN's upsample + concat - with their backwards (csrc/route.hip, yolo_bn_act_add_fwd;
+DESIGN.md 3.6f); models/train.py wires the training-mode forward of the two models from all seven ops.
 """
 from __future__ import annotations
 
@@ -22,7 +26,7 @@ import torch
 from . import kernels as K
 from ._lib import ACT_LEAKY01, ACT_NONE, DT_BF16, DT_F32
 
-__all__ = ["conv_block", "conv_bn_block", "down_block", "down_bn_block"]
+__all__ = ["conv_block", "conv_bn_block", "down_block", "down_bn_block", "res_bn_block", "spp_concat", "upsample_concat"]
 
 _ACTS = {"leaky": ACT_LEAKY01, "none": ACT_NONE}
 
@@ -277,6 +281,204 @@ def conv_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or gamma.requires_grad or beta.requires_grad):
         return _ConvBnBlockFunction.apply(x, weight, gamma, beta, running, float(momentum), float(eps), act_id)
     return _bn_forward(x.detach(), weight.detach(), gamma.detach(), beta.detach(), running, float(momentum), float(eps), act_id)[0]
+
+
+# ---- the residual unit's closing ConvBlock with the add fused in -------------------------------------------------------------------------
+class _ResBnBlockFunction(torch.autograd.Function):
+    """conv -> batch statistics -> normalise, activate and add the residual in one pass (yolo_bn_act_add_fwd).  The backward is
+    conv_bn_block's on dy (+ the gradient of y_preadd where it was routed, summed in fp32 by torch); dy itself is the residual's."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, residual, running, momentum, eps, want_preadd):
+        z, d = _forward(x, weight, None, ACT_NONE, False)
+        z = z.permute(0, 2, 3, 1)
+        with torch.cuda.device(x.device):
+            saved = torch.empty((4, d.cout), dtype=torch.float32, device=x.device)
+            ws = torch.empty((K.bn_workspace_bytes(d.n * d.h * d.w, d.cout),), dtype=torch.uint8, device=x.device)
+            K.bn_train_stats(z, gamma.detach(), beta.detach(), eps, momentum, running[0], running[1], saved, ws)
+            y = torch.empty_like(z)
+            pre = torch.empty_like(z) if want_preadd else None
+            K.bn_act_add_fwd(z, saved, residual.detach().permute(0, 2, 3, 1), y, pre, ACT_LEAKY01)
+        ctx.desc = d
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, weight, z, saved)
+        y = y.permute(0, 3, 1, 2)
+        return (y, pre.permute(0, 3, 1, 2)) if want_preadd else y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, dpre=None):
+        x, weight, z, saved = ctx.saved_tensors
+        d = ctx.desc
+        need_x, need_w, need_g, need_b, need_r = ctx.needs_input_grad[:5]
+        dx = dw = dgamma = dbeta = g = None
+        if dy is None and dpre is None:
+            return (None,) * 9
+        dres = dy if need_r else None
+        if dy is not None and dpre is not None:
+            dy = dy.float() + dpre.float()                              # one fp32 sum: yolo_bn_act_bwd takes an fp32 dy
+        elif dy is None:
+            dy = dpre
+        with torch.cuda.device(x.device):
+            if need_x or need_w or need_g or need_b:
+                dy = dy.permute(0, 2, 3, 1).contiguous()
+                if need_x or need_w:
+                    g = torch.empty_like(z)
+                if need_g:
+                    dgamma = torch.empty((d.cout,), dtype=torch.float32, device=x.device)
+                if need_b:
+                    dbeta = torch.empty((d.cout,), dtype=torch.float32, device=x.device)
+                ws = torch.empty((K.bn_workspace_bytes(d.n * d.h * d.w, d.cout),), dtype=torch.uint8, device=x.device)
+                K.bn_act_bwd(dy, z, saved, ACT_LEAKY01, True, g, dgamma, dbeta, ws)
+            if need_w:
+                dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)
+                ws = torch.empty((K.conv2d_bwd_workspace_bytes(d),), dtype=torch.uint8, device=x.device)
+                K.conv2d_bwd_weight(x, g, dw, None, ws, d)
+            if need_x:
+                packed_t, _, _ = K.pack_conv_weight_dev(weight, d.cout, transposed=True)
+                buf = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=x.device)
+                K.conv2d_bwd_data(g, packed_t, buf, d)
+                dx = buf.permute(0, 3, 1, 2)
+        return dx, dw, dgamma, dbeta, dres, None, None, None, None
+
+
+def _dense_bf16(t):
+    """t as bfloat16, dense channels-last, by torch operations (torch differentiates them)."""
+    if t.dtype != torch.bfloat16:
+        t = t.to(torch.bfloat16)
+    if not t.permute(0, 2, 3, 1).is_contiguous():
+        t = t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    return t
+
+
+def res_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, residual=None, *, want_preadd=False, training=True,
+                 momentum=0.1, eps=1e-5):
+    """``leaky(batch_norm(conv2d(x, bf16(weight), padding=k // 2))) + residual`` on the device, differentiable once: the closing ConvBlock
+    of a Darknet-53 residual unit with its add (reference models/yolov3_spp.py:12-14,42-46), the add fused into the normalise-and-activate
+    pass (yolo_bn_act_add_fwd).
+
+    conv_bn_block's contract at stride 1 with LeakyReLU(0.1) and ``training=True`` (anything else raises ValueError).
+    residual    [n, cout, h, w]; bfloat16 dense channels-last is taken as it is, anything else is converted by torch.
+    want_preadd also return ``y_preadd = bf16(leaky(batch_norm(..)))``, the branch output before the add (what the reference routes to the
+                FPN from the last unit of down3 / down4): ``(y, y_preadd)``; both carry gradients.
+    Gradients: x bf16, weight, gamma and beta float32, residual the incoming gradient of y unchanged; each computed only where asked."""
+    if not isinstance(x, torch.Tensor) or not isinstance(weight, torch.Tensor) or x.dim() != 4 or weight.dim() != 4:
+        raise ValueError("res_bn_block: x must be [n, cin, h, w] and weight [cout, cin, k, k]")
+    if not training:
+        raise ValueError("res_bn_block: training=True only (the frozen layer is the models' inference path)")
+    _check_momentum_eps("res_bn_block", momentum, eps)
+    cout, cin, k, k2 = weight.shape
+    if k != k2 or k not in (1, 3):
+        raise ValueError(f"res_bn_block: kernel {k}x{k2} unsupported (1x1 or 3x3)")
+    if x.shape[1] != cin:
+        raise ValueError(f"res_bn_block: x has {x.shape[1]} channels, weight expects {cin}")
+    if min(x.shape) < 1 or cout < 1:
+        raise ValueError("res_bn_block: empty tensor")
+    if cout % 8:
+        raise ValueError(f"res_bn_block: cout % 8 == 0 is required (cout {cout})")
+    if weight.dtype != torch.float32:
+        raise ValueError("res_bn_block: weight must be float32 [cout, cin, k, k]")
+    if not isinstance(residual, torch.Tensor) or tuple(residual.shape) != (x.shape[0], cout, x.shape[2], x.shape[3]):
+        raise ValueError("res_bn_block: residual must be [n, cout, h, w]")
+    vectors = _check_bn_vectors("res_bn_block", cout, gamma, beta, running_mean, running_var, True)
+    if x.shape[0] * x.shape[2] * x.shape[3] < 2:
+        raise ValueError("res_bn_block: expected more than 1 value per channel when training")
+    if not (x.is_cuda and weight.is_cuda and residual.is_cuda and all(t is None or t.is_cuda for _, t in vectors)):
+        raise RuntimeError("pytorch_yolo_amd.res_bn_block runs on a ROCm device only (no CPU fallback)")
+    x, weight = _to_kernel_layout(x, weight)
+    residual = _dense_bf16(residual)
+    gamma, beta = gamma.contiguous(), beta.contiguous()
+    running = _running("res_bn_block", running_mean, running_var)
+    return _ResBnBlockFunction.apply(x, weight, gamma, beta, residual, running, float(momentum), float(eps), bool(want_preadd))
+
+
+# ---- the SPP pyramid and the FPN's upsample + concat -------------------------------------------------------------------------------------
+class _SppConcatFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        xn = x.permute(0, 2, 3, 1)
+        n, h, w, c = xn.shape
+        with torch.cuda.device(x.device):
+            y = torch.empty((n, h, w, 4 * c), dtype=torch.bfloat16, device=x.device)
+            idx = torch.empty((n, h, w, 3 * c), dtype=torch.uint8, device=x.device)
+            K.spp_train_fwd(xn, y, idx)
+        ctx.save_for_backward(idx)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        idx, = ctx.saved_tensors
+        n, h, w, c3 = idx.shape
+        with torch.cuda.device(idx.device):
+            dy = _dense_bf16(dy).permute(0, 2, 3, 1)
+            dx = torch.empty((n, h, w, c3 // 3), dtype=torch.bfloat16, device=idx.device)
+            K.spp_bwd(dy, idx, dx)
+        return dx.permute(0, 3, 1, 2)
+
+
+class _UpsampleConcatFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        an, bn = a.permute(0, 2, 3, 1), b.permute(0, 2, 3, 1)
+        n, h, w, ca = an.shape
+        ctx.dims = (n, h, w, ca, bn.shape[3])
+        with torch.cuda.device(a.device):
+            y = torch.empty((n, 2 * h, 2 * w, ca + bn.shape[3]), dtype=torch.bfloat16, device=a.device)
+            K.upsample2_concat_fwd(an, bn, y)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        n, h, w, ca, cb = ctx.dims
+        need_a, need_b = ctx.needs_input_grad
+        da = db = None
+        if not (need_a or need_b):
+            return None, None
+        with torch.cuda.device(dy.device):
+            dy = _dense_bf16(dy).permute(0, 2, 3, 1)
+            if need_a:
+                da = torch.empty((n, h, w, ca), dtype=torch.bfloat16, device=dy.device)
+            if need_b:
+                db = torch.empty((n, 2 * h, 2 * w, cb), dtype=torch.bfloat16, device=dy.device)
+            K.upsample2_concat_bwd(dy, da, db, n=n, h=h, w=w, ca=ca, cb=cb)
+        return (None if da is None else da.permute(0, 3, 1, 2)), (None if db is None else db.permute(0, 3, 1, 2))
+
+
+def _check_map(name, what, t):
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+        raise ValueError(f"{name}: {what} must be [n, c, h, w]")
+    if min(t.shape) < 1:
+        raise ValueError(f"{name}: empty tensor")
+    if t.shape[1] % 8:
+        raise ValueError(f"{name}: {what} needs c % 8 == 0 (c {t.shape[1]})")
+
+
+def spp_concat(x):
+    """``cat([max_pool2d(x, 5, 1, 2), max_pool2d(x, 9, 1, 4), max_pool2d(x, 13, 1, 6), x], 1)`` on the device, differentiable once: the SPP
+    pyramid of YOLOv3-SPP (reference models/yolov3_spp.py:75-77,129).  x [n, c, h, w], ``c % 8 == 0``, any h, w >= 1; bfloat16 dense
+    channels-last is taken as it is, anything else is converted by torch.  Returns bfloat16 [n, 4c, h, w], channels-last.  The gradient
+    of a window goes to its first maximum in row-major order (torch's rule), summed in fp32 in a fixed order and rounded once.
+    Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no CPU fallback)."""
+    _check_map("spp_concat", "x", x)
+    if not x.is_cuda:
+        raise RuntimeError("pytorch_yolo_amd.spp_concat runs on a ROCm device only (no CPU fallback)")
+    return _SppConcatFunction.apply(_dense_bf16(x))
+
+
+def upsample_concat(a, b):
+    """``cat([interpolate(a, scale_factor=2, mode="nearest"), b], 1)`` on the device, differentiable once: the FPN's Upsample + Concat
+    (reference models/yolo_layer.py:6-22).  a [n, ca, h, w], b [n, cb, 2h, 2w], ``ca % 8 == 0`` and ``cb % 8 == 0``; converted like
+    spp_concat's x.  Returns bfloat16 [n, ca + cb, 2h, 2w], channels-last.  Gradients: a the fp32 sum of each 2x2 block rounded once, b
+    the copy of its slice; each computed only where asked.  Errors as spp_concat."""
+    _check_map("upsample_concat", "a", a)
+    _check_map("upsample_concat", "b", b)
+    if tuple(b.shape[0:1] + b.shape[2:]) != (a.shape[0], 2 * a.shape[2], 2 * a.shape[3]):
+        raise ValueError(f"upsample_concat: b {tuple(b.shape)} must be [n, cb, 2h, 2w] of a {tuple(a.shape)}")
+    if not (a.is_cuda and b.is_cuda):
+        raise RuntimeError("pytorch_yolo_amd.upsample_concat runs on a ROCm device only (no CPU fallback)")
+    return _UpsampleConcatFunction.apply(_dense_bf16(a), _dense_bf16(b))
 
 
 # ---- the downsample: ConvBlock(3x3, stride 2, pad 1) ---------------------------------------------------------------------------------------
