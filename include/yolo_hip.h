@@ -243,6 +243,35 @@ YOLO_API int yolo_spp_bwd(const void* dy, const void* idx, void* dx, int n, int 
 YOLO_API int yolo_upsample2_concat_fwd(const void* a, const void* b, void* y, int n, int h, int w, int ca, int cb, yolo_stream_t s);
 YOLO_API int yolo_upsample2_concat_bwd(const void* dy, void* da, void* db, int n, int h, int w, int ca, int cb, yolo_stream_t s);
 
+/* ---- the max-pools of a training step of YOLOv3-tiny / LiteYOLOv3, with their backward; bf16 mode: csrc/pool_train.hip, one entry of
+ *  csrc/batchnorm.hip and two of csrc/route.hip, DESIGN.md 3.6g.  The conventions of the block above: bf16, DENSE NHWC, c % 8 == 0, no
+ *  atomics, no workspace, every output element written exactly once, every sum in a fixed order, no contraction.
+ *  yolo_maxpool_train_fwd: the reference's MaxPool (models/yolo_base.py:60-66; inside ConvPoolBlock :69-80; nn.MaxPool2d(2, 2) at
+ *    models/yolov3_tiny.py:26) of x [n,h,w,c].  stride 2: y [n,h/2,w/2,c] = MaxPool2d(2, 2)(x), floor: an odd last row or column is
+ *    dropped; tap 2i + j of the window at (oy, ox) is the pixel (2oy + i, 2ox + j).  stride 1: y [n,h,w,c] = MaxPool2d(2, 1, padding=1,
+ *    dilation=2)(x), the form MaxPool(2, 1) turns into (:62-64): tap 2i + j of the window at (y, x) is the diagonal neighbour
+ *    (y - 1 + 2i, x - 1 + 2j), padded with -inf; h >= 2 and w >= 2 (on a smaller map a window can be all padding).  idx (uint8, y's
+ *    shape) is the tap number 0..3 of the window's FIRST maximum among its in-bounds taps in row-major order: a later tap replaces the
+ *    running maximum only when strictly greater (torch's rule, yolo_spp_train_fwd's).  A NaN is never greater: x must hold no NaN.
+ *  yolo_maxpool_bwd: dx [n,h,w,c], every element written, from dy and idx (y's shape).  stride 2: dx[p] = dy[q] where idx[q] names p
+ *    inside its own 2x2 block q, otherwise 0 (a dropped odd row or column: 0); a copy, nothing is summed.  stride 1: a gather over the
+ *    four windows that can hold p, their centres q = p + (-1,-1), (-1,+1), (+1,-1), (+1,+1) in that order (p is their tap 3, 2, 1, 0):
+ *    acc = 0; acc = acc + f32(dy[q]) where q is in bounds and idx[q] names p; dx[p] = bf16_rne(acc).
+ *  yolo_bn_act_pool_fwd: yolo_bn_act_fwd's pass over z [n,h,w,c] with the stride-2 pool inside it (ConvPoolBlock as it trains): per tap
+ *    t = bf16_rne(act(f32(z) scale + shift)); the four t of a block are compared as bf16 values under the first-maximum rule (the
+ *    activated values, not z: gamma can be negative); y [n,h/2,w/2,c] and idx are written, the full-resolution activation never is.
+ *    Bit-equal to yolo_bn_act_fwd followed by yolo_maxpool_train_fwd(stride 2).
+ *  yolo_concat_upsample2_fwd / _bwd: yolo_upsample2_concat_* in the other order (models/yolov3_tiny.py:73):
+ *    y [n,2h,2w,cb+ca] = cat([b, nearest_x2(a)], channel) of b [n,2h,2w,cb] and a [n,h,w,ca]; db = dy[..., :cb], da the same fixed 2x2
+ *    sum of dy[..., cb:]; db or da may be NULL, not both.  The same kernels behind a channel offset.
+ *  YOLO_E_ARG before any launch for an empty shape or empty output (h < 2 or w < 2), c % 8, a stride other than 1 or 2, an act other than
+ *  YOLO_ACT_NONE / YOLO_ACT_LEAKY01, a null or misaligned pointer (the bf16 maps and saved: 16 bytes; idx: 8). */
+YOLO_API int yolo_maxpool_train_fwd(const void* x, void* y, void* idx, int n, int h, int w, int c, int stride, yolo_stream_t s);
+YOLO_API int yolo_maxpool_bwd(const void* dy, const void* idx, void* dx, int n, int h, int w, int c, int stride, yolo_stream_t s);
+YOLO_API int yolo_bn_act_pool_fwd(const void* z, const float* saved, void* y, void* idx, int n, int h, int w, int c, int act, yolo_stream_t s);
+YOLO_API int yolo_concat_upsample2_fwd(const void* b, const void* a, void* y, int n, int h, int w, int cb, int ca, yolo_stream_t s);
+YOLO_API int yolo_concat_upsample2_bwd(const void* dy, void* db, void* da, int n, int h, int w, int cb, int ca, yolo_stream_t s);
+
 /* First layer fused with the input packing: x is the caller's f32 NCHW batch [n,cin_real,h,w] (cin_real <= 8),
  * w_packed / bias as for yolo_conv2d_fwd with d->cin = 8; 3x3 / pad 1, bf16 NHWC output: stride 1 with cout 16 or 32
  * (Darknet), or stride 2 with cout 32 (MobileNetV2's first layer). */

@@ -40,6 +40,7 @@ SOURCES = {
     "coco_eval.hip": ["-ffp-contract=off"],
     "batchnorm.hip": ["-ffp-contract=off"],
     "route.hip": ["-ffp-contract=off"],
+    "pool_train.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
           "-Wall", "-Wno-unused-function"]

@@ -4,6 +4,7 @@
 //   eval_stats_kernel                      the same four vectors from the running statistics
 //   act_fwd_kernel                         y = bf16(act(f32(z) scale + shift))
 //   act_add_fwd_kernel                     the same with the residual add: y = bf16(act(..) + f32(residual)), y_preadd = bf16(act(..))
+//   act_pool_fwd_kernel                    act_fwd_kernel's pass with MaxPool2d(2, 2) inside: the pooled y and its argmax plane (3.6g)
 //   bwd_reduce_kernel + bwd_finalize_kernel  B = sum ga, G = sum ga xh in float64 -> dgamma, dbeta, c1, c2
 //   act_bwd_kernel                         g = bf16(scale ((ga - c1) - xh c2)), the operand of yolo_conv2d_bwd_weight / _data
 // Every pass is a stream of 16-byte loads; a thread owns one chunk of 8 channels.  The two reductions split the rows over blockIdx.x
@@ -310,6 +311,46 @@ __global__ __launch_bounds__(256) void act_add_fwd_kernel(const bf16_t* __restri
   if (PREADD) *reinterpret_cast<bf16x8*>(y_preadd + idx * 8) = pre;
 }
 
+// act_fwd_kernel's pass with MaxPool2d(2, 2) inside it (the ConvPoolBlock as it trains): one thread per chunk of one POOLED
+// pixel.  Each of the block's four taps is rounded to bf16 exactly as act_fwd_kernel would write it, then the four bf16 values are compared
+// under the first-maximum rule of yolo_maxpool_train_fwd (gamma may be negative: the activated values are compared, not z).  Only the
+// pooled y and idx are written; an odd last row / column of z is never read.
+__global__ __launch_bounds__(256) void act_pool_fwd_kernel(const bf16_t* __restrict__ z, const float* __restrict__ saved, bf16_t* __restrict__ y,
+                                                           uint8_t* __restrict__ idx, long total, int h, int w, int ho, int wo, int c, int chunks,
+                                                           int leaky) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int ch = (int)(i % chunks);
+  const long pix = i / chunks;                                               // (n, oy, ox) of the pooled map
+  const int ox = (int)(pix % wo);
+  const long t = pix / wo;
+  const int oy = (int)(t % ho);
+  const long n = t / ho;
+  const bf16_t* src = z + ((n * h + 2 * oy) * w + 2 * ox) * c + (long)ch * 8;
+  bf16x8 tap[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) tap[k] = *reinterpret_cast<const bf16x8*>(src + ((long)(k >> 1) * w + (k & 1)) * c);
+  float scale[8], shift[8];
+  load8f(saved + 2 * (size_t)c + (size_t)ch * 8, scale), load8f(saved + 3 * (size_t)c + (size_t)ch * 8, shift);
+  bf16x8 best;
+  u32x2 arg = {0u, 0u};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    bf16_t b = (bf16_t)0.f;
+    uint32_t at = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float a = (float)tap[k][j] * scale[j] + shift[j];
+      const bf16_t v = (bf16_t)((!leaky || a > 0.f) ? a : 0.1f * a);
+      if (k == 0 || (float)v > (float)b) b = v, at = (uint32_t)k;
+    }
+    best[j] = b;
+    arg[j >> 2] |= at << (8 * (j & 3));
+  }
+  *reinterpret_cast<bf16x8*>(y + i * 8) = best;
+  *reinterpret_cast<u32x2*>(idx + i * 8) = arg;
+}
+
 template <typename TDY>
 __global__ __launch_bounds__(256) void act_bwd_kernel(const TDY* __restrict__ dy, const bf16_t* __restrict__ z, const float* __restrict__ saved,
                                                       const float* __restrict__ c12, bf16_t* __restrict__ g, long total, int c, int chunks,
@@ -414,6 +455,21 @@ extern "C" int yolo_bn_act_fwd(const void* z, const float* saved, void* y, long 
   hipLaunchKernelGGL(act_fwd_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)z, saved, (bf16_t*)y, total, c, c / 8,
                      act == YOLO_ACT_LEAKY01);
   return yolo_check_launch("bn_act_fwd");
+}
+
+extern "C" int yolo_bn_act_pool_fwd(const void* z, const float* saved, void* y, void* idx, int n, int h, int w, int c, int act, yolo_stream_t s) {
+  YOLO_REQUIRE(n > 0 && h > 0 && w > 0, "bn_act_pool_fwd: empty shape (n %d, h %d, w %d)", n, h, w);
+  if (const int rc = bn_check((long long)n * h * w, c, "bn_act_pool_fwd")) return rc;
+  if (const int rc = act_check(act, "bn_act_pool_fwd")) return rc;
+  YOLO_REQUIRE(h >= 2 && w >= 2, "bn_act_pool_fwd: empty output (the 2/2 pool of a %d x %d map)", h, w);
+  YOLO_REQUIRE(h <= (1 << 20) && w <= (1 << 20), "bn_act_pool_fwd: shape out of range (h %d, w %d)", h, w);
+  YOLO_REQUIRE(z && saved && y && idx, "bn_act_pool_fwd: null pointer");
+  YOLO_REQUIRE(al(z, 16) && al(saved, 16) && al(y, 16) && al(idx, 8), "bn_act_pool_fwd: misaligned pointer");
+  const int ho = h / 2, wo = w / 2;
+  const long total = (long)n * ho * wo * (c / 8);
+  hipLaunchKernelGGL(act_pool_fwd_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)z, saved, (bf16_t*)y, (uint8_t*)idx,
+                     total, h, w, ho, wo, c, c / 8, act == YOLO_ACT_LEAKY01);
+  return yolo_check_launch("bn_act_pool_fwd");
 }
 
 extern "C" int yolo_bn_act_add_fwd(const void* z, const float* saved, const void* residual, void* y, void* y_preadd, long long pixels, int c,

@@ -3,7 +3,7 @@
 // owns one chunk of 8 channels (16 bytes) of one pixel:
 //   spp_fwd_kernel     y = cat([maxpool5(x), maxpool9(x), maxpool13(x), x]) and the argmax planes idx (uint8 window offsets)
 //   spp_bwd_kernel     dx as a gather: every pixel adds the dy of the windows whose argmax it is, then the pass-through slice
-//   upcat_fwd_kernel   y = cat([nearest_x2(a), b])
+//   upcat_fwd_kernel   y = cat([nearest_x2(a), b]), or cat([b, nearest_x2(a)]) (YOLOv3-tiny's order): a channel offset
 //   upcat_da_kernel    da = the 2x2 block sums of dy[..., :ca];  upcat_db_kernel  db = dy[..., ca:]
 // The two SPP kernels run one workgroup per (image, chunk); maps of up to kSppLdsPixels pixels are staged in LDS first (x in the forward;
 // the three pooled slices of dy and the three index planes in the backward), larger maps read global memory with the same code.
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void spp_bwd_kernel(const bf16_t* __restrict__
 
 // ---- nearest x2 upsample + concat ----------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void upcat_fwd_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ b, bf16_t* __restrict__ y,
-                                                        long total, int h, int w, int ca, int cb) {
+                                                        long total, int h, int w, int ca, int cb, int a_first) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int chunks = (ca + cb) / 8;
@@ -156,15 +156,16 @@ __global__ __launch_bounds__(256) void upcat_fwd_kernel(const bf16_t* __restrict
   const long t = pix / (2 * w);
   const int oy = (int)(t % (2 * h));
   const long n = t / (2 * h);
+  const int cha = a_first ? ch : ch - cb / 8, chb = a_first ? ch - ca / 8 : ch;       // the chunk inside a's / b's slice
   bf16x8 v;
-  if (ch < ca / 8) v = *reinterpret_cast<const bf16x8*>(a + ((n * h + oy / 2) * w + ox / 2) * ca + (long)ch * 8);
-  else v = *reinterpret_cast<const bf16x8*>(b + pix * cb + (long)(ch - ca / 8) * 8);
+  if (cha >= 0 && cha < ca / 8) v = *reinterpret_cast<const bf16x8*>(a + ((n * h + oy / 2) * w + ox / 2) * ca + (long)cha * 8);
+  else v = *reinterpret_cast<const bf16x8*>(b + pix * cb + (long)chb * 8);
   *reinterpret_cast<bf16x8*>(y + i * 8) = v;
 }
 
 // da = bf16_rne(((f32(dy00) + f32(dy01)) + f32(dy10)) + f32(dy11)): the block's pixels in row-major order
 __global__ __launch_bounds__(256) void upcat_da_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ da, long total, int h, int w, int ca,
-                                                       int cb) {
+                                                       int cb, int a_off) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int chunks = ca / 8, ct = ca + cb;
@@ -172,7 +173,7 @@ __global__ __launch_bounds__(256) void upcat_da_kernel(const bf16_t* __restrict_
   const long pix = i / chunks;                                               // (n, y, x) of the [n, h, w] map
   const int x = (int)(pix % w);
   const long t = pix / w;                                                    // n h + y
-  const bf16_t* src = dy + ((2 * t) * (2 * w) + 2 * x) * ct + (long)ch * 8;
+  const bf16_t* src = dy + ((2 * t) * (2 * w) + 2 * x) * ct + a_off + (long)ch * 8;
   float acc[8];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
@@ -186,13 +187,14 @@ __global__ __launch_bounds__(256) void upcat_da_kernel(const bf16_t* __restrict_
   *reinterpret_cast<bf16x8*>(da + i * 8) = o;
 }
 
-__global__ __launch_bounds__(256) void upcat_db_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ db, long total, int ca, int cb) {
+__global__ __launch_bounds__(256) void upcat_db_kernel(const bf16_t* __restrict__ dy, bf16_t* __restrict__ db, long total, int ca, int cb,
+                                                       int b_off) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int chunks = cb / 8;
   const int ch = (int)(i % chunks);
   const long pix = i / chunks;
-  *reinterpret_cast<bf16x8*>(db + i * 8) = *reinterpret_cast<const bf16x8*>(dy + pix * (ca + cb) + ca + (long)ch * 8);
+  *reinterpret_cast<bf16x8*>(db + i * 8) = *reinterpret_cast<const bf16x8*>(dy + pix * (ca + cb) + b_off + (long)ch * 8);
 }
 
 bool al(const void* p, int n) { return (uintptr_t)p % n == 0; }
@@ -246,29 +248,50 @@ extern "C" int yolo_spp_bwd(const void* dy, const void* idx, void* dx, int n, in
   return yolo_check_launch("spp_bwd");
 }
 
-extern "C" int yolo_upsample2_concat_fwd(const void* a, const void* b, void* y, int n, int h, int w, int ca, int cb, yolo_stream_t s) {
-  if (const int rc = upcat_check(n, h, w, ca, cb, "upsample2_concat_fwd")) return rc;
-  YOLO_REQUIRE(a && b && y, "upsample2_concat_fwd: null pointer");
-  YOLO_REQUIRE(al(a, 16) && al(b, 16) && al(y, 16), "upsample2_concat_fwd: misaligned pointer");
+// the two concat orders share the kernels: a_first says whether nearest_x2(a) takes the low channels (yolo_upsample2_concat_*) or the high
+// ones (yolo_concat_upsample2_*)
+static int upcat_fwd(const void* a, const void* b, void* y, int n, int h, int w, int ca, int cb, int a_first, yolo_stream_t s, const char* fn) {
+  if (const int rc = upcat_check(n, h, w, ca, cb, fn)) return rc;
+  YOLO_REQUIRE(a && b && y, "%s: null pointer", fn);
+  YOLO_REQUIRE(al(a, 16) && al(b, 16) && al(y, 16), "%s: misaligned pointer", fn);
   const long total = (long)n * h * w * 4 * ((ca + cb) / 8);
   hipLaunchKernelGGL(upcat_fwd_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)a, (const bf16_t*)b, (bf16_t*)y, total, h,
-                     w, ca, cb);
-  return yolo_check_launch("upsample2_concat_fwd");
+                     w, ca, cb, a_first);
+  return yolo_check_launch(fn);
 }
 
-extern "C" int yolo_upsample2_concat_bwd(const void* dy, void* da, void* db, int n, int h, int w, int ca, int cb, yolo_stream_t s) {
-  if (const int rc = upcat_check(n, h, w, ca, cb, "upsample2_concat_bwd")) return rc;
-  YOLO_REQUIRE(dy && (da || db), "upsample2_concat_bwd: null pointer (dy, or both of da and db)");
-  YOLO_REQUIRE(al(dy, 16) && al(da, 16) && al(db, 16), "upsample2_concat_bwd: misaligned pointer");
+static int upcat_bwd(const void* dy, void* da, void* db, int n, int h, int w, int ca, int cb, int a_first, yolo_stream_t s, const char* fn) {
+  if (const int rc = upcat_check(n, h, w, ca, cb, fn)) return rc;
+  YOLO_REQUIRE(dy && (da || db), "%s: null pointer (dy, or both of da and db)", fn);
+  YOLO_REQUIRE(al(dy, 16) && al(da, 16) && al(db, 16), "%s: misaligned pointer", fn);
   if (da) {
     const long total = (long)n * h * w * (ca / 8);
-    hipLaunchKernelGGL(upcat_da_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dy, (bf16_t*)da, total, h, w, ca, cb);
-    if (const int rc = yolo_check_launch("upsample2_concat_bwd", " (da)")) return rc;
+    hipLaunchKernelGGL(upcat_da_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dy, (bf16_t*)da, total, h, w, ca, cb,
+                       a_first ? 0 : cb);
+    if (const int rc = yolo_check_launch(fn, " (da)")) return rc;
   }
   if (db) {
     const long total = (long)n * h * w * 4 * (cb / 8);
-    hipLaunchKernelGGL(upcat_db_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dy, (bf16_t*)db, total, ca, cb);
-    if (const int rc = yolo_check_launch("upsample2_concat_bwd", " (db)")) return rc;
+    hipLaunchKernelGGL(upcat_db_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dy, (bf16_t*)db, total, ca, cb,
+                       a_first ? ca : 0);
+    if (const int rc = yolo_check_launch(fn, " (db)")) return rc;
   }
   return 0;
+}
+
+extern "C" int yolo_upsample2_concat_fwd(const void* a, const void* b, void* y, int n, int h, int w, int ca, int cb, yolo_stream_t s) {
+  return upcat_fwd(a, b, y, n, h, w, ca, cb, 1, s, "upsample2_concat_fwd");
+}
+
+extern "C" int yolo_upsample2_concat_bwd(const void* dy, void* da, void* db, int n, int h, int w, int ca, int cb, yolo_stream_t s) {
+  return upcat_bwd(dy, da, db, n, h, w, ca, cb, 1, s, "upsample2_concat_bwd");
+}
+
+// y [n, 2h, 2w, cb + ca] = cat([b, nearest_x2(a)]): the order of YOLOv3-tiny (reference models/yolov3_tiny.py:73)
+extern "C" int yolo_concat_upsample2_fwd(const void* b, const void* a, void* y, int n, int h, int w, int cb, int ca, yolo_stream_t s) {
+  return upcat_fwd(a, b, y, n, h, w, ca, cb, 0, s, "concat_upsample2_fwd");
+}
+
+extern "C" int yolo_concat_upsample2_bwd(const void* dy, void* db, void* da, int n, int h, int w, int cb, int ca, yolo_stream_t s) {
+  return upcat_bwd(dy, da, db, n, h, w, ca, cb, 0, s, "concat_upsample2_bwd");
 }

@@ -19,7 +19,8 @@ __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pic
            "conv2d_bwd_workspace_bytes", "conv2d_bwd_pick", "conv2d_bwd_prepare", "conv2d_bwd_weight", "conv2d_bwd_data", "pack_conv_weight_dev",
            "conv2d_down_bwd_workspace_bytes", "conv2d_down_bwd_pick", "conv2d_down_bwd_weight", "conv2d_down_bwd_data", "pack_conv_weight_down_dev",
            "bn_workspace_bytes", "bn_pick", "bn_train_stats", "bn_eval_stats", "bn_act_fwd", "bn_act_bwd",
-           "bn_act_add_fwd", "spp_train_fwd", "spp_bwd", "upsample2_concat_fwd", "upsample2_concat_bwd"]
+           "bn_act_add_fwd", "spp_train_fwd", "spp_bwd", "upsample2_concat_fwd", "upsample2_concat_bwd",
+           "maxpool_train_fwd", "maxpool_bwd", "bn_act_pool_fwd", "concat_upsample2_fwd", "concat_upsample2_bwd"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -582,6 +583,85 @@ def upsample2_concat_bwd(dy, da, db, *, n, h, w, ca, cb):
         _nhwc(db, (n, 2 * h, 2 * w, cb), "upsample2_concat_bwd: db")
     check(load().yolo_upsample2_concat_bwd(_ptr(dy), _ptr(da), _ptr(db), n, h, w, ca, cb, stream_ptr()), "upsample2_concat_bwd")
     return da, db
+
+
+# ---- the max-pools of a training step of YOLOv3-tiny / LiteYOLOv3 (csrc/pool_train.hip, one entry of csrc/batchnorm.hip, two of
+# csrc/route.hip) ---------------------------------------------------------------------------------------------------------
+def _pooled(h, w, stride):
+    if stride not in (1, 2):
+        raise RuntimeError(f"max-pool stride {stride} unsupported (1 or 2)")
+    return (h // 2, w // 2) if stride == 2 else (h, w)
+
+
+def maxpool_train_fwd(x, y, idx, stride):
+    """The reference's MaxPool of the dense bf16 x [n,h,w,c].  stride 2: y [n,h/2,w/2,c] = MaxPool2d(2, 2)(x); stride 1: y [n,h,w,c] =
+    MaxPool2d(2, 1, padding=1, dilation=2)(x).  idx uint8 of y's shape: the tap 0..3 of each window's first maximum."""
+    _need_cuda(x, y, idx)
+    if x.dim() != 4:
+        raise RuntimeError("maxpool_train_fwd: x must be [n, h, w, c]")
+    n, h, w, c = x.shape
+    ho, wo = _pooled(h, w, stride)
+    _nhwc(x, (n, h, w, c), "maxpool_train_fwd: x")
+    _nhwc(y, (n, ho, wo, c), "maxpool_train_fwd: y")
+    _nhwc(idx, (n, ho, wo, c), "maxpool_train_fwd: idx", torch.uint8)
+    check(load().yolo_maxpool_train_fwd(_ptr(x), _ptr(y), _ptr(idx), n, h, w, c, int(stride), stream_ptr()), "maxpool_train_fwd")
+    return y, idx
+
+
+def maxpool_bwd(dy, idx, dx, stride):
+    """dx [n,h,w,c] (every element written) from dy and maxpool_train_fwd's idx: a copy at stride 2, a gather of up to four terms with a
+    fixed fp32 summation order, rounded once, at stride 1."""
+    _need_cuda(dy, idx, dx)
+    if dx.dim() != 4:
+        raise RuntimeError("maxpool_bwd: dx must be [n, h, w, c]")
+    n, h, w, c = dx.shape
+    ho, wo = _pooled(h, w, stride)
+    _nhwc(dx, (n, h, w, c), "maxpool_bwd: dx")
+    _nhwc(dy, (n, ho, wo, c), "maxpool_bwd: dy")
+    _nhwc(idx, (n, ho, wo, c), "maxpool_bwd: idx", torch.uint8)
+    check(load().yolo_maxpool_bwd(_ptr(dy), _ptr(idx), _ptr(dx), n, h, w, c, int(stride), stream_ptr()), "maxpool_bwd")
+    return dx
+
+
+def bn_act_pool_fwd(z, saved, y, idx, act):
+    """bn_act_fwd with MaxPool2d(2, 2) inside: y [n,h/2,w/2,c] and idx of the dense bf16 z [n,h,w,c]; bit-equal to bn_act_fwd followed by
+    maxpool_train_fwd(stride 2), the full-resolution activation is never written."""
+    _need_cuda(z, saved, y, idx)
+    if z.dim() != 4:
+        raise RuntimeError("bn_act_pool_fwd: z must be [n, h, w, c]")
+    n, h, w, c = z.shape
+    _nhwc(z, (n, h, w, c), "bn_act_pool_fwd: z")
+    _nhwc(y, (n, h // 2, w // 2, c), "bn_act_pool_fwd: y")
+    _nhwc(idx, (n, h // 2, w // 2, c), "bn_act_pool_fwd: idx", torch.uint8)
+    _bn_vec(saved, c, "bn_act_pool_fwd: saved", 4)
+    check(load().yolo_bn_act_pool_fwd(_ptr(z), _ptr(saved), _ptr(y), _ptr(idx), n, h, w, c, int(act), stream_ptr()), "bn_act_pool_fwd")
+    return y, idx
+
+
+def concat_upsample2_fwd(b, a, y):
+    """y [n,2h,2w,cb+ca] = cat([b, nearest_x2(a)]) of the dense bf16 b [n,2h,2w,cb] and a [n,h,w,ca]: YOLOv3-tiny's order."""
+    _need_cuda(a, b, y)
+    if a.dim() != 4 or b.dim() != 4:
+        raise RuntimeError("concat_upsample2_fwd: b must be [n, 2h, 2w, cb] and a [n, h, w, ca]")
+    n, h, w, ca = a.shape
+    cb = b.shape[3]
+    _nhwc(a, (n, h, w, ca), "concat_upsample2_fwd: a")
+    _nhwc(b, (n, 2 * h, 2 * w, cb), "concat_upsample2_fwd: b")
+    _nhwc(y, (n, 2 * h, 2 * w, ca + cb), "concat_upsample2_fwd: y")
+    check(load().yolo_concat_upsample2_fwd(_ptr(b), _ptr(a), _ptr(y), n, h, w, cb, ca, stream_ptr()), "concat_upsample2_fwd")
+    return y
+
+
+def concat_upsample2_bwd(dy, db, da, *, n, h, w, cb, ca):
+    """db [n,2h,2w,cb] = dy[..., :cb], da [n,h,w,ca] = the fp32 2x2 block sums of dy[..., cb:] rounded once; either may be None."""
+    _need_cuda(dy, da, db)
+    _nhwc(dy, (n, 2 * h, 2 * w, ca + cb), "concat_upsample2_bwd: dy")
+    if da is not None:
+        _nhwc(da, (n, h, w, ca), "concat_upsample2_bwd: da")
+    if db is not None:
+        _nhwc(db, (n, 2 * h, 2 * w, cb), "concat_upsample2_bwd: db")
+    check(load().yolo_concat_upsample2_bwd(_ptr(dy), _ptr(db), _ptr(da), n, h, w, cb, ca, stream_ptr()), "concat_upsample2_bwd")
+    return db, da
 
 
 def conv2d_splitk_plan(desc: YoloConvDesc, has_residual=False, has_preadd=False):

@@ -5,6 +5,7 @@ from __future__ import annotations
 from torch import nn
 
 from .. import engine
+from . import train as T
 from .yolo_base import ConvBlock, ConvPoolBlock, YOLOBase
 from .yolo_layer import Concat, Upsample
 from .yolov3 import _seq
@@ -78,3 +79,22 @@ class LiteYOLOv3(YOLOBase):
         z = g.concat([g.upsample2(self.seqy3_1.conv._trace(g, y)), downs[2]])
         z = self.seqy3_2.conv1._trace(g, z)
         g.head(self.seqy3_2.conv2._trace(g, z, f32_out=True), self.yolo3)
+
+    # the training step is reached through pytorch_yolo_amd.forward_train(model, x); model.train()(x) keeps raising
+    _train_in_forward = False
+
+    def _train_wiring(self, ops, x):
+        """The same wiring in training mode on the ops of a table (models/train.py): the three raw head maps [bs, 3 (5 + nc), ny, nx]."""
+        pair = lambda m, t: T.conv_bn(ops, m.conv2, T.conv_bn(ops, m.conv1, t))                  # Conv: 1x1 then 3x3
+        downs = []
+        for m in self.down:
+            x = T.conv_bn(ops, m.conv_pool, T.conv_bn(ops, m.conv, x)) if isinstance(m, Down) else T.conv_bn(ops, m, x)
+            downs.append(x)
+        x = T.conv_bn(ops, self.seq.conv1, x)
+        b1 = T.head(ops, T.conv_bn(ops, self.seq_y1.conv1, x), self.seq_y1.conv2)
+        y = ops.upsample_concat(T.conv_bn(ops, self.seqy2_1.conv, x), downs[3])
+        y = T.conv_bn(ops, self.seqy2_2.conv2, pair(self.seqy2_2.conv1, y))
+        b2 = T.head(ops, T.conv_bn(ops, self.seqy2_3.conv6, y), self.seqy2_3.conv7)
+        z = ops.upsample_concat(T.conv_bn(ops, self.seqy3_1.conv, y), downs[2])
+        b3 = T.head(ops, pair(self.seqy3_2.conv1, z), self.seqy3_2.conv2)
+        return b1, b2, b3

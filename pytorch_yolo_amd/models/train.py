@@ -1,9 +1,16 @@
-"""Training-mode forward of the Darknet-53 models (YOLOv3, YOLOv3-SPP): the reference's ``model.train()(x)`` - batch-statistics BN, the
-raw ``p`` list with a ``grad_fn`` - wired from the differentiable ops of pytorch_yolo_amd.ops.
+"""Training-mode forward of the Darknet-53 models (YOLOv3, YOLOv3-SPP) and of the max-pool models (YOLOv3-tiny, LiteYOLOv3): the
+reference's ``model.train()(x)`` - batch-statistics BN, the raw ``p`` list with a ``grad_fn`` - wired from the differentiable ops of
+pytorch_yolo_amd.ops.
 
-The wiring (``model._train_wiring``) takes every op from a table, a namespace with the six functions of ``DEVICE_OPS``: the default
-table runs the package's kernels; the tests run the same Python wiring on the CPU with float64 torch restatements of the ops, which is
-how it is compared with the reference without a GPU.  A table function has the signature of the op it stands for.
+The wiring (``model._train_wiring``) takes every op from a table, a namespace of functions: the default table runs the package's
+kernels; the tests run the same Python wiring on the CPU with float64 torch restatements of the ops, which is how it is compared with
+the reference without a GPU.  A table function has the signature of the op it stands for.  ``DEVICE_OPS`` holds the six functions the
+Darknet-53 models use; ``DEVICE_OPS_POOL`` adds ``max_pool`` and ``pool_bn_block`` and is the table ``forward_train`` runs by default
+(the ``up_first`` keyword of ``upsample_concat`` goes through both).
+
+``forward_train(model, x)`` is the public entry for all four classes.  ``model.train()(x)`` delegates to it for the classes whose
+``_train_in_forward`` is True (YOLOv3, YOLOv3-SPP); YOLOv3-tiny and LiteYOLOv3 keep raising from the module call and train through the
+function (DESIGN.md 3.6g says why: flipping their switch is a one-line change).
 """
 from __future__ import annotations
 
@@ -13,10 +20,11 @@ import torch
 from torch import nn
 
 from .. import ops as _ops
-from .yolo_base import ConvBlock
+from .yolo_base import ConvBlock, ConvPoolBlock
 
 DEVICE_OPS = SimpleNamespace(conv_block=_ops.conv_block, conv_bn_block=_ops.conv_bn_block, down_bn_block=_ops.down_bn_block,
                              res_bn_block=_ops.res_bn_block, spp_concat=_ops.spp_concat, upsample_concat=_ops.upsample_concat)
+DEVICE_OPS_POOL = SimpleNamespace(**vars(DEVICE_OPS), max_pool=_ops.max_pool, pool_bn_block=_ops.pool_bn_block)
 
 
 def conv_bn(ops, block, x, residual=None, want_preadd=False):
@@ -31,6 +39,8 @@ def conv_bn(ops, block, x, residual=None, want_preadd=False):
     w, gamma, beta, rm, rv = conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var
     if residual is not None:
         return ops.res_bn_block(x, w, gamma, beta, rm, rv, residual, want_preadd=want_preadd, **kw)
+    if isinstance(block, ConvPoolBlock):        # (stride 1, cout % 8 == 0 in every model: ops.pool_bn_block checks)
+        return ops.pool_bn_block(x, w, gamma, beta, rm, rv, pool_stride=block.pool.stride, **kw)
     if block.stride == 2:
         return ops.down_bn_block(x, w, gamma, beta, rm, rv, **kw)
     cout = w.shape[0]
@@ -86,8 +96,9 @@ def encoder(ops, model, x):
 
 
 def forward_train(model, x, ops=None):
-    """``[p1, p2, p3]``, each ``[bs, 3, ny, nx, 5 + nc]`` contiguous with a grad_fn, as the reference's training-mode forward returns.
-    With the default table: float32 on the device; x float32 NCHW, H and W multiples of 32, bf16 mode, BN not fused."""
+    """``[p1, p2, p3]`` (``[p1, p2]`` for YOLOv3-tiny), each ``[bs, 3, ny, nx, 5 + nc]`` contiguous with a grad_fn, as the reference's
+    training-mode forward returns.  With the default table: float32 on the device; x float32 NCHW, H and W multiples of 32 (YOLOv3-tiny:
+    at least 64), bf16 mode, BN not fused."""
     if not hasattr(model, "_train_wiring"):
         raise NotImplementedError(
             "training-mode forward (batch-statistics BN, raw p list) is outside the inference hot path; "
@@ -100,13 +111,18 @@ def forward_train(model, x, ops=None):
         raise ValueError(f"expected input [bs,{model.in_channels},H,W], got {tuple(getattr(x, 'shape', ()))}")
     if x.shape[2] % 32 or x.shape[3] % 32 or min(x.shape[2:]) < 32:
         raise ValueError(f"the training-mode forward needs H and W to be multiples of 32, got {tuple(x.shape[2:])}")
+    min_size = getattr(model, "_train_min_size", 32)
+    if min(x.shape[2:]) < min_size:
+        raise ValueError(f"the training-mode forward of {type(model).__name__} needs H and W of at least {min_size}, got "
+                         f"{tuple(x.shape[2:])}: on a smaller input its stride-1 max-pool sees a 1x1 map, whose window is all padding "
+                         "(the reference itself returns -inf there)")
     if ops is None:
         if x.dtype != torch.float32:
             raise ValueError(f"the training-mode forward takes a float32 NCHW batch, got {x.dtype}")
         if not x.is_cuda:
             raise RuntimeError("pytorch_yolo_amd runs on a ROCm device only: move the input to cuda "
                                "(there is no CPU fallback)")
-        ops = DEVICE_OPS
+        ops = DEVICE_OPS_POOL
     branches = model._train_wiring(ops, x)
     img_size = max(x.shape[-2:])
     out = []

@@ -218,11 +218,19 @@ class YOLOBase(nn.Module):
                 self._plans.pop(next(iter(self._plans)))
         return plan
 
+    # whether model.train()(x) delegates to models/train.forward_train.  False for YOLOv3-tiny and LiteYOLOv3, which have a
+    # _train_wiring but train through pytorch_yolo_amd.forward_train(model, x) only
+    _train_in_forward = True
+
     def forward(self, x):
         """eval: (io [bs, sum(3*ny*nx), 5+nc], (p_k [bs,3,ny,nx,5+nc], ...)) like the reference
-        (yolov3_spp.py:141-164, yolov3_tiny.py:79-100).  training (YOLOv3 and YOLOv3-SPP, the classes with a ``_train_wiring``; every
-        other class raises): the raw list [p_k] with a grad_fn (models/train.py)."""
+        (yolov3_spp.py:141-164, yolov3_tiny.py:79-100).  training (YOLOv3 and YOLOv3-SPP, the classes with a ``_train_wiring`` whose
+        ``_train_in_forward`` is set; every other class raises): the raw list [p_k] with a grad_fn (models/train.py)."""
         if self.training:
+            if not self._train_in_forward:
+                raise NotImplementedError(
+                    "training-mode forward through the module call is switched off for this class: call "
+                    "pytorch_yolo_amd.forward_train(model, x), or .eval() first")
             from .train import forward_train
             return forward_train(self, x)
         if x.dtype != torch.float32:

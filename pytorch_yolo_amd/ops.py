@@ -18,6 +18,11 @@ norm is conv_bn_block's (yolo_bn_* take the n ho wo output pixels).
 ``res_bn_block``, ``spp_concat`` and ``upsample_concat`` are the layers between those convs in YOLOv3 / YOLOv3-SPP - the residual unit's
 closing ConvBlock with its add, the SPP pyramid, the FPN's upsample + concat - with their backwards (csrc/route.hip, yolo_bn_act_add_fwd;
 DESIGN.md 3.6f); models/train.py wires the training-mode forward of the two models from all seven ops.
+
+``max_pool`` and ``pool_bn_block`` are the reference's MaxPool and ConvPoolBlock as they train - MaxPool2d(2, 2) and the form MaxPool(2, 1)
+turns into, MaxPool2d(2, 1, padding=1, dilation=2) - and ``upsample_concat(..., up_first=False)`` is the concat in YOLOv3-tiny's order
+(csrc/pool_train.hip, yolo_bn_act_pool_fwd, yolo_concat_upsample2_*): with them models/train.py wires YOLOv3-tiny and
+LiteYOLOv3 too.
 """
 from __future__ import annotations
 
@@ -26,7 +31,8 @@ import torch
 from . import kernels as K
 from ._lib import ACT_LEAKY01, ACT_NONE, DT_BF16, DT_F32
 
-__all__ = ["conv_block", "conv_bn_block", "down_block", "down_bn_block", "res_bn_block", "spp_concat", "upsample_concat"]
+__all__ = ["conv_block", "conv_bn_block", "down_block", "down_bn_block", "res_bn_block", "spp_concat", "upsample_concat", "max_pool",
+           "pool_bn_block"]
 
 _ACTS = {"leaky": ACT_LEAKY01, "none": ACT_NONE}
 
@@ -419,31 +425,38 @@ class _SppConcatFunction(torch.autograd.Function):
 
 class _UpsampleConcatFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, a, b):
+    def forward(ctx, a, b, up_first=True):
         an, bn = a.permute(0, 2, 3, 1), b.permute(0, 2, 3, 1)
         n, h, w, ca = an.shape
         ctx.dims = (n, h, w, ca, bn.shape[3])
+        ctx.up_first = up_first
         with torch.cuda.device(a.device):
             y = torch.empty((n, 2 * h, 2 * w, ca + bn.shape[3]), dtype=torch.bfloat16, device=a.device)
-            K.upsample2_concat_fwd(an, bn, y)
+            if up_first:
+                K.upsample2_concat_fwd(an, bn, y)
+            else:
+                K.concat_upsample2_fwd(bn, an, y)
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         n, h, w, ca, cb = ctx.dims
-        need_a, need_b = ctx.needs_input_grad
+        need_a, need_b = ctx.needs_input_grad[:2]
         da = db = None
         if not (need_a or need_b):
-            return None, None
+            return None, None, None
         with torch.cuda.device(dy.device):
             dy = _dense_bf16(dy).permute(0, 2, 3, 1)
             if need_a:
                 da = torch.empty((n, h, w, ca), dtype=torch.bfloat16, device=dy.device)
             if need_b:
                 db = torch.empty((n, 2 * h, 2 * w, cb), dtype=torch.bfloat16, device=dy.device)
-            K.upsample2_concat_bwd(dy, da, db, n=n, h=h, w=w, ca=ca, cb=cb)
-        return (None if da is None else da.permute(0, 3, 1, 2)), (None if db is None else db.permute(0, 3, 1, 2))
+            if ctx.up_first:
+                K.upsample2_concat_bwd(dy, da, db, n=n, h=h, w=w, ca=ca, cb=cb)
+            else:
+                K.concat_upsample2_bwd(dy, db, da, n=n, h=h, w=w, cb=cb, ca=ca)
+        return (None if da is None else da.permute(0, 3, 1, 2)), (None if db is None else db.permute(0, 3, 1, 2)), None
 
 
 def _check_map(name, what, t):
@@ -467,18 +480,19 @@ def spp_concat(x):
     return _SppConcatFunction.apply(_dense_bf16(x))
 
 
-def upsample_concat(a, b):
+def upsample_concat(a, b, *, up_first=True):
     """``cat([interpolate(a, scale_factor=2, mode="nearest"), b], 1)`` on the device, differentiable once: the FPN's Upsample + Concat
     (reference models/yolo_layer.py:6-22).  a [n, ca, h, w], b [n, cb, 2h, 2w], ``ca % 8 == 0`` and ``cb % 8 == 0``; converted like
     spp_concat's x.  Returns bfloat16 [n, ca + cb, 2h, 2w], channels-last.  Gradients: a the fp32 sum of each 2x2 block rounded once, b
-    the copy of its slice; each computed only where asked.  Errors as spp_concat."""
+    the copy of its slice; each computed only where asked.  Errors as spp_concat.
+    ``up_first=False`` gives ``cat([b, interpolate(a, ...)], 1)``, the order of YOLOv3-tiny (reference models/yolov3_tiny.py:73)."""
     _check_map("upsample_concat", "a", a)
     _check_map("upsample_concat", "b", b)
     if tuple(b.shape[0:1] + b.shape[2:]) != (a.shape[0], 2 * a.shape[2], 2 * a.shape[3]):
         raise ValueError(f"upsample_concat: b {tuple(b.shape)} must be [n, cb, 2h, 2w] of a {tuple(a.shape)}")
     if not (a.is_cuda and b.is_cuda):
         raise RuntimeError("pytorch_yolo_amd.upsample_concat runs on a ROCm device only (no CPU fallback)")
-    return _UpsampleConcatFunction.apply(_dense_bf16(a), _dense_bf16(b))
+    return _UpsampleConcatFunction.apply(_dense_bf16(a), _dense_bf16(b), bool(up_first))
 
 
 # ---- the downsample: ConvBlock(3x3, stride 2, pad 1) ---------------------------------------------------------------------------------------
@@ -627,3 +641,166 @@ def down_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or gamma.requires_grad or beta.requires_grad):
         return _DownBnBlockFunction.apply(x, weight, gamma, beta, running, float(momentum), float(eps), act_id)
     return _bn_forward(x.detach(), weight.detach(), gamma.detach(), beta.detach(), running, float(momentum), float(eps), act_id, 2)[0]
+
+
+# ---- the max-pools of YOLOv3-tiny / LiteYOLOv3: MaxPool and ConvPoolBlock as they train -----------------------------------
+def _pool_forward(xn, stride):
+    """The pool launch on the dense bf16 [n, h, w, c] xn: (y, idx), both dense NHWC."""
+    n, h, w, c = xn.shape
+    ho, wo = (h // 2, w // 2) if stride == 2 else (h, w)
+    y = torch.empty((n, ho, wo, c), dtype=torch.bfloat16, device=xn.device)
+    idx = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=xn.device)
+    K.maxpool_train_fwd(xn, y, idx, stride)
+    return y, idx
+
+
+def _pool_backward(dy, idx, shape, stride):
+    """dy (NCHW-shaped, any layout / dtype) -> the dense bf16 [n, h, w, c] gradient of the pool's input."""
+    dx = torch.empty(shape, dtype=torch.bfloat16, device=idx.device)
+    K.maxpool_bwd(_dense_bf16(dy).permute(0, 2, 3, 1), idx, dx, stride)
+    return dx
+
+
+class _MaxPoolFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, stride):
+        xn = x.permute(0, 2, 3, 1)
+        with torch.cuda.device(x.device):
+            y, idx = _pool_forward(xn, stride)
+        ctx.shape, ctx.stride = tuple(xn.shape), stride
+        ctx.save_for_backward(idx)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        idx, = ctx.saved_tensors
+        with torch.cuda.device(idx.device):
+            dx = _pool_backward(dy, idx, ctx.shape, ctx.stride)
+        return dx.permute(0, 3, 1, 2), None
+
+
+def _check_pool(name, stride, h, w):
+    if isinstance(stride, bool) or stride not in (1, 2):
+        raise ValueError(f"{name}: pool stride must be 2 (MaxPool2d(2, 2)) or 1 (MaxPool2d(2, 1, padding=1, dilation=2)), not {stride!r}")
+    if h < 2 or w < 2:
+        raise ValueError(f"{name}: the pool needs a map of at least 2 x 2, got {h} x {w} (stride 2: empty output; stride 1: a window "
+                         "would be all padding)")
+
+
+def max_pool(x, *, stride=2):
+    """The reference's MaxPool (models/yolo_base.py:60-66) on the device, differentiable once.  ``stride=2``: ``max_pool2d(x, 2, 2)``
+    (floor: an odd last row or column is dropped); ``stride=1``: ``max_pool2d(x, 2, 1, padding=1, dilation=2)``, the form MaxPool(2, 1)
+    turns into - the four diagonal neighbours, the output has the input's size.  x [n, c, h, w], ``c % 8 == 0``, h and w >= 2; bfloat16
+    dense channels-last is taken as it is, anything else is converted by torch.  Returns bfloat16, channels-last.  The gradient of a window
+    goes to its first maximum in row-major order (torch's rule); at stride 1 the up to four terms of a pixel are summed in fp32 in a fixed
+    order and rounded once.  x must hold no NaN.  Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there
+    is no CPU fallback)."""
+    _check_map("max_pool", "x", x)
+    _check_pool("max_pool", stride, x.shape[2], x.shape[3])
+    if not x.is_cuda:
+        raise RuntimeError("pytorch_yolo_amd.max_pool runs on a ROCm device only (no CPU fallback)")
+    return _MaxPoolFunction.apply(_dense_bf16(x), int(stride))
+
+
+def _pool_bn_forward(x, weight, gamma, beta, running, momentum, eps, act_id, pool_stride):
+    """conv (act none) -> batch statistics over the unpooled z -> normalise, activate and pool: the fused pass at pool stride 2, the two
+    separate launches at stride 1.  Returns the NCHW-shaped pooled result, the conv's descriptor, z, saved and idx."""
+    z, d = _forward(x, weight, None, ACT_NONE, False)
+    z = z.permute(0, 2, 3, 1)
+    with torch.cuda.device(x.device):
+        saved = torch.empty((4, d.cout), dtype=torch.float32, device=x.device)
+        ws = torch.empty((K.bn_workspace_bytes(d.n * d.h * d.w, d.cout),), dtype=torch.uint8, device=x.device)
+        K.bn_train_stats(z, gamma, beta, eps, momentum, running[0], running[1], saved, ws)
+        if pool_stride == 2:
+            y = torch.empty((d.n, d.h // 2, d.w // 2, d.cout), dtype=torch.bfloat16, device=x.device)
+            idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+            K.bn_act_pool_fwd(z, saved, y, idx, act_id)
+        else:
+            full = torch.empty_like(z)
+            K.bn_act_fwd(z, saved, full, act_id)
+            y, idx = _pool_forward(full, 1)
+    return y.permute(0, 3, 1, 2), d, z, saved, idx
+
+
+class _PoolBnBlockFunction(torch.autograd.Function):
+    """_pool_bn_forward with a backward: yolo_maxpool_bwd expands dy to a full-resolution bf16 map, which goes through conv_bn_block's
+    backward (yolo_bn_act_bwd, then the conv's weight and data gradients), each only where asked.  x, weight, z, saved and idx are kept."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, running, momentum, eps, act_id, pool_stride):
+        out, d, z, saved, idx = _pool_bn_forward(x, weight, gamma.detach(), beta.detach(), running, momentum, eps, act_id, pool_stride)
+        ctx.desc, ctx.act_id, ctx.pool_stride = d, act_id, pool_stride
+        ctx.save_for_backward(x, weight, z, saved, idx)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, z, saved, idx = ctx.saved_tensors
+        d = ctx.desc
+        need_x, need_w, need_g, need_b = ctx.needs_input_grad[:4]
+        dx = dw = dgamma = dbeta = g = None
+        with torch.cuda.device(x.device):
+            dfull = _pool_backward(dy, idx, tuple(z.shape), ctx.pool_stride)
+            if need_x or need_w:
+                g = torch.empty_like(z)
+            if need_g:
+                dgamma = torch.empty((d.cout,), dtype=torch.float32, device=x.device)
+            if need_b:
+                dbeta = torch.empty((d.cout,), dtype=torch.float32, device=x.device)
+            ws = torch.empty((K.bn_workspace_bytes(d.n * d.h * d.w, d.cout),), dtype=torch.uint8, device=x.device)
+            K.bn_act_bwd(dfull, z, saved, ctx.act_id, True, g, dgamma, dbeta, ws)
+            if need_w:
+                dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)
+                ws = torch.empty((K.conv2d_bwd_workspace_bytes(d),), dtype=torch.uint8, device=x.device)
+                K.conv2d_bwd_weight(x, g, dw, None, ws, d)
+            if need_x:
+                packed_t, _, _ = K.pack_conv_weight_dev(weight, d.cout, transposed=True)
+                buf = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=x.device)
+                K.conv2d_bwd_data(g, packed_t, buf, d)
+                dx = buf.permute(0, 3, 1, 2)
+        return dx, dw, dgamma, dbeta, None, None, None, None, None
+
+
+def pool_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *, pool_stride=2, training=True, momentum=0.1, eps=1e-5,
+                  act="leaky"):
+    """``max_pool(act(batch_norm(conv2d(x, bf16(weight), padding=k // 2))), stride=pool_stride)`` on the device, differentiable once: the
+    reference's ConvPoolBlock (models/yolo_base.py:69-80) as it trains.
+
+    conv_bn_block's contract at stride 1 with ``training=True`` (anything else raises ValueError).  The conv, the batch statistics and the
+    update of the running tensors run over the unpooled map.  ``pool_stride=2``: the normalise-and-activate pass pools as it goes
+    (yolo_bn_act_pool_fwd; the full-resolution activation is never written); ``pool_stride=1``: yolo_bn_act_fwd, then the stride-1 pool.
+    Both are max_pool's forms and rules, and the result is bit-equal to ``max_pool(conv_bn_block(...), stride=pool_stride)``.
+    The backward expands the incoming gradient to the unpooled map (yolo_maxpool_bwd) and continues as conv_bn_block's.
+    Gradients: x bf16, weight, gamma and beta float32, each computed only where asked; two runs give the same bits."""
+    if not isinstance(x, torch.Tensor) or not isinstance(weight, torch.Tensor) or x.dim() != 4 or weight.dim() != 4:
+        raise ValueError("pool_bn_block: x must be [n, cin, h, w] and weight [cout, cin, k, k]")
+    if not training:
+        raise ValueError("pool_bn_block: training=True only (the frozen layer is the models' inference path)")
+    if act not in _ACTS:
+        raise ValueError(f"pool_bn_block: act must be 'leaky' or 'none', not {act!r}")
+    _check_momentum_eps("pool_bn_block", momentum, eps)
+    cout, cin, k, k2 = weight.shape
+    if k != k2 or k not in (1, 3):
+        raise ValueError(f"pool_bn_block: kernel {k}x{k2} unsupported (1x1 or 3x3)")
+    if x.shape[1] != cin:
+        raise ValueError(f"pool_bn_block: x has {x.shape[1]} channels, weight expects {cin}")
+    if min(x.shape) < 1 or cout < 1:
+        raise ValueError("pool_bn_block: empty tensor")
+    if cout % 8:
+        raise ValueError(f"pool_bn_block: cout % 8 == 0 is required (cout {cout})")
+    if weight.dtype != torch.float32:
+        raise ValueError("pool_bn_block: weight must be float32 [cout, cin, k, k]")
+    _check_pool("pool_bn_block", pool_stride, x.shape[2], x.shape[3])
+    vectors = _check_bn_vectors("pool_bn_block", cout, gamma, beta, running_mean, running_var, True)
+    if not (x.is_cuda and weight.is_cuda and all(t is None or t.is_cuda for _, t in vectors)):
+        raise RuntimeError("pytorch_yolo_amd.pool_bn_block runs on a ROCm device only (no CPU fallback)")
+    x, weight = _to_kernel_layout(x, weight)
+    gamma, beta = gamma.contiguous(), beta.contiguous()
+    running = _running("pool_bn_block", running_mean, running_var)
+    act_id, pool_stride = _ACTS[act], int(pool_stride)
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or gamma.requires_grad or beta.requires_grad):
+        return _PoolBnBlockFunction.apply(x, weight, gamma, beta, running, float(momentum), float(eps), act_id, pool_stride)
+    return _pool_bn_forward(x.detach(), weight.detach(), gamma.detach(), beta.detach(), running, float(momentum), float(eps), act_id,
+                            pool_stride)[0]
