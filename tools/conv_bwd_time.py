@@ -92,6 +92,9 @@ def main():
         # the two computations agree (bf16 weight gradient on the torch side: compared at its precision)
         _, tdw, tdb = aten.convolution_backward(g[..., :cout].permute(0, 3, 1, 2), tx, tw, *conv_args, [False, True, True])
         worst = float((dw - tdw.float()).abs().max()) / float(dw.abs().max())
+        # ... and so do the data gradients: both sides round dx once to bf16, on the same g and the same bf16 weight
+        tdx, _, _ = aten.convolution_backward(g[..., :cout].permute(0, 3, 1, 2), tx, tw, *conv_args, [True, False, False])
+        worst_dx = float((dx.float() - tdx.permute(0, 2, 3, 1).float()).abs().max()) / float(dx.float().abs().max())
         times = {s: [] for s, _ in sides}
         for _ in range(args.repeats):
             for s, fn in sides:
@@ -113,7 +116,7 @@ def main():
         losers = [p for p, a, b in (("prepare", best["prepare"], best.get("torch_act", float("inf"))), ("wgrad", best["bwd_weight"], best["torch_wgrad"]),
                                     ("data gradient", best["bwd_data"], best["torch_dgrad"])) if a > b]
         notes.append(f"- {name}: ours {ours:.1f} us, torch {theirs:.1f} us; " + ("slower than torch in: " + ", ".join(losers) if losers else "no piece slower than torch") +
-                     f"; largest |dW - torch dW| / max |dW| = {worst:.1e} (torch's dW is bf16).")
+                     f"; largest |dW - torch dW| / max |dW| = {worst:.1e} (torch's dW is bf16), largest |dx - torch dx| / max |dx| = {worst_dx:.1e} (both bf16).")
     lines += ["", "Per shape, which piece loses to torch (best windows):", ""] + notes + [
         "", "The torch side is handed bf16 channels-last tensors and a bf16 weight (what `F.conv2d` autograd sees under bf16), its wgrad window",
         "includes the bias gradient, and for the heads (act none) it has no activation backward while ours still casts the fp32 dy to g.", ""]
