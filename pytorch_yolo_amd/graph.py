@@ -98,6 +98,24 @@ class Recorder:
             self.nodes[-1].attrs["pad"] = pad            # (SqueezeNet's unpadded first conv; no fused form takes it)
         return (y, outs[1]) if want_preadd else y
 
+    # The three methods below and maxpool / spp_concat / head are the vocabulary a trainable model's ``_trace`` keeps to:
+    # models/train.TrainTracer has the same names and runs them on tensors, so one ``_trace`` is both wirings.
+    def conv_block(self, block, x: Sym, **kw):
+        """A ConvBlock (conv + folded BN + LeakyReLU) and, where the block has one, its max-pool (ConvPoolBlock)."""
+        y = self.conv(x, block.folded(), stride=block.stride, act="leaky", name=getattr(block, "_trace_name", None), **kw)
+        pool = getattr(block, "pool", None)
+        return y if pool is None else self.maxpool(y, pool.size, pool.stride)
+
+    def plain_conv(self, conv, x: Sym):
+        """A biased ``nn.Conv2d(C, 3 (5 + nc), 1)`` without BN or activation, float32 out: the last layer of a plain head."""
+        return self.conv(x, (conv.weight.detach().float().cpu(), conv.bias.detach().float().cpu()), stride=1,
+                         act="none", f32_out=True, name=getattr(conv, "_trace_name", None))
+
+    def upsample_concat(self, a: Sym, b: Sym, up_first=True):
+        """cat([nearest_x2(a), b]), or cat([b, nearest_x2(a)]) with ``up_first=False``."""
+        up = self.upsample2(a)
+        return self.concat([up, b] if up_first else [b, up])
+
     def dwconv(self, x: Sym, weight, stride=1, act="relu6", tf_same=False):
         """Depthwise k x k conv.  Default: 3x3 / pad 1 (MobileNetV2).  ``tf_same``: k = 3 or 5 with TensorFlow "same" padding
         (EfficientNet-B0's MBConvBlock._depthwise_conv) - the general kernel, which also takes the swish activation."""

@@ -9,7 +9,6 @@ from . import train as T
 from .yolo_base import ConvBlock, ConvPoolBlock, YOLOBase
 from .yolo_layer import Concat, Upsample
 from .yolov3 import _seq
-from .yolov3_tiny import plain_head
 
 
 class Conv(nn.Module):
@@ -72,29 +71,14 @@ class LiteYOLOv3(YOLOBase):
             x = m._trace(g, x)
             downs.append(x)
         x = self.seq.conv1._trace(g, x)
-        g.head(plain_head(g, self.seq_y1.conv1._trace(g, x), self.seq_y1.conv2), self.yolo1)
-        y = g.concat([g.upsample2(self.seqy2_1.conv._trace(g, x)), downs[3]])
+        g.head(g.plain_conv(self.seq_y1.conv2, self.seq_y1.conv1._trace(g, x)), self.yolo1)
+        y = g.upsample_concat(self.seqy2_1.conv._trace(g, x), downs[3])
         y = self.seqy2_2.conv2._trace(g, self.seqy2_2.conv1._trace(g, y))
-        g.head(plain_head(g, self.seqy2_3.conv6._trace(g, y), self.seqy2_3.conv7), self.yolo2)
-        z = g.concat([g.upsample2(self.seqy3_1.conv._trace(g, y)), downs[2]])
+        g.head(g.plain_conv(self.seqy2_3.conv7, self.seqy2_3.conv6._trace(g, y)), self.yolo2)
+        z = g.upsample_concat(self.seqy3_1.conv._trace(g, y), downs[2])
         z = self.seqy3_2.conv1._trace(g, z)
         g.head(self.seqy3_2.conv2._trace(g, z, f32_out=True), self.yolo3)
 
     # the training step is reached through pytorch_yolo_amd.forward_train(model, x); model.train()(x) keeps raising
     _train_in_forward = False
-
-    def _train_wiring(self, ops, x):
-        """The same wiring in training mode on the ops of a table (models/train.py): the three raw head maps [bs, 3 (5 + nc), ny, nx]."""
-        pair = lambda m, t: T.conv_bn(ops, m.conv2, T.conv_bn(ops, m.conv1, t))                  # Conv: 1x1 then 3x3
-        downs = []
-        for m in self.down:
-            x = T.conv_bn(ops, m.conv_pool, T.conv_bn(ops, m.conv, x)) if isinstance(m, Down) else T.conv_bn(ops, m, x)
-            downs.append(x)
-        x = T.conv_bn(ops, self.seq.conv1, x)
-        b1 = T.head(ops, T.conv_bn(ops, self.seq_y1.conv1, x), self.seq_y1.conv2)
-        y = ops.upsample_concat(T.conv_bn(ops, self.seqy2_1.conv, x), downs[3])
-        y = T.conv_bn(ops, self.seqy2_2.conv2, pair(self.seqy2_2.conv1, y))
-        b2 = T.head(ops, T.conv_bn(ops, self.seqy2_3.conv6, y), self.seqy2_3.conv7)
-        z = ops.upsample_concat(T.conv_bn(ops, self.seqy3_1.conv, y), downs[2])
-        b3 = T.head(ops, pair(self.seqy3_2.conv1, z), self.seqy3_2.conv2)
-        return b1, b2, b3
+    _train_wiring = T.wiring          # training runs the same _trace on the ops of a table (models/train.py)

@@ -2,11 +2,13 @@
 reference's ``model.train()(x)`` - batch-statistics BN, the raw ``p`` list with a ``grad_fn`` - wired from the differentiable ops of
 pytorch_yolo_amd.ops.
 
-The wiring (``model._train_wiring``) takes every op from a table, a namespace of functions: the default table runs the package's
-kernels; the tests run the same Python wiring on the CPU with float64 torch restatements of the ops, which is how it is compared with
-the reference without a GPU.  A table function has the signature of the op it stands for.  ``DEVICE_OPS`` holds the six functions the
-Darknet-53 models use; ``DEVICE_OPS_POOL`` adds ``max_pool`` and ``pool_bn_block`` and is the table ``forward_train`` runs by default
-(the ``up_first`` keyword of ``upsample_concat`` goes through both).
+A model states its layer graph once, in ``_trace``.  For inference graph.Recorder records it; for training ``wiring`` (every trainable
+class's ``_train_wiring``) runs the same ``_trace`` through a ``TrainTracer``, which has the Recorder's method names and runs each call at
+once on tensors.  The tracer takes every op from a table, a namespace of functions: the default table runs the package's kernels; the
+tests run the same wiring on the CPU with float64 torch restatements of the ops, which is how it is compared with the reference without a
+GPU.  A table function has the signature of the op it stands for.  ``DEVICE_OPS`` holds the six functions the Darknet-53 models use;
+``DEVICE_OPS_POOL`` adds ``max_pool`` and ``pool_bn_block`` and is the table ``forward_train`` runs by default (the ``up_first`` keyword
+of ``upsample_concat`` goes through both).
 
 ``forward_train(model, x)`` is the public entry for all four classes.  ``model.train()(x)`` delegates to it for the classes whose
 ``_train_in_forward`` is True (YOLOv3, YOLOv3-SPP); YOLOv3-tiny and LiteYOLOv3 keep raising from the module call and train through the
@@ -20,7 +22,7 @@ import torch
 from torch import nn
 
 from .. import ops as _ops
-from .yolo_base import ConvBlock, ConvPoolBlock
+from .yolo_base import ConvPoolBlock
 
 DEVICE_OPS = SimpleNamespace(conv_block=_ops.conv_block, conv_bn_block=_ops.conv_bn_block, down_bn_block=_ops.down_bn_block,
                              res_bn_block=_ops.res_bn_block, spp_concat=_ops.spp_concat, upsample_concat=_ops.upsample_concat)
@@ -57,42 +59,45 @@ def conv_bn(ops, block, x, residual=None, want_preadd=False):
     return y
 
 
-def chain(ops, x, modules):
-    """The ConvBlocks of a Sequential in order (its Concat / Upsample markers are wired by the caller)."""
-    for m in modules:
-        if isinstance(m, ConvBlock):
-            x = conv_bn(ops, m, x)
-    return x
+class TrainTracer:
+    """What a model's ``_trace`` drives in training mode: the method names of graph.Recorder that a trainable model uses, run at once on
+    tensors through the op table ``ops``.  It has no ``conv``, ``dwconv``, ``se``, ``slice``, ``shuffle2``, ``concat`` or ``upsample2``: a
+    class whose ``_trace`` needs one has no ``_train_wiring`` and is refused by ``forward_train`` before it gets here."""
+
+    def __init__(self, ops, yolo_layers):
+        self.ops, self.yolo_layers, self.branches = ops, tuple(yolo_layers), []
+
+    def conv_block(self, block, x, residual=None, want_preadd=False, f32_out=False):
+        """A ConvBlock (``conv_bn``; a ConvPoolBlock's pool is part of its op); ``f32_out``: the last layer of a head as float32."""
+        y = conv_bn(self.ops, block, x, residual, want_preadd)
+        return y.float() if f32_out and y.dtype == torch.bfloat16 else y    # (a table that works in float32 / float64 keeps its dtype)
+
+    def plain_conv(self, conv, x):
+        return self.ops.conv_block(x, conv.weight, conv.bias, act="none", out_dtype=torch.float32)
+
+    def maxpool(self, x, size, stride):
+        if (size, stride) != (2, 2):
+            raise NotImplementedError(f"the training-mode forward has no stand-alone max-pool of size {size} / stride {stride} (2 / 2 only)")
+        return self.ops.max_pool(x, stride=2)
+
+    def spp_concat(self, x):
+        return self.ops.spp_concat(x)
+
+    def upsample_concat(self, a, b, up_first=True):
+        # (no keyword where the upsampled map comes first: the tables of the Darknet-53 models take two arguments)
+        return self.ops.upsample_concat(a, b) if up_first else self.ops.upsample_concat(a, b, up_first=False)
+
+    def head(self, x, layer):
+        if len(self.branches) >= len(self.yolo_layers) or layer is not self.yolo_layers[len(self.branches)]:
+            raise RuntimeError(f"head {len(self.branches)} of the trace is not yolo_layers[{len(self.branches)}]: the heads are out of order")
+        self.branches.append(x)
 
 
-def head(ops, x, module):
-    """The last layer of a head as float32: a ConvBlock (YOLOv3-SPP's three heads, YOLOv3's third) or a plain biased nn.Conv2d."""
-    if isinstance(module, nn.Conv2d):
-        return ops.conv_block(x, module.weight, module.bias, act="none", out_dtype=torch.float32)
-    y = conv_bn(ops, module, x)
-    return y.float() if y.dtype == torch.bfloat16 else y         # (a table that works in float32 / float64 keeps its dtype)
-
-
-def down_stage(ops, stage, x, need_sub):
-    """One Darknet-53 stage (reference models/yolov3_spp.py:38-46): (x, sub), sub the last unit's branch output before its add."""
-    x = conv_bn(ops, stage.conv0, x)
-    sub = None
-    for i in range(stage.n_units):
-        squeeze, expand = getattr(stage, f"seq{i}")
-        last = need_sub and i == stage.n_units - 1
-        out = conv_bn(ops, expand, conv_bn(ops, squeeze, x), residual=x, want_preadd=last)
-        x, sub = out if last else (out, None)
-    return x, sub
-
-
-def encoder(ops, model, x):
-    """conv1 and the five stages: (x, subs); only downs[2] and downs[3] are routed (reference models/yolov3_spp.py:133,137)."""
-    x = conv_bn(ops, model.conv1, x)
-    subs = []
-    for i, stage in enumerate(model.down):
-        x, sub = down_stage(ops, stage, x, need_sub=i in (2, 3))
-        subs.append(sub)
-    return x, subs
+def wiring(model, ops, x):
+    """``model._train_wiring``: the raw head maps [bs, 3 (5 + nc), ny, nx] of ``model._trace`` run on the ops of a table."""
+    g = TrainTracer(ops, model.yolo_layers)
+    model._trace(g, x)
+    return tuple(g.branches)
 
 
 def forward_train(model, x, ops=None):

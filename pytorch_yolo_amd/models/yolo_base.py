@@ -69,7 +69,7 @@ class ConvBlock(nn.Module):
         _STRUCT_EPOCH[0] += 1
 
     def _trace(self, g: engine.Recorder, x, **kw):
-        return g.conv(x, self.folded(), stride=self.stride, act="leaky", name=getattr(self, "_trace_name", None), **kw)
+        return g.conv_block(self, x, **kw)
 
     def forward(self, x):
         return engine.run_standalone(lambda g, s: self._trace(g, s), x)
@@ -100,9 +100,6 @@ class ConvPoolBlock(ConvBlock):
     @property
     def pool(self) -> MaxPool:
         return self.sequence[-1]
-
-    def _trace(self, g, x, **kw):
-        return self.pool._trace(g, super()._trace(g, x, **kw))
 
 
 class YOLOBase(nn.Module):

@@ -10,8 +10,7 @@ from .. import engine
 from . import train as T
 from .yolo_base import ConvBlock, YOLOBase
 from .yolo_layer import Concat, Upsample
-from .yolov3_spp import DownSample
-from .yolov3_tiny import plain_head
+from .yolov3_spp import DownSample, chain
 
 
 def _seq(named):
@@ -19,13 +18,6 @@ def _seq(named):
     for name, m in named:
         s.add_module(name, m)
     return s
-
-
-def _chain(g, x, modules, f32_last=False):
-    blocks = [m for m in modules if isinstance(m, ConvBlock)]
-    for i, b in enumerate(blocks):
-        x = b._trace(g, x, f32_out=f32_last and i == len(blocks) - 1)
-    return x
 
 
 class YOLOv3(YOLOBase):
@@ -68,25 +60,14 @@ class YOLOv3(YOLOBase):
         for i, stage in enumerate(self.down):
             x, sub = stage._trace(g, x, need_sub=i in (2, 3))
             subs.append(sub)
-        x = _chain(g, x, self.seq)
+        x = chain(g, x, self.seq)
         b1 = self.seq_y1.conv1._trace(g, x)
-        g.head(plain_head(g, b1, self.seq_y1.conv2), self.yolo1)
-        y = g.concat([g.upsample2(self.seqy2_1.conv._trace(g, x)), subs[3]])
-        y = _chain(g, y, self.seqy2_2)
+        g.head(g.plain_conv(self.seq_y1.conv2, b1), self.yolo1)
+        y = g.upsample_concat(self.seqy2_1.conv._trace(g, x), subs[3])
+        y = chain(g, y, self.seqy2_2)
         b2 = self.seqy2_3.conv6._trace(g, y)
-        g.head(plain_head(g, b2, self.seqy2_3.conv7), self.yolo2)
-        z = g.concat([g.upsample2(self.seqy3_1.conv._trace(g, y)), subs[2]])
-        g.head(_chain(g, z, self.seqy3_2, f32_last=True), self.yolo3)
+        g.head(g.plain_conv(self.seqy2_3.conv7, b2), self.yolo2)
+        z = g.upsample_concat(self.seqy3_1.conv._trace(g, y), subs[2])
+        g.head(chain(g, z, self.seqy3_2, f32_last=True), self.yolo3)
 
-    def _train_wiring(self, ops, x):
-        """The same wiring in training mode on the ops of a table (models/train.py): the three raw head maps [bs, 3 (5 + nc), ny, nx]."""
-        x, subs = T.encoder(ops, self, x)
-        x = T.chain(ops, x, self.seq)
-        b1 = T.head(ops, T.conv_bn(ops, self.seq_y1.conv1, x), self.seq_y1.conv2)
-        y = ops.upsample_concat(T.conv_bn(ops, self.seqy2_1.conv, x), subs[3])
-        y = T.chain(ops, y, self.seqy2_2)
-        b2 = T.head(ops, T.conv_bn(ops, self.seqy2_3.conv6, y), self.seqy2_3.conv7)
-        z = ops.upsample_concat(T.conv_bn(ops, self.seqy3_1.conv, y), subs[2])
-        blocks = [m for m in self.seqy3_2 if isinstance(m, ConvBlock)]
-        b3 = T.head(ops, T.chain(ops, z, blocks[:-1]), blocks[-1])
-        return b1, b2, b3
+    _train_wiring = T.wiring          # training runs the same _trace on the ops of a table (models/train.py)

@@ -4,6 +4,7 @@ Host mirror of reference models/yolov3_spp.py: same constructor, module names
 (hence ``state_dict`` keys) and ``forward`` return structure.  The wiring is
 recorded once by ``_trace`` and executed by libyolo_hip.so; see
 pytorch_yolo_amd/engine.py for how Add / Upsample / Concat / SPP are fused away.
+Training runs the same ``_trace`` on tensors (models/train.py).
 """
 from __future__ import annotations
 
@@ -40,7 +41,7 @@ class DownSample(nn.Module):
 
     def _trace(self, g: engine.Recorder, x, need_sub=True):
         x = self.conv0._trace(g, x)
-        sub = x
+        sub = None
         for i in range(self.n_units):
             squeeze, expand = getattr(self, f"seq{i}")
             last = need_sub and i == self.n_units - 1
@@ -50,6 +51,15 @@ class DownSample(nn.Module):
 
     def forward(self, x):
         return engine.run_standalone(lambda g, s: self._trace(g, s, need_sub=True), x)
+
+
+def chain(g, x, modules, f32_last=False):
+    """The ConvBlocks of a Sequential in order (its Concat / Upsample markers are wired by the caller); ``f32_last``: the last one ends
+    a head."""
+    blocks = [m for m in modules if isinstance(m, ConvBlock)]
+    for i, b in enumerate(blocks):
+        x = b._trace(g, x, f32_out=f32_last and i == len(blocks) - 1)
+    return x
 
 
 class YOLOv3SPP(YOLOBase):
@@ -112,13 +122,6 @@ class YOLOv3SPP(YOLOBase):
     def yolo_layers(self):
         return self.yolo1, self.yolo2, self.yolo3
 
-    @staticmethod
-    def _chain(g, x, blocks, head_last=False):
-        blocks = [b for b in blocks if isinstance(b, ConvBlock)]
-        for i, b in enumerate(blocks):
-            x = b._trace(g, x, f32_out=head_last and i == len(blocks) - 1)
-        return x
-
     def _trace(self, g: engine.Recorder, x):
         """Reference _forward_encoder + forward (yolov3_spp.py:119-164)."""
         x = self.conv1._trace(g, x)
@@ -126,28 +129,16 @@ class YOLOv3SPP(YOLOBase):
         for i, stage in enumerate(self.down):
             x, sub = stage._trace(g, x, need_sub=i in (2, 3))      # only downs[2], downs[3] are routed (:133,:137)
             subs.append(sub)
-        x = self._chain(g, x, self.sequence_spp)
+        x = chain(g, x, self.sequence_spp)
         x = g.spp_concat(x)                                        # cat([p5, p9, p13, x]) :129
-        x = self._chain(g, x, self.branch1_1)
-        g.head(self._chain(g, x, self.branch1_2, head_last=True), self.yolo1)
+        x = chain(g, x, self.branch1_1)
+        g.head(chain(g, x, self.branch1_2, f32_last=True), self.yolo1)
 
-        y = g.concat([g.upsample2(self.branch2_1[0]._trace(g, x)), subs[3]])       # :132-133
-        y = self._chain(g, y, self.branch2_2)
-        g.head(self._chain(g, y, self.branch2_3, head_last=True), self.yolo2)
+        y = g.upsample_concat(self.branch2_1[0]._trace(g, x), subs[3])             # :132-133
+        y = chain(g, y, self.branch2_2)
+        g.head(chain(g, y, self.branch2_3, f32_last=True), self.yolo2)
 
-        z = g.concat([g.upsample2(self.branch3_1[0]._trace(g, y)), subs[2]])       # :136-137
-        g.head(self._chain(g, z, self.branch3_2, head_last=True), self.yolo3)
+        z = g.upsample_concat(self.branch3_1[0]._trace(g, y), subs[2])             # :136-137
+        g.head(chain(g, z, self.branch3_2, f32_last=True), self.yolo3)
 
-    def _train_wiring(self, ops, x):
-        """The same wiring in training mode on the ops of a table (models/train.py): the three raw head maps [bs, 3 (5 + nc), ny, nx]."""
-        x, subs = T.encoder(ops, self, x)
-        x = T.chain(ops, x, self.sequence_spp)
-        x = T.chain(ops, ops.spp_concat(x), self.branch1_1)                                   # :129
-        b1 = T.head(ops, T.conv_bn(ops, self.branch1_2.conv1, x), self.branch1_2.conv2)
-        y = ops.upsample_concat(T.conv_bn(ops, self.branch2_1[0], x), subs[3])                # :132-133
-        y = T.chain(ops, y, self.branch2_2)
-        b2 = T.head(ops, T.conv_bn(ops, self.branch2_3.conv6, y), self.branch2_3.conv7)
-        z = ops.upsample_concat(T.conv_bn(ops, self.branch3_1[0], y), subs[2])                # :136-137
-        blocks = [m for m in self.branch3_2 if isinstance(m, ConvBlock)]
-        b3 = T.head(ops, T.chain(ops, z, blocks[:-1]), blocks[-1])
-        return b1, b2, b3
+    _train_wiring = T.wiring          # training runs the same _trace on the ops of a table (models/train.py)

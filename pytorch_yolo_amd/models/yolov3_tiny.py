@@ -17,12 +17,6 @@ class _Pool22(nn.MaxPool2d):
         return g.maxpool(x, 2, 2)
 
 
-def plain_head(g: engine.Recorder, x, conv: nn.Conv2d):
-    """nn.Conv2d(C, 3*(5+nc), kernel_size=1) with bias, no BN / activation (yolov3_tiny.py:38,42)."""
-    return g.conv(x, (conv.weight.detach().float().cpu(), conv.bias.detach().float().cpu()), stride=1,
-                  act="none", f32_out=True, name=getattr(conv, "_trace_name", None))
-
-
 class YOLOv3Tiny(YOLOBase):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -81,25 +75,16 @@ class YOLOv3Tiny(YOLOBase):
     # the training step is reached through pytorch_yolo_amd.forward_train(model, x); model.train()(x) keeps raising
     _train_in_forward = False
     _train_min_size = 64          # at 32 the stride-1 pool after conv6 would see a 1x1 map
-
-    def _train_wiring(self, ops, x):
-        """The same wiring in training mode on the ops of a table (models/train.py): the two raw head maps [bs, 3 (5 + nc), ny, nx]."""
-        route1 = T.chain(ops, x, self.sequence_1)
-        s2 = self.sequence_2
-        route2 = T.chain(ops, ops.max_pool(route1, stride=2), [s2.conv6, s2.conv7, s2.conv8])
-        up = T.conv_bn(ops, self.sequence_branch1_1.branch1_conv1, route2)
-        b1 = ops.upsample_concat(up, route1, up_first=False)                 # order [route1, upsampled] (yolov3_tiny.py:73)
-        b1 = T.head(ops, T.conv_bn(ops, self.sequence_branch1_2.branch1_conv2, b1), self.sequence_branch1_2.branch1_conv3)
-        b2 = T.head(ops, T.conv_bn(ops, self.sequence_branch2.branch2_conv1, route2), self.sequence_branch2.branch2_conv2)
-        return b1, b2
+    _train_wiring = T.wiring      # training runs the same _trace on the ops of a table (models/train.py)
 
 
 def trace_tiny_heads(model, g, route1, route2):
     """Tiny-style FPN head shared with the MobileNetV2 variant
-    (yolov3_tiny.py:30-43,72-77; yolov3_tiny_mobilenet.py:58-69,81-86)."""
-    up = g.upsample2(model.sequence_branch1_1.branch1_conv1._trace(g, route2))
-    b1 = g.concat([route1, up])                                          # order [route1, upsampled] (:73)
+    (yolov3_tiny.py:30-43,72-77; yolov3_tiny_mobilenet.py:58-69,81-86).  A plain head ends in a biased 1x1 nn.Conv2d without BN or
+    activation (yolov3_tiny.py:38,42)."""
+    up = model.sequence_branch1_1.branch1_conv1._trace(g, route2)
+    b1 = g.upsample_concat(up, route1, up_first=False)                   # order [route1, upsampled] (:73)
     b1 = model.sequence_branch1_2.branch1_conv2._trace(g, b1)
-    g.head(plain_head(g, b1, model.sequence_branch1_2.branch1_conv3), model.yolo1)
+    g.head(g.plain_conv(model.sequence_branch1_2.branch1_conv3, b1), model.yolo1)
     b2 = model.sequence_branch2.branch2_conv1._trace(g, route2)
-    g.head(plain_head(g, b2, model.sequence_branch2.branch2_conv2), model.yolo2)
+    g.head(g.plain_conv(model.sequence_branch2.branch2_conv2, b2), model.yolo2)

@@ -26,7 +26,6 @@ from ..kernels import roundup
 from ..utils.torch_utils import fold_conv_bn
 from .yolo_base import ConvBlock, YOLOBase
 from .yolo_layer import Concat, Upsample
-from .yolov3_tiny import plain_head
 
 _STAGES = ((4, 116), (8, 232), (4, 464))
 _SLOT = 32      # slot granule: 8 channels would do for the views; 32 keeps every 1x1 / 3x3 conv on the LDS-DMA fast path
@@ -174,6 +173,6 @@ class YOLOv3TinyShuffle(YOLOBase):
         blk = self.sequence_branch1_2.branch1_conv2                      # its weights see 232 + 128 logical channels
         cmap = map1 + [route1.c + i for i in range(up.c)]
         b1 = g.conv(cat, _scatter(blk.folded(), list(range(blk.out_channels)), blk.out_channels, cmap, cat.c), act="leaky")
-        g.head(plain_head(g, b1, self.sequence_branch1_2.branch1_conv3), self.yolo1)
+        g.head(g.plain_conv(self.sequence_branch1_2.branch1_conv3, b1), self.yolo1)
         b2 = self.sequence_branch2.branch2_conv1._trace(g, route2)
-        g.head(plain_head(g, b2, self.sequence_branch2.branch2_conv2), self.yolo2)
+        g.head(g.plain_conv(self.sequence_branch2.branch2_conv2, b2), self.yolo2)

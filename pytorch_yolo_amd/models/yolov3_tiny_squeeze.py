@@ -16,7 +16,6 @@ from torch import nn
 from .. import engine
 from .yolo_base import ConvBlock, YOLOBase
 from .yolo_layer import Concat
-from .yolov3_tiny import plain_head
 
 
 def _wb(conv: nn.Conv2d):
@@ -134,6 +133,6 @@ class YOLOv3TinySqueeze(YOLOBase):
         b1 = self.sequence_branch1_1.branch1_conv1._trace(g, route2)
         b1 = g.concat([route1, b1])                                        # [x_route1, x_branch1] (:77), same grid
         b1 = self.sequence_branch1_2.branch1_conv2._trace(g, b1)
-        g.head(plain_head(g, b1, self.sequence_branch1_2.branch1_conv3), self.yolo1)
+        g.head(g.plain_conv(self.sequence_branch1_2.branch1_conv3, b1), self.yolo1)
         b2 = self.sequence_branch2.branch2_conv1._trace(g, route2)
-        g.head(plain_head(g, b2, self.sequence_branch2.branch2_conv2), self.yolo2)
+        g.head(g.plain_conv(self.sequence_branch2.branch2_conv2, b2), self.yolo2)
