@@ -89,6 +89,16 @@ typedef struct YoloConvDesc {
   int32_t aux_c_total, aux_c_offset; /* pre-add copy view (bf16)                           */
 } YoloConvDesc;
 
+/* Operand sizes.  The conv kernels address x and the packed weights with 32-bit byte offsets: the bytes behind the x VIEW,
+ * n * h * w * in_c_total * 2, and cout_pad * kpad * 2 must stay below 0xF0000000 (3.75 GiB); from there on yolo_conv2d_fwd,
+ * yolo_conv2d_f16_fwd, yolo_conv3x3_t20_f16_fwd, yolo_head_decode_*_fwd and yolo_resunit_fwd return YOLO_E_UNSUPPORTED
+ * ("tensor larger than 3.75 GiB not supported"), and n * ho * wo must stay below 2^31 / 4 pixels ("M out of range").  y, the
+ * residual and the pre-add copy have no such limit: at 0xF0000000 bytes (n * ho * wo * c_total * 2) the forms that address them
+ * with 32-bit offsets step aside for one that writes through 64-bit pointers - the 20x20-tile 3x3 kernels (t20v2, t20s2) for the
+ * halo or the gather kernel, the streaming 1x1 forms (stream1x1, stream1x1p) for the gather kernel - which yolo_conv2d_pick names.
+ * tests/test_large_operands_cpu.py pins both sides of each bound, tests/test_large_operands_gpu.py runs every family on operands
+ * of 0xEECC8000 bytes and the fallbacks on a y of 0x113898000 bytes. */
+
 /* w_packed: bf16 [cout_pad][kpad], k = (kh*ksize + kw)*cin + c  (yolo_pack_conv_weight_f32).
  * bias: f32 [cout_pad].  residual / y_preadd may be NULL. */
 YOLO_API int yolo_conv2d_fwd(const void* x, const void* w_packed, const float* bias, const void* residual,
@@ -346,7 +356,10 @@ YOLO_API int yolo_spp_fwd(void* buf, int n, int h, int w, int c, yolo_stream_t s
  *  d describes the 3x3/s1/p1 conv: cin = C/2, cout = C, kpad/cout_pad = packing of W2; its INPUT view fields
  *  (in_c_total/in_c_offset) describe x (C channels); res_* fields are ignored.  W1 is packed like any 1x1
  *  ([cout_pad1][kpad1]).  y must not alias x.  yolo_resunit_supported(): C in {64,128,256} on maps >= 80x80 that
- *  tile well by 16x16; other shapes use two yolo_conv2d_fwd calls. */
+ *  tile well by 16x16; other shapes use two yolo_conv2d_fwd calls.
+ *  Operand sizes (see YoloConvDesc): x - the residual too - and the weights below 0xF0000000 bytes, else YOLO_E_UNSUPPORTED; a y or
+ *  a pre-add copy of 0xF0000000 bytes and more hands the unit from the 20-pixel-wide tile kernels (resunit64_t20, resunit_t20w) to
+ *  the 16x16-tile ones (resunit64, resunit), which write through 64-bit pointers. */
 YOLO_API int yolo_resunit_supported(int c, int h, int w);
 /** Which kernel yolo_resunit_fwd launches for a C-channel unit on n maps of h x w: 0 not supported, 1 the generic 16x16-tile kernel
  *  (slower than the two-launch path above C = 64: a planner should not fuse there), 2 the persistent 64-channel kernel, 3 the
@@ -364,7 +377,9 @@ YOLO_API int yolo_resunit_fwd(const void* x, const void* w1_packed, const float*
  *  ConvBlock 3x3/s2 32->64, :26-27):  y = act(conv_s2(act(conv_s1(x,W1)+b1), W2)+b2), x = float32 NCHW
  *  [n,cin_real,h,w] (1..8 channels), y = bf16 NHWC view at h/2 x w/2.  The 32-channel intermediate (the
  *  largest activation of the network) stays in LDS.  d describes the stride-2 conv (h,w = input size,
- *  cin 32, cout 64, kpad = packing of W2); W1 is packed as for yolo_conv1_nchw_f32_fwd (cin = 8, kpad1 >= 80). */
+ *  cin 32, cout 64, kpad = packing of W2); W1 is packed as for yolo_conv1_nchw_f32_fwd (cin = 8, kpad1 >= 80).
+ *  Operand sizes: stem2 addresses x and y with 32-bit offsets; from 0xF0000000 bytes of x (n * 3 * h * w * 4) or of y
+ *  (n * ho * wo * out_c_total * 2) on the one-role kernel "stem<...,CIN 3,...>" runs instead, on 64-bit pointers. */
 YOLO_API int yolo_stem_supported(int cin_real, int c1, int c2, int h, int w);
 /** The kernel + grid yolo_stem_fwd would launch under the current tuning: "stem2<leaky,8x16 outputs> grid N" (3 input channels) or
  *  "stem<leaky,CIN 0,16x16 outputs> grid N" (CIN 3: three channels under knob 6 or beyond 32-bit offsets).  Runs the checks of
@@ -388,7 +403,10 @@ YOLO_API int yolo_stem_fwd(const float* x_nchw, int cin_real, const void* w1_pac
  *       in 64..160 (stride 2: ..96), hidden a multiple of 64, cout <= 320, expand conv present.  Plain row-major matrices,
  *       read through buffer descriptors:  w_exp bf16 [hidden][cin], b_exp f32 [hidden], w_dw f32 [9][hidden], b_dw f32 [hidden],
  *       w_proj bf16 [cout_pad][hidden], b_proj f32 [cout_pad];
- *    0  not covered: the block runs as yolo_conv2d_fwd + yolo_dwconv3x3_fwd + yolo_conv2d_fwd. */
+ *    0  not covered: the block runs as yolo_conv2d_fwd + yolo_dwconv3x3_fwd + yolo_conv2d_fwd.
+ *  Operand sizes: forms 1 (tile and strip) use 64-bit pointers and have no byte limit; form 2 addresses x with a signed 32-bit
+ *  count: from 2^31 bytes behind the x view (n * h * w * in_c_total * 2) on it returns YOLO_E_UNSUPPORTED ("... or a tensor of
+ *  2 GB"). */
 typedef struct YoloMbconvDesc {
   int32_t n, h, w, cin, in_c_total, in_c_offset, hidden, cout, out_c_total, out_c_offset, stride, has_expand, has_res, _pad;
 } YoloMbconvDesc;
