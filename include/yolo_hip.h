@@ -125,8 +125,9 @@ YOLO_API int yolo_conv2d_splitk_fwd(const void* x, const void* w_packed, const f
  *  does for the reference's nn.Conv2d + LeakyReLU), bf16 mode, STRIDE 1 (1x1 and 3x3 "same" convs): csrc/conv_bwd.hip.
  *  Every entry takes the FORWARD's descriptor d of  y = act(conv(x, bf16(W)) + bias)  and returns YOLO_E_ARG for stride != 1, ksize not
  *  in {1, 3}, pad != ksize / 2, upsample2x, a residual or pre-add view (res_* / aux_* non-zero), an act other than YOLO_ACT_NONE /
- *  YOLO_ACT_LEAKY01, or misaligned views.  Arithmetic, cg = roundup(cout, 8):
- *    g  = bf16_rne(fp32(dy) * (y > 0 ? 1 : 0.1f))  (act none: bf16_rne(dy)), bf16 NHWC [n,h,w,cg], channels cout..cg-1 zero;
+ *  YOLO_ACT_LEAKY01 / YOLO_ACT_RELU, or misaligned views.  Arithmetic, cg = roundup(cout, 8):
+ *    g  = bf16_rne(fp32(dy) * (y > 0 ? 1 : 0.1f))  (act none: bf16_rne(dy); ReLU: the factor is y > 0 ? 1 : 0), bf16 NHWC [n,h,w,cg],
+ *         channels cout..cg-1 zero;
  *    dW[co][ci][kh][kw] = sum_{n,oh,ow} g[n,oh,ow,co] * x[n,oh+kh-pad,ow+kw-pad,ci]  (taps outside the image add nothing), bf16
  *         operands, fp32 accumulation, fp32 in the parameter's OIHW layout [cout][cin][k][k];   db[co] = sum g, fp32;
  *    dx = bf16_rne(conv(g, Wt)),  Wt[ci][co][kh][kw] = bf16(W)[co][ci][k-1-kh][k-1-kw], same pad, fp32 accumulation.
@@ -281,6 +282,48 @@ YOLO_API int yolo_maxpool_bwd(const void* dy, const void* idx, void* dx, int n, 
 YOLO_API int yolo_bn_act_pool_fwd(const void* z, const float* saved, void* y, void* idx, int n, int h, int w, int c, int act, yolo_stream_t s);
 YOLO_API int yolo_concat_upsample2_fwd(const void* b, const void* a, void* y, int n, int h, int w, int cb, int ca, yolo_stream_t s);
 YOLO_API int yolo_concat_upsample2_bwd(const void* dy, void* db, void* da, int n, int h, int w, int cb, int ca, yolo_stream_t s);
+
+/* ---- the layers of a training step of YOLOv3-tiny/SqueezeNet (SqueezeNet 1.1: biased convs with ReLU, MaxPool2d(3, 2, ceil_mode=True),
+ *  the Fire module's concat; models/yolov3_tiny_squeeze.py), bf16 mode: csrc/fire_train.hip and three entries of csrc/conv_down_bwd.hip,
+ *  DESIGN.md 3.6i.  The conventions of the two blocks above: bf16, DENSE NHWC, every channel count % 8 == 0, 16-byte accesses, no atomics,
+ *  every output element written exactly once, every fp32 sum in a fixed order, no contraction; two runs give the same bits.
+ *  ReLU in the conv backward: yolo_conv2d_bwd_pick / _workspace_bytes / _prepare / _weight / _data take YOLO_ACT_RELU beside none and
+ *    LeakyReLU(0.1); yolo_conv2d_bwd_prepare then writes g = bf16_rne(fp32(dy) * (y > 0 ? 1 : 0)).  (yolo_conv2d_down_bwd_* and
+ *    yolo_bn_act_* do not.)
+ *  yolo_maxpool3s2_train_fwd: y [n,ho,wo,c] = MaxPool2d(3, 2, ceil_mode=True)(x) of x [n,h,w,c], pad 0: ho = ceil((h - 3) / 2) + 1 (= h / 2
+ *    for h >= 2), wo likewise; h >= 2 and w >= 2.  Tap 3i + j of the window at (oy, ox) is the pixel (2oy + i, 2ox + j); with pad 0 the
+ *    last window always starts inside the map, and its taps beyond the map (an even h or w) count as -inf.  idx (uint8, y's shape) is the
+ *    tap number 0..8 of the window's FIRST maximum among its in-bounds taps in row-major order: a later tap replaces the running maximum
+ *    only when strictly greater (torch's rule, yolo_maxpool_train_fwd's).  A NaN is never greater: x must hold no NaN.
+ *  yolo_maxpool3s2_bwd: dx [n,h,w,c], every element written, from dy and idx (y's shape), as a gather: pixel (py, px) can sit in the
+ *    windows oy in [ceil((py - 2) / 2), floor(py / 2)] and [0, ho), ox likewise - at most four.  acc = 0; for those windows in row-major
+ *    (oy, ox) order: acc = acc + f32(dy[q]) where idx[q] == 3 (py - 2oy) + (px - 2ox); dx = bf16_rne(acc).
+ *  yolo_fire_bwd_split: one pass over a Fire module's concat map y_cat [pixels][e1 + e3] (bf16, the forward's ReLU output) and its
+ *    gradient dy (dense, the same shape, dy_dtype YOLO_DT_BF16 | YOLO_DT_F32): g1 [pixels][e1] = bf16_rne(f32(dy[p][c]) * (y_cat[p][c] > 0
+ *    ? 1 : 0)) for c < e1, g3 [pixels][e3] the same for the other e3 channels.  Both are dense: the g operands yolo_conv2d_bwd_weight and
+ *    yolo_conv2d_bwd_data take for the expand 1x1 and expand 3x3 convs.
+ *  yolo_fire_bwd_join: g_s [pixels][sq] = bf16_rne((f32(d1) + f32(d3)) * (s_act > 0 ? 1 : 0)): d1, d3 the two expand convs' data
+ *    gradients (bf16, as yolo_conv2d_bwd_data writes them), s_act the squeeze conv's ReLU output; g_s is the squeeze conv's g operand.
+ *    Bit-equal to a bf16 add followed by yolo_conv2d_bwd_prepare (the add is an fp32 add rounded once, the factor is 0 or 1).
+ *  yolo_conv2d_stem_bwd_*: the weight and bias gradient of the unpadded first layer Conv2d(cin, cout, 3, stride=2, padding=0) with ReLU,
+ *    LeakyReLU(0.1) or no act: d is the FORWARD's descriptor (ksize 3, stride 2, pad 0, ho = (h - 3) / 2 + 1, wo likewise: an even map's
+ *    last row and column are never read; h, w >= 3; cin % 8 == cout % 8 == 0, bf16 output).  g comes from yolo_conv2d_bwd_prepare on the
+ *    stride-1 descriptor of the output map, as for the downsample.  dW[co][ci][kh][kw] = sum_{n,oh,ow} g[n,oh,ow,co] * x[n, 2 oh + kh,
+ *    2 ow + kw, ci], db[co] = sum g: yolo_conv2d_down_bwd_weight's kernel, arithmetic and split order with pad 0.  _workspace_bytes:
+ *    splits * cout * (9 cin + 1) * 4 (0 with a message for another descriptor); _pick: "wgrad<64x128,BK64,tr_b16,s2,p0> grid 1x1 splits
+ *    43", no launch, no GPU.  There is no data gradient: the layer's input is the image.
+ *  YOLO_E_ARG before any launch for an empty shape, h < 2 or w < 2 (the pool), a channel count that is no positive multiple of 8, a
+ *  dy_dtype other than bf16 / fp32, a descriptor the entry does not take, a null or misaligned pointer (the maps: 16 bytes; idx: 8);
+ *  YOLO_E_WORKSPACE for a small workspace. */
+YOLO_API int yolo_maxpool3s2_train_fwd(const void* x, void* y, void* idx, int n, int h, int w, int c, yolo_stream_t s);
+YOLO_API int yolo_maxpool3s2_bwd(const void* dy, const void* idx, void* dx, int n, int h, int w, int c, yolo_stream_t s);
+YOLO_API int yolo_fire_bwd_split(const void* dy, int dy_dtype, const void* y_cat, void* g1, void* g3, long long pixels, int e1, int e3,
+                                 yolo_stream_t s);
+YOLO_API int yolo_fire_bwd_join(const void* d1, const void* d3, const void* s_act, void* g_s, long long pixels, int sq, yolo_stream_t s);
+YOLO_API size_t yolo_conv2d_stem_bwd_workspace_bytes(const YoloConvDesc* d);
+YOLO_API int yolo_conv2d_stem_bwd_pick(const YoloConvDesc* d, char* out, int out_len);
+YOLO_API int yolo_conv2d_stem_bwd_weight(const void* x, const void* g, float* dw_oihw, float* dbias, void* workspace, size_t ws_bytes,
+                                         const YoloConvDesc* d, yolo_stream_t s);
 
 /* First layer fused with the input packing: x is the caller's f32 NCHW batch [n,cin_real,h,w] (cin_real <= 8),
  * w_packed / bias as for yolo_conv2d_fwd with d->cin = 8; 3x3 / pad 1, bf16 NHWC output: stride 1 with cout 16 or 32

@@ -101,6 +101,13 @@ SIGNATURES = {
     "yolo_bn_act_pool_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p]),
     "yolo_concat_upsample2_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
     "yolo_concat_upsample2_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "yolo_maxpool3s2_train_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    "yolo_maxpool3s2_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    "yolo_fire_bwd_split": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_longlong, C.c_int, C.c_int, C.c_void_p]),
+    "yolo_fire_bwd_join": (C.c_int, [C.c_void_p] * 4 + [C.c_longlong, C.c_int, C.c_void_p]),
+    "yolo_conv2d_stem_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(YoloConvDesc)]),
+    "yolo_conv2d_stem_bwd_pick": (C.c_int, [C.POINTER(YoloConvDesc), C.c_char_p, C.c_int]),
+    "yolo_conv2d_stem_bwd_weight": (C.c_int, [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(YoloConvDesc), C.c_void_p]),
     "yolo_pack_conv_weight_dev": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
     "yolo_conv1_nchw_f32_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(YoloConvDesc), C.c_void_p]),

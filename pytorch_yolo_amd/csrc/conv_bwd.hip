@@ -1,5 +1,6 @@
 // Backward of the stride-1 ConvBlock / plain head convolutions (reference models/yolo_base.py:19-44), bf16 mode:
-//   g  = bf16(dy * act'(y))                                  bwd_prepare_kernel, a 16-byte-per-lane stream
+//   g  = bf16(dy * act'(y))                                  bwd_prepare_kernel, a 16-byte-per-lane stream; act' = 1 (none), y > 0 ? 1 : 0.1
+//                                                            (LeakyReLU(0.1)) or y > 0 ? 1 : 0 (ReLU: SqueezeNet's convs)
 //   dW = sum over pixels of g[p][co] * x[p + tap][ci], db    wgrad_kernel (conv_wgrad.h: MFMA, split over the pixels) + wgrad_reduce_kernel
 //   dx = conv(g, flipped transposed W)                       the FORWARD dispatcher on a pack of pack_weight_kernel
 // No atomics and no read-modify-write: every element of g, dW, db and of the used workspace is written once per call, in an order
@@ -11,9 +12,10 @@ namespace {
 // ---- g = bf16(dy * slope(y)) -----------------------------------------------------------------------------------------
 // One thread owns 8 consecutive channels of one pixel of g (16 bytes).  dy is dense [pixels][cout]; y is the forward's output view.
 // VEC: cout, the view of y and both bases allow whole 8-channel loads; otherwise element loads (a 255-channel head).
+// leaky: the act looks at y; low: its slope where y <= 0 (0.1f LeakyReLU(0.1), 0.f ReLU).
 template <typename TDY, typename TY, bool VEC>
 __global__ __launch_bounds__(256) void bwd_prepare_kernel(const TDY* __restrict__ dy, const TY* __restrict__ y, bf16_t* __restrict__ g,
-                                                          long pixels, int cout, int cg, int y_total, int y_offset, int leaky) {
+                                                          long pixels, int cout, int cg, int y_total, int y_offset, int leaky, float low) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   const int groups = cg / 8;
   if (idx >= pixels * groups) return;
@@ -43,7 +45,7 @@ __global__ __launch_bounds__(256) void bwd_prepare_kernel(const TDY* __restrict_
   bf16x8 out;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const float slope = (leaky && !(yv[j] > 0.f)) ? 0.1f : 1.f;      // torch's leaky_relu backward: the slope at y == 0
+    const float slope = (leaky && !(yv[j] > 0.f)) ? low : 1.f;       // torch's leaky_relu / relu backward: the low slope at y == 0
     out[j] = c0 + j < cout ? (bf16_t)(dv[j] * slope) : (bf16_t)0.f;
   }
   *reinterpret_cast<bf16x8*>(g + p * cg + c0) = out;
@@ -78,7 +80,7 @@ int bwd_check(const YoloConvDesc* dp, const char* fn) {
   YOLO_REQUIRE(d.out_dtype == YOLO_DT_BF16 || d.out_dtype == YOLO_DT_F32, "%s: out_dtype %d", fn, d.out_dtype);
   YOLO_REQUIRE(d.out_c_offset >= 0 && (long)d.out_c_offset + d.cout <= d.out_c_total, "%s: bad output view (cout %d, offset %d, total %d)", fn,
                d.cout, d.out_c_offset, d.out_c_total);
-  return bwd_check_shared(d, fn);
+  return bwd_check_shared(d, fn, true);
 }
 
 constexpr int kZeroBias = 8192;
@@ -108,13 +110,14 @@ static int launch_prepare(const void* dy, const void* y, void* g, const YoloConv
   YOLO_REQUIRE(total < kMaxThreads, "conv2d_bwd_prepare: too many elements");
   const bool vec = d.cout % 8 == 0 && d.out_c_total % 8 == 0 && d.out_c_offset % 8 == 0 && (uintptr_t)dy % (8 * sizeof(TDY)) == 0 &&
                    (uintptr_t)y % (8 * sizeof(TY)) == 0;
-  const int leaky = d.act == YOLO_ACT_LEAKY01;
+  const int leaky = d.act != YOLO_ACT_NONE;
+  const float low = d.act == YOLO_ACT_RELU ? 0.f : 0.1f;
   if (vec)
     hipLaunchKernelGGL((bwd_prepare_kernel<TDY, TY, true>), dim3(blocks_for(total)), dim3(256), 0, s, (const TDY*)dy, (const TY*)y,
-                       (bf16_t*)g, pixels, d.cout, cg, d.out_c_total, d.out_c_offset, leaky);
+                       (bf16_t*)g, pixels, d.cout, cg, d.out_c_total, d.out_c_offset, leaky, low);
   else
     hipLaunchKernelGGL((bwd_prepare_kernel<TDY, TY, false>), dim3(blocks_for(total)), dim3(256), 0, s, (const TDY*)dy, (const TY*)y,
-                       (bf16_t*)g, pixels, d.cout, cg, d.out_c_total, d.out_c_offset, leaky);
+                       (bf16_t*)g, pixels, d.cout, cg, d.out_c_total, d.out_c_offset, leaky, low);
   return yolo_check_launch("conv2d_bwd_prepare");
 }
 

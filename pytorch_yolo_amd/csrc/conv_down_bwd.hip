@@ -5,6 +5,8 @@
 //   dx[n,ih,iw][ci] = bf16(sum over co and the taps with ih + 1 - kh = 2 oh, iw + 1 - kw = 2 ow)        dgrad_parity_kernel
 //   the dgrad operand [kh][kw][ci][co] bf16                                                             pack_weight_down_kernel
 // No atomics and no read-modify-write: every element of dW, db, dx (its view) and of the used workspace is written once per call.
+// The unpadded stride-2 first layer of SqueezeNet 1.1 (Conv2d(3, 64, 3, stride=2)) has the same weight gradient with pad 0
+// - wgrad_kernel<MI, 2> takes the pad as an argument - behind the yolo_conv2d_stem_bwd_* entries; its input is the image: no data gradient.
 #include "conv_wgrad.h"
 
 namespace {
@@ -191,7 +193,7 @@ int down_check(const YoloConvDesc* dp, const char* fn) {
   YOLO_REQUIRE(d.out_dtype == YOLO_DT_BF16, "%s: out_dtype %d unsupported (a bf16 output)", fn, d.out_dtype);
   YOLO_REQUIRE(d.cout % 8 == 0 && d.out_c_offset >= 0 && (long)d.out_c_offset + d.cout <= d.out_c_total,
                "%s: bad output view (cout %d: a multiple of 8, offset %d, total %d)", fn, d.cout, d.out_c_offset, d.out_c_total);
-  return bwd_check_shared(d, fn);
+  return bwd_check_shared(d, fn, false);
 }
 
 // choose_wgrad as it is, on the OUTPUT pixels
@@ -199,6 +201,21 @@ WgradPick choose_down_wgrad(const YoloConvDesc& d) {
   YoloConvDesc t = d;
   t.h = d.ho, t.w = d.wo;
   return choose_wgrad(t, yolo_conv::launch_cus());
+}
+
+// the unpadded first layer: 3x3, stride 2, pad 0, ho = (h - 3) / 2 + 1 (an even map's last row and column are never read)
+int stem_check(const YoloConvDesc* dp, const char* fn) {
+  YOLO_REQUIRE(dp, "%s: null descriptor", fn);
+  const YoloConvDesc& d = *dp;
+  YOLO_REQUIRE(d.ksize == 3 && d.stride == 2, "%s: ksize %d / stride %d unsupported (the unpadded first layer is 3x3 at stride 2)", fn, d.ksize,
+               d.stride);
+  YOLO_REQUIRE(d.h >= 3 && d.w >= 3, "%s: a %d x %d map has no unpadded 3x3 window", fn, d.h, d.w);
+  YOLO_REQUIRE(d.pad == 0 && d.ho == (d.h - 3) / 2 + 1 && d.wo == (d.w - 3) / 2 + 1,
+               "%s: pad %d / output %dx%d: pad 0 and the output size (h - 3) / 2 + 1 only (pad 1 is yolo_conv2d_down_bwd_*)", fn, d.pad, d.ho, d.wo);
+  YOLO_REQUIRE(d.out_dtype == YOLO_DT_BF16, "%s: out_dtype %d unsupported (a bf16 output)", fn, d.out_dtype);
+  YOLO_REQUIRE(d.cout % 8 == 0 && d.out_c_offset >= 0 && (long)d.out_c_offset + d.cout <= d.out_c_total,
+               "%s: bad output view (cout %d: a multiple of 8, offset %d, total %d)", fn, d.cout, d.out_c_offset, d.out_c_total);
+  return bwd_check_shared(d, fn, true);
 }
 
 struct DgradPick {
@@ -252,6 +269,34 @@ extern "C" int yolo_conv2d_down_bwd_weight(const void* x, const void* g, float* 
   const size_t need = wgrad_ws_bytes(d, k.splits);
   if (ws_bytes < need) return yolo_set_error(YOLO_E_WORKSPACE, "conv2d_down_bwd_weight: workspace %zu < %zu bytes", ws_bytes, need);
   return launch_wgrad<2>(x, g, dw_oihw, dbias, workspace, d, k, (hipStream_t)s, "conv2d_down_bwd_weight");
+}
+
+// ---- the unpadded first layer: the same two launches with pad 0 ----------------------------------------------------------------------
+extern "C" size_t yolo_conv2d_stem_bwd_workspace_bytes(const YoloConvDesc* d) {
+  if (stem_check(d, "conv2d_stem_bwd_workspace_bytes")) return 0;
+  return wgrad_ws_bytes(*d, choose_down_wgrad(*d).splits);
+}
+
+extern "C" int yolo_conv2d_stem_bwd_pick(const YoloConvDesc* d, char* out, int out_len) {
+  YOLO_REQUIRE(out && out_len > 0, "conv2d_stem_bwd_pick: bad arguments");
+  out[0] = 0;
+  if (const int rc = stem_check(d, "conv2d_stem_bwd_pick")) return rc;
+  const WgradPick k = choose_down_wgrad(*d);
+  snprintf(out, (size_t)out_len, "wgrad<%dx%d,BK%d,tr_b16,s2,p0> grid %dx%d splits %d", 64 * k.mi, kTN, kBK, k.tiles_n, k.tiles_m, k.splits);
+  return 0;
+}
+
+extern "C" int yolo_conv2d_stem_bwd_weight(const void* x, const void* g, float* dw_oihw, float* dbias, void* workspace, size_t ws_bytes,
+                                           const YoloConvDesc* dp, yolo_stream_t s) {
+  if (const int rc = stem_check(dp, "conv2d_stem_bwd_weight")) return rc;
+  const YoloConvDesc& d = *dp;
+  YOLO_REQUIRE(x && g && dw_oihw && workspace, "conv2d_stem_bwd_weight: null pointer");
+  YOLO_REQUIRE((uintptr_t)x % 16 == 0 && (uintptr_t)g % 16 == 0 && (uintptr_t)workspace % 16 == 0 && (uintptr_t)dw_oihw % 4 == 0,
+               "conv2d_stem_bwd_weight: misaligned pointer");
+  const WgradPick k = choose_down_wgrad(d);
+  const size_t need = wgrad_ws_bytes(d, k.splits);
+  if (ws_bytes < need) return yolo_set_error(YOLO_E_WORKSPACE, "conv2d_stem_bwd_weight: workspace %zu < %zu bytes", ws_bytes, need);
+  return launch_wgrad<2>(x, g, dw_oihw, dbias, workspace, d, k, (hipStream_t)s, "conv2d_stem_bwd_weight");
 }
 
 extern "C" int yolo_conv2d_down_bwd_data(const void* g, const void* w_packed_d, void* dx, const YoloConvDesc* dp, yolo_stream_t s) {

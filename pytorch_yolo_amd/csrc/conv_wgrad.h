@@ -273,12 +273,13 @@ WgradPick choose_wgrad(const YoloConvDesc& d, int n_cu) {
 int roundup_i(int v, int m) { return (v + m - 1) / m * m; }
 
 // what the backward entries of both strides ask of the forward's descriptor beside their own geometry: no epilogue the backward does
-// not have, act none or LeakyReLU(0.1), a non-empty shape in range, an input view on 8-channel groups
-int bwd_check_shared(const YoloConvDesc& d, const char* fn) {
+// not have, act none or LeakyReLU(0.1) (``relu_ok``: or ReLU), a non-empty shape in range, an input view on 8-channel groups
+int bwd_check_shared(const YoloConvDesc& d, const char* fn, bool relu_ok) {
   YOLO_REQUIRE(!d.upsample2x, "%s: no backward of the upsampling store", fn);
   YOLO_REQUIRE(d.res_c_total == 0 && d.res_c_offset == 0 && d.aux_c_total == 0 && d.aux_c_offset == 0,
                "%s: no backward of the residual / pre-add epilogues", fn);
-  YOLO_REQUIRE(d.act == YOLO_ACT_NONE || d.act == YOLO_ACT_LEAKY01, "%s: act %d unsupported (none or LeakyReLU(0.1))", fn, d.act);
+  YOLO_REQUIRE(d.act == YOLO_ACT_NONE || d.act == YOLO_ACT_LEAKY01 || (relu_ok && d.act == YOLO_ACT_RELU), "%s: act %d unsupported (none%s)", fn,
+               d.act, relu_ok ? ", LeakyReLU(0.1) or ReLU" : " or LeakyReLU(0.1)");
   YOLO_REQUIRE(d.n > 0 && d.h > 0 && d.w > 0 && d.cout > 0, "%s: empty shape", fn);
   YOLO_REQUIRE(d.cin > 0 && d.cin % 8 == 0 && yolo_view_ok(d.cin, d.in_c_total, d.in_c_offset, 8),
                "%s: bad input view (cin %d, offset %d, total %d: multiples of 8)", fn, d.cin, d.in_c_offset, d.in_c_total);

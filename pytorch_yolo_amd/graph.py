@@ -116,6 +116,29 @@ class Recorder:
         up = self.upsample2(a)
         return self.concat([up, b] if up_first else [b, up])
 
+    # SqueezeNet 1.1's two layers (models/yolov3_tiny_squeeze.py); with maxpool(3, 2, pad=0, ceil_mode=True) and concat they are what
+    # models/train.FireTracer adds to the trainable vocabulary.
+    def stem_conv(self, conv, x: Sym):
+        """features[0]: a biased ``nn.Conv2d(cin, cout, 3, stride=2)`` WITHOUT padding, the ReLU that follows folded in."""
+        return self.conv(x, (conv.weight.detach().float().cpu(), conv.bias.detach().float().cpu()), stride=2, act="relu", pad=0)
+
+    def fire(self, fire, x: Sym):
+        """A Fire module: squeeze 1x1 + ReLU -> cat(expand 1x1 + ReLU, expand 3x3 (pad 1) + ReLU).  The squeeze tensor (16 / 32 / 48 / 64
+        channels) is kept in a multiple of 32 physical channels (zero weight rows and biases, zero input columns in the expand convs):
+        the expand convs then take the LDS-DMA fast path."""
+        pad = torch.nn.functional.pad
+
+        def wb(conv):
+            return conv.weight.detach().float().cpu(), conv.bias.detach().float().cpu()
+        sq, sp = fire.squeeze.out_channels, -(-fire.squeeze.out_channels // 32) * 32
+        w, b = wb(fire.squeeze)
+        s = self.conv(x, (pad(w, (0, 0, 0, 0, 0, 0, 0, sp - sq)), pad(b, (0, sp - sq))), act="relu")
+
+        def widen(conv):
+            w_, b_ = wb(conv)
+            return pad(w_, (0, 0, 0, 0, 0, sp - sq)), b_
+        return self.concat([self.conv(s, widen(fire.expand1x1), act="relu"), self.conv(s, widen(fire.expand3x3), act="relu")])
+
     def dwconv(self, x: Sym, weight, stride=1, act="relu6", tf_same=False):
         """Depthwise k x k conv.  Default: 3x3 / pad 1 (MobileNetV2).  ``tf_same``: k = 3 or 5 with TensorFlow "same" padding
         (EfficientNet-B0's MBConvBlock._depthwise_conv) - the general kernel, which also takes the swish activation."""

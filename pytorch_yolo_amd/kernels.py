@@ -20,7 +20,9 @@ __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pic
            "conv2d_down_bwd_workspace_bytes", "conv2d_down_bwd_pick", "conv2d_down_bwd_weight", "conv2d_down_bwd_data", "pack_conv_weight_down_dev",
            "bn_workspace_bytes", "bn_pick", "bn_train_stats", "bn_eval_stats", "bn_act_fwd", "bn_act_bwd",
            "bn_act_add_fwd", "spp_train_fwd", "spp_bwd", "upsample2_concat_fwd", "upsample2_concat_bwd",
-           "maxpool_train_fwd", "maxpool_bwd", "bn_act_pool_fwd", "concat_upsample2_fwd", "concat_upsample2_bwd"]
+           "maxpool_train_fwd", "maxpool_bwd", "bn_act_pool_fwd", "concat_upsample2_fwd", "concat_upsample2_bwd",
+           "maxpool3s2_train_fwd", "maxpool3s2_bwd", "fire_bwd_split", "fire_bwd_join",
+           "conv2d_stem_bwd_workspace_bytes", "conv2d_stem_bwd_pick", "conv2d_stem_bwd_weight"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -662,6 +664,95 @@ def concat_upsample2_bwd(dy, db, da, *, n, h, w, cb, ca):
         _nhwc(db, (n, 2 * h, 2 * w, cb), "concat_upsample2_bwd: db")
     check(load().yolo_concat_upsample2_bwd(_ptr(dy), _ptr(db), _ptr(da), n, h, w, cb, ca, stream_ptr()), "concat_upsample2_bwd")
     return db, da
+
+
+# ---- the layers of a training step of YOLOv3-tiny/SqueezeNet (csrc/fire_train.hip, three entries of csrc/conv_down_bwd.hip; DESIGN.md
+# 3.6i) ---------------------------------------------------------------------------------------------------------------------------------
+def maxpool3s2_train_fwd(x, y, idx):
+    """y [n,h//2,w//2,c] = MaxPool2d(3, 2, ceil_mode=True)(x) of the dense bf16 x [n,h,w,c] (h, w >= 2; ceil((h - 3) / 2) + 1 = h // 2);
+    idx uint8 of y's shape: the tap 3i + j (0..8) of each window's first maximum among its in-bounds taps."""
+    _need_cuda(x, y, idx)
+    if x.dim() != 4:
+        raise RuntimeError("maxpool3s2_train_fwd: x must be [n, h, w, c]")
+    n, h, w, c = x.shape
+    _nhwc(x, (n, h, w, c), "maxpool3s2_train_fwd: x")
+    _nhwc(y, (n, h // 2, w // 2, c), "maxpool3s2_train_fwd: y")
+    _nhwc(idx, (n, h // 2, w // 2, c), "maxpool3s2_train_fwd: idx", torch.uint8)
+    check(load().yolo_maxpool3s2_train_fwd(_ptr(x), _ptr(y), _ptr(idx), n, h, w, c, stream_ptr()), "maxpool3s2_train_fwd")
+    return y, idx
+
+
+def maxpool3s2_bwd(dy, idx, dx):
+    """dx [n,h,w,c] (every element written) from dy and maxpool3s2_train_fwd's idx: a gather of up to four terms with a fixed fp32
+    summation order, rounded once."""
+    _need_cuda(dy, idx, dx)
+    if dx.dim() != 4:
+        raise RuntimeError("maxpool3s2_bwd: dx must be [n, h, w, c]")
+    n, h, w, c = dx.shape
+    _nhwc(dx, (n, h, w, c), "maxpool3s2_bwd: dx")
+    _nhwc(dy, (n, h // 2, w // 2, c), "maxpool3s2_bwd: dy")
+    _nhwc(idx, (n, h // 2, w // 2, c), "maxpool3s2_bwd: idx", torch.uint8)
+    check(load().yolo_maxpool3s2_bwd(_ptr(dy), _ptr(idx), _ptr(dx), n, h, w, c, stream_ptr()), "maxpool3s2_bwd")
+    return dx
+
+
+def fire_bwd_split(dy, y_cat, g1, g3):
+    """g1 [..., e1] | g3 [..., e3] = bf16(dy * (y_cat > 0)) split at channel e1: ``dy`` (bf16 or f32) and ``y_cat`` (bf16) dense
+    [..., e1 + e3], the outputs dense bf16 - every element written."""
+    _need_cuda(dy, y_cat, g1, g3)
+    e1, e3 = g1.shape[-1], g3.shape[-1]
+    pixels = y_cat.numel() // (e1 + e3)
+    _bn_map(y_cat, pixels, e1 + e3, "fire_bwd_split: y_cat")
+    _bn_map(dy, pixels, e1 + e3, "fire_bwd_split: dy", (torch.bfloat16, torch.float32))
+    _bn_map(g1, pixels, e1, "fire_bwd_split: g1")
+    _bn_map(g3, pixels, e3, "fire_bwd_split: g3")
+    check(load().yolo_fire_bwd_split(_ptr(dy), _dt_of(dy, "dy"), _ptr(y_cat), _ptr(g1), _ptr(g3), pixels, e1, e3, stream_ptr()), "fire_bwd_split")
+    return g1, g3
+
+
+def fire_bwd_join(d1, d3, s_act, g_s):
+    """g_s = bf16((f32(d1) + f32(d3)) * (s_act > 0)) on dense bf16 [..., sq] maps - every element written."""
+    _need_cuda(d1, d3, s_act, g_s)
+    sq = s_act.shape[-1]
+    pixels = s_act.numel() // sq
+    for t, what in ((d1, "d1"), (d3, "d3"), (s_act, "s_act"), (g_s, "g_s")):
+        _bn_map(t, pixels, sq, f"fire_bwd_join: {what}")
+    check(load().yolo_fire_bwd_join(_ptr(d1), _ptr(d3), _ptr(s_act), _ptr(g_s), pixels, sq, stream_ptr()), "fire_bwd_join")
+    return g_s
+
+
+def conv2d_stem_bwd_workspace_bytes(desc: YoloConvDesc) -> int:
+    """Bytes of caller-owned workspace yolo_conv2d_stem_bwd_weight needs for the forward's stride-2 pad-0 ``desc`` (no launch, works
+    without a GPU)."""
+    n = load().yolo_conv2d_stem_bwd_workspace_bytes(C.byref(desc))
+    if n == 0:
+        check(-1, "conv2d_stem_bwd_workspace_bytes")
+    return int(n)
+
+
+def conv2d_stem_bwd_pick(desc: YoloConvDesc) -> str:
+    """Tile, grid and split count of the weight-gradient launch for the forward's stride-2 pad-0 ``desc`` (no launch, works without a
+    GPU)."""
+    buf = C.create_string_buffer(256)
+    check(load().yolo_conv2d_stem_bwd_pick(C.byref(desc), buf, 256), "conv2d_stem_bwd_pick")
+    return buf.value.decode()
+
+
+def conv2d_stem_bwd_weight(x, g, dw, dbias, workspace, desc: YoloConvDesc):
+    """dW (f32 OIHW [cout,cin,3,3]) and, unless ``dbias`` is None, db (f32 [cout]) of the unpadded stride-2 forward ``desc``; ``g`` dense
+    bf16 [n,ho,wo,cout]; ``workspace``: a tensor of at least conv2d_stem_bwd_workspace_bytes(desc) bytes whose content does not matter."""
+    _need_cuda(x, g, dw, dbias, workspace)
+    if dw.dtype != torch.float32 or not dw.is_contiguous() or tuple(dw.shape) != (desc.cout, desc.cin, desc.ksize, desc.ksize):
+        raise RuntimeError("conv2d_stem_bwd_weight: dw must be contiguous float32 [cout,cin,3,3]")
+    if dbias is not None and (dbias.dtype != torch.float32 or not dbias.is_contiguous() or dbias.numel() != desc.cout):
+        raise RuntimeError("conv2d_stem_bwd_weight: dbias must be contiguous float32 [cout]")
+    if g.dtype != torch.bfloat16 or not g.is_contiguous() or g.numel() != desc.n * desc.ho * desc.wo * desc.cout:
+        raise RuntimeError("conv2d_stem_bwd_weight: g must be contiguous bf16 [n,ho,wo,cout]")
+    if x.dtype != torch.bfloat16 or x.numel() != desc.n * desc.h * desc.w * desc.in_c_total:
+        raise RuntimeError("conv2d_stem_bwd_weight: x must be the dense bf16 [n,h,w,in_c_total] map")
+    check(load().yolo_conv2d_stem_bwd_weight(_ptr(x), _ptr(g), _ptr(dw), _ptr(dbias), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                             C.byref(desc), stream_ptr()), "conv2d_stem_bwd_weight")
+    return dw, dbias
 
 
 def conv2d_splitk_plan(desc: YoloConvDesc, has_residual=False, has_preadd=False):

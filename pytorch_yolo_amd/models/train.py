@@ -1,6 +1,6 @@
-"""Training-mode forward of the Darknet-53 models (YOLOv3, YOLOv3-SPP) and of the max-pool models (YOLOv3-tiny, LiteYOLOv3): the
-reference's ``model.train()(x)`` - batch-statistics BN, the raw ``p`` list with a ``grad_fn`` - wired from the differentiable ops of
-pytorch_yolo_amd.ops.
+"""Training-mode forward of the Darknet-53 models (YOLOv3, YOLOv3-SPP), of the max-pool models (YOLOv3-tiny, LiteYOLOv3) and of
+YOLOv3-tiny/SqueezeNet: the reference's ``model.train()(x)`` - batch-statistics BN, the raw ``p`` list with a ``grad_fn`` - wired from the
+differentiable ops of pytorch_yolo_amd.ops.
 
 A model states its layer graph once, in ``_trace``.  For inference graph.Recorder records it; for training ``wiring`` (every trainable
 class's ``_train_wiring``) runs the same ``_trace`` through a ``TrainTracer``, which has the Recorder's method names and runs each call at
@@ -8,9 +8,11 @@ once on tensors.  The tracer takes every op from a table, a namespace of functio
 tests run the same wiring on the CPU with float64 torch restatements of the ops, which is how it is compared with the reference without a
 GPU.  A table function has the signature of the op it stands for.  ``DEVICE_OPS`` holds the six functions the Darknet-53 models use;
 ``DEVICE_OPS_POOL`` adds ``max_pool`` and ``pool_bn_block`` and is the table ``forward_train`` runs by default (the ``up_first`` keyword
-of ``upsample_concat`` goes through both).
+of ``upsample_concat`` goes through both).  ``DEVICE_OPS_FIRE`` adds ``stem_block``, ``fire_block``, ``max_pool_ceil`` and a ``concat``:
+the table of YOLOv3-tiny/SqueezeNet, whose ``_trace`` runs through ``FireTracer`` - a model names its tracer class in ``_train_tracer``
+and its default table in ``_train_ops``.
 
-``forward_train(model, x)`` is the public entry for all four classes.  ``model.train()(x)`` delegates to it for the classes whose
+``forward_train(model, x)`` is the public entry for all five classes.  ``model.train()(x)`` delegates to it for the classes whose
 ``_train_in_forward`` is True (YOLOv3, YOLOv3-SPP); YOLOv3-tiny and LiteYOLOv3 keep raising from the module call and train through the
 function (DESIGN.md 3.6g says why: flipping their switch is a one-line change).
 """
@@ -27,6 +29,16 @@ from .yolo_base import ConvPoolBlock
 DEVICE_OPS = SimpleNamespace(conv_block=_ops.conv_block, conv_bn_block=_ops.conv_bn_block, down_bn_block=_ops.down_bn_block,
                              res_bn_block=_ops.res_bn_block, spp_concat=_ops.spp_concat, upsample_concat=_ops.upsample_concat)
 DEVICE_OPS_POOL = SimpleNamespace(**vars(DEVICE_OPS), max_pool=_ops.max_pool, pool_bn_block=_ops.pool_bn_block)
+
+
+def _concat(xs):
+    """cat of same-grid maps on the channels (YOLOv3-tiny/SqueezeNet's head concat [route1, b1]): torch's copy on channels-last bf16;
+    autograd slices the gradient back."""
+    return torch.cat(list(xs), 1)
+
+
+DEVICE_OPS_FIRE = SimpleNamespace(**vars(DEVICE_OPS_POOL), stem_block=_ops.stem_block, fire_block=_ops.fire_block,
+                                  max_pool_ceil=_ops.max_pool_ceil, concat=_concat)
 
 
 def conv_bn(ops, block, x, residual=None, want_preadd=False):
@@ -93,9 +105,34 @@ class TrainTracer:
         self.branches.append(x)
 
 
+class FireTracer(TrainTracer):
+    """TrainTracer plus what YOLOv3-tiny/SqueezeNet's ``_trace`` calls: graph.Recorder's ``stem_conv``, ``fire`` and ``concat``, and its
+    ``maxpool`` with the geometry of MaxPool2d(3, 2, ceil_mode=True).  The ops take the modules' own parameters, so a gradient reaches
+    them (the Recorder's side of the same methods packs detached copies)."""
+
+    def stem_conv(self, conv, x):
+        return self.ops.stem_block(x, conv.weight, conv.bias, act="relu")
+
+    def fire(self, fire, x):
+        return self.ops.fire_block(x, fire.squeeze.weight, fire.squeeze.bias, fire.expand1x1.weight, fire.expand1x1.bias,
+                                   fire.expand3x3.weight, fire.expand3x3.bias)
+
+    def maxpool(self, x, size, stride, pad=None, ceil_mode=False):
+        if (size, stride, pad, ceil_mode) == (3, 2, 0, True):
+            return self.ops.max_pool_ceil(x)
+        if pad is not None or ceil_mode:
+            raise NotImplementedError(f"the training-mode forward has no max-pool of size {size} / stride {stride} with pad {pad}, "
+                                      f"ceil_mode {ceil_mode} (3 / 2 / 0 / True only)")
+        return super().maxpool(x, size, stride)
+
+    def concat(self, xs):
+        return self.ops.concat(xs)
+
+
 def wiring(model, ops, x):
-    """``model._train_wiring``: the raw head maps [bs, 3 (5 + nc), ny, nx] of ``model._trace`` run on the ops of a table."""
-    g = TrainTracer(ops, model.yolo_layers)
+    """``model._train_wiring``: the raw head maps [bs, 3 (5 + nc), ny, nx] of ``model._trace`` run on the ops of a table, through the
+    tracer class the model names (``_train_tracer``; TrainTracer without one)."""
+    g = getattr(model, "_train_tracer", TrainTracer)(ops, model.yolo_layers)
     model._trace(g, x)
     return tuple(g.branches)
 
@@ -127,7 +164,7 @@ def forward_train(model, x, ops=None):
         if not x.is_cuda:
             raise RuntimeError("pytorch_yolo_amd runs on a ROCm device only: move the input to cuda "
                                "(there is no CPU fallback)")
-        ops = DEVICE_OPS_POOL
+        ops = getattr(model, "_train_ops", DEVICE_OPS_POOL)
     branches = model._train_wiring(ops, x)
     img_size = max(x.shape[-2:])
     out = []

@@ -10,23 +10,19 @@ weights with ``load_state_dict``.  The split four modules from the end (``route_
 """
 from __future__ import annotations
 
-import torch
 from torch import nn
 
 from .. import engine
+from . import train as T
 from .yolo_base import ConvBlock, YOLOBase
 from .yolo_layer import Concat
-
-
-def _wb(conv: nn.Conv2d):
-    return conv.weight.detach().float().cpu(), conv.bias.detach().float().cpu()
 
 
 class _ConvReLU0(nn.Conv2d):
     """features[0]: Conv2d(in, 64, kernel_size=3, stride=2), NO padding; the ReLU that follows is folded in."""
 
     def _trace(self, g, x):
-        return g.conv(x, _wb(self), stride=2, act="relu", pad=0)
+        return g.stem_conv(self, x)
 
 
 class _ReLU(nn.ReLU):
@@ -54,16 +50,7 @@ class Fire(nn.Module):
         self.expand3x3_activation = nn.ReLU(inplace=True)
 
     def _trace(self, g, x):
-        # the squeeze tensor (16 / 32 / 48 / 64 channels) is kept in a multiple of 32 physical channels (zero weight rows
-        # and biases, zero input columns in the expand convs): the expand convs then take the LDS-DMA fast path
-        sq, sp = self.squeeze.out_channels, -(-self.squeeze.out_channels // 32) * 32
-        w, b = _wb(self.squeeze)
-        s = g.conv(x, (torch.nn.functional.pad(w, (0, 0, 0, 0, 0, 0, 0, sp - sq)), torch.nn.functional.pad(b, (0, sp - sq))), act="relu")
-
-        def widen(conv):
-            w_, b_ = _wb(conv)
-            return torch.nn.functional.pad(w_, (0, 0, 0, 0, 0, sp - sq)), b_
-        return g.concat([g.conv(s, widen(self.expand1x1), act="relu"), g.conv(s, widen(self.expand3x3), act="relu")])
+        return g.fire(self, x)      # (graph.Recorder.fire pads the squeeze tensor to 32 physical channels; training runs ops.fire_block)
 
 
 def _squeezenet1_1_features(in_channels):
@@ -126,6 +113,12 @@ class YOLOv3TinySqueeze(YOLOBase):
     @property
     def yolo_layers(self):
         return self.yolo1, self.yolo2
+
+    # training goes through pytorch_yolo_amd.forward_train(model, x), as for YOLOv3-tiny and LiteYOLOv3
+    _train_in_forward = False
+    _train_tracer = T.FireTracer      # stem_conv, fire, concat and the ceil-mode pool beside TrainTracer's vocabulary
+    _train_ops = T.DEVICE_OPS_FIRE
+    _train_wiring = T.wiring          # training runs the same _trace on the ops of a table (models/train.py)
 
     def _trace(self, g: engine.Recorder, x):
         """Reference _forward_encoder + forward (yolov3_tiny_squeeze.py:71-104)."""

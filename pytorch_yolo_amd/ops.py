@@ -7,11 +7,13 @@ The ops (contracts in their docstrings; the kernels in DESIGN.md 3.6c-g):
     res_bn_block                    the closing ConvBlock of a residual unit with its add
     pool_bn_block, max_pool         ConvPoolBlock and MaxPool of YOLOv3-tiny / LiteYOLOv3
     spp_concat, upsample_concat     the SPP pyramid, the FPN's upsample + concat
+    stem_block, fire_block, max_pool_ceil   SqueezeNet 1.1's unpadded stride-2 first layer, Fire module and MaxPool2d(3, 2, ceil_mode=True)
+                                    (DESIGN.md 3.6i); ``conv_block(act="relu")`` is its plain conv
 models/train.py wires the training-mode forward of the models from them; the models' eval forward stays inference-only.
 
 The structure - every launch has one owner:
-    _forward        pack the weight, yolo_conv2d_fwd: the launch the models use, at either stride
-    _conv_grads     the conv's weight / bias and data gradients on g, each only where asked; dispatches on the descriptor's stride
+    _forward        pack the weight, yolo_conv2d_fwd: the launch the models use, at either stride; ``into``: a channel view of a wider buffer
+    _conv_grads     the conv's weight / bias and data gradients on g, each only where asked; dispatches on the descriptor's stride and pad
                     (csrc/conv_bwd.hip, csrc/conv_down_bwd.hip) and is the only caller of those bindings
     _conv_stats     conv with act none, then the batch statistics: the only caller of bn_train_stats
     _bn_forward     _conv_stats and the tail: bn_act_fwd, bn_act_pool_fwd (pool stride 2) or bn_act_fwd + the stride-1 pool
@@ -21,6 +23,9 @@ The structure - every launch has one owner:
     _ConvBnFunction(stride, pool_stride)  conv_bn_block, down_bn_block, pool_bn_block:  _bn_forward / [_pool_backward,] _bn_grads, _conv_grads
     _ResBnBlockFunction                 res_bn_block:  _conv_stats, bn_act_add_fwd / _bn_grads, _conv_grads; dy passes through to the residual
     _SppConcatFunction, _UpsampleConcatFunction, _MaxPoolFunction   the glue ops (csrc/route.hip, csrc/pool_train.hip)
+    _FireFunction                       fire_block:  three _forward (the expands into one buffer) / fire_bwd_split, _conv_grads twice,
+                                        fire_bwd_join, _conv_grads
+    _MaxPoolCeilFunction                max_pool_ceil (csrc/fire_train.hip)
     _check_conv, _check_bn, _need_device    the argument checks: every ValueError, then the RuntimeError, then the first allocation
     _apply          Function.apply where a gradient can be asked for, the plain forward on detached inputs otherwise
 tests/test_ops_trace_gpu.py pins every op's launch list (tests/golden/ops_trace.json).
@@ -30,48 +35,59 @@ from __future__ import annotations
 import torch
 
 from . import kernels as K
-from ._lib import ACT_LEAKY01, ACT_NONE, DT_BF16, DT_F32
+from ._lib import ACT_LEAKY01, ACT_NONE, ACT_RELU, DT_BF16, DT_F32
 
 __all__ = ["conv_block", "conv_bn_block", "down_block", "down_bn_block", "res_bn_block", "spp_concat", "upsample_concat", "max_pool",
-           "pool_bn_block"]
+           "pool_bn_block", "stem_block", "fire_block", "max_pool_ceil"]
 
 _ACTS = {"leaky": ACT_LEAKY01, "none": ACT_NONE}
+_ACTS_RELU = {**_ACTS, "relu": ACT_RELU}          # the ops without a batch norm at stride 1, and the unpadded first layer
 
 
 # ---- the launches and their owners -------------------------------------------------------------------------------------------------------
-def _desc(x, weight, act_id, out_f32, stride=1):
+def _desc(x, weight, act_id, out_f32, stride=1, pad=None, view=None):
     n, c, h, w = x.shape
     cout, _, k, _ = weight.shape
-    ct = K.roundup(cout, 4) if out_f32 else cout
-    return K.conv_desc(n=n, h=h, w=w, cin=c, in_c_total=c, in_c_offset=0, cout=cout, out_c_total=ct, out_c_offset=0, ksize=k, stride=stride,
-                       act=act_id, kpad=K.roundup(k * k * c, 64), cout_pad=K.roundup(cout, 128), out_dtype=DT_F32 if out_f32 else DT_BF16)
+    ct, off = view if view is not None else (K.roundup(cout, 4) if out_f32 else cout, 0)
+    return K.conv_desc(n=n, h=h, w=w, cin=c, in_c_total=c, in_c_offset=0, cout=cout, out_c_total=ct, out_c_offset=off, ksize=k, stride=stride,
+                       act=act_id, kpad=K.roundup(k * k * c, 64), cout_pad=K.roundup(cout, 128), out_dtype=DT_F32 if out_f32 else DT_BF16,
+                       pad=pad)
 
 
-def _forward(x, weight, bias, act_id, out_f32, stride=1):
+def _forward(x, weight, bias, act_id, out_f32, stride=1, pad=None, into=None):
     """The forward launch on a device-packed weight.  x: bf16, NCHW-shaped, dense channels-last.  Returns the NCHW-shaped
-    channels-last result (a view of the [n, ho, wo, out_c_total] buffer the kernel wrote) and the descriptor."""
-    d = _desc(x, weight, act_id, out_f32, stride)
+    channels-last result (a view of the [n, ho, wo, out_c_total] buffer the kernel wrote) and the descriptor.  ``pad``: None is k // 2.
+    ``into`` = (buffer [n, ho, wo, c_total], channel offset): the conv writes that channel view of a buffer the caller owns."""
+    d = _desc(x, weight, act_id, out_f32, stride, pad, None if into is None else (into[0].shape[3], into[1]))
     with torch.cuda.device(x.device):
         packed, _, cout_pad = K.pack_conv_weight_dev(weight, d.cin)
         b = torch.zeros((cout_pad,), dtype=torch.float32, device=x.device)
         if bias is not None:
             b[:d.cout] = bias
-        y = torch.empty((d.n, d.ho, d.wo, d.out_c_total), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
+        y = into[0] if into is not None else \
+            torch.empty((d.n, d.ho, d.wo, d.out_c_total), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
         K.conv2d(x, packed, b, y, d)
-    return y[..., :d.cout].permute(0, 3, 1, 2), d
+    return y[..., d.out_c_offset:d.out_c_offset + d.cout].permute(0, 3, 1, 2), d
 
 
 def _conv_grads(x, weight, g, d, need_x, need_w, need_b):
     """The gradients of the conv ``d`` on the dense bf16 g [n, ho, wo, roundup(cout, 8)], each only where asked: (dx, dw, db).  Stride 1
-    runs csrc/conv_bwd.hip, stride 2 csrc/conv_down_bwd.hip.  Every buffer is allocated per call and fully written by its kernel."""
+    runs csrc/conv_bwd.hip, stride 2 csrc/conv_down_bwd.hip: the downsample's entries at pad 1, the unpadded first layer's (a weight
+    gradient only) at pad 0.  Every buffer is allocated per call and fully written by its kernel."""
     down = d.stride == 2
+    stem = down and d.pad == 0
+    if stem and need_x:
+        raise NotImplementedError("the unpadded stride-2 conv is a first layer: it has no data gradient")
     dx = dw = db = None
     if need_w or need_b:
         dw = torch.empty(weight.shape, dtype=torch.float32, device=x.device)
         db = torch.empty((d.cout,), dtype=torch.float32, device=x.device) if need_b else None
-        ws_bytes = K.conv2d_down_bwd_workspace_bytes(d) if down else K.conv2d_bwd_workspace_bytes(d)
+        ws_bytes = K.conv2d_stem_bwd_workspace_bytes(d) if stem else K.conv2d_down_bwd_workspace_bytes(d) if down else \
+            K.conv2d_bwd_workspace_bytes(d)
         ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device)
-        if down:
+        if stem:
+            K.conv2d_stem_bwd_weight(x, g, dw, db, ws, d)
+        elif down:
             K.conv2d_down_bwd_weight(x, g, dw, db, ws, d)
         else:
             K.conv2d_bwd_weight(x, g, dw, db, ws, d)
@@ -153,8 +169,8 @@ class _ConvFunction(torch.autograd.Function):
     """_forward with a backward: prepare (g = dy act'(y)), then _conv_grads.  Once differentiable."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, act_id, out_f32, stride):
-        out, d = _forward(x, weight, None if bias is None else bias.detach(), act_id, out_f32, stride)
+    def forward(ctx, x, weight, bias, act_id, out_f32, stride, pad):
+        out, d = _forward(x, weight, None if bias is None else bias.detach(), act_id, out_f32, stride, pad)
         ctx.desc = d
         ctx.has_bias = bias is not None
         ctx.save_for_backward(x, weight, out if act_id != ACT_NONE else None)
@@ -175,7 +191,7 @@ class _ConvFunction(torch.autograd.Function):
             g = torch.empty((d.n, d.ho, d.wo, K.roundup(d.cout, 8)), dtype=torch.bfloat16, device=x.device)
             K.conv2d_bwd_prepare(dy, y, g, od)
             dx, dw, db = _conv_grads(x, weight, g, d, need_x, need_w, need_b and ctx.has_bias)
-        return dx, dw, db, None, None, None
+        return dx, dw, db, None, None, None, None
 
 
 class _ConvBnFunction(torch.autograd.Function):
@@ -241,13 +257,14 @@ class _ResBnBlockFunction(torch.autograd.Function):
 
 
 # ---- the argument checks and the dispatch the ops share -----------------------------------------------------------------------------------
-def _check_conv(name, x, weight, bias, act, ksizes, cout8):
+def _check_conv(name, x, weight, bias, act, ksizes, cout8, acts=_ACTS):
     """The ValueErrors of a conv-bearing op's x, weight, bias and act; ``ksizes``: the kernel sizes it takes; ``cout8``: cout % 8 == 0
-    is required (every bfloat16 output)."""
+    is required (every bfloat16 output); ``acts``: the activations it takes (_ACTS, or _ACTS_RELU where the backward has the ReLU slope)."""
     if not isinstance(x, torch.Tensor) or not isinstance(weight, torch.Tensor) or x.dim() != 4 or weight.dim() != 4:
         raise ValueError(f"{name}: x must be [n, cin, h, w] and weight [cout, cin, k, k]")
-    if act not in _ACTS:
-        raise ValueError(f"{name}: act must be 'leaky' or 'none', not {act!r}")
+    if act not in acts:
+        names = [repr(a) for a in acts]
+        raise ValueError(f"{name}: act must be {', '.join(names[:-1])} or {names[-1]}, not {act!r}")
     cout, cin, k, k2 = weight.shape
     if k != k2 or k not in ksizes:
         raise ValueError(f"{name}: kernel {k}x{k2} unsupported ({' or '.join(f'{s}x{s}' for s in ksizes)})")
@@ -321,12 +338,12 @@ def _apply(function, plain, tensors, *rest):
     return plain(*(None if t is None else t.detach() for t in tensors), *rest)[0]
 
 
-def _conv_op(name, ksizes, stride, x, weight, bias, act, out_dtype=torch.bfloat16):
+def _conv_op(name, ksizes, stride, x, weight, bias, act, out_dtype=torch.bfloat16, acts=_ACTS):
     """The body of conv_block and down_block, and of the batch-norm ops with ``training=False``."""
-    _check_conv(name, x, weight, bias, act, ksizes, out_dtype == torch.bfloat16)
+    _check_conv(name, x, weight, bias, act, ksizes, out_dtype == torch.bfloat16, acts)
     _need_device(name, x, weight, bias)
     x, weight = _to_kernel_layout(x, weight)
-    return _apply(_ConvFunction, _forward, (x, weight, bias), _ACTS[act], out_dtype == torch.float32, stride)
+    return _apply(_ConvFunction, _forward, (x, weight, bias), acts[act], out_dtype == torch.float32, stride, None)
 
 
 def _bn_op(name, ksizes, stride, pool_stride, x, weight, gamma, beta, running_mean, running_var, training, momentum, eps, act):
@@ -351,7 +368,7 @@ def conv_block(x, weight, bias=None, *, act="leaky", out_dtype=torch.bfloat16, s
             differentiates the conversion and such an x gets a gradient of its own dtype and layout.
     weight  float32 [cout, cin, k, k] on the device, k = 1 or 3 (typically an nn.Parameter; rounded to bf16 for the product).
     bias    float32 [cout] or None.
-    act     "leaky" (LeakyReLU(0.1)) or "none".
+    act     "leaky" (LeakyReLU(0.1)), "none" or "relu" (SqueezeNet's convs; the gradient at y == 0 is 0, torch's rule).
     out_dtype  torch.bfloat16 (``cout % 8 == 0``) or torch.float32 (the head form: any cout).
     Returns an NCHW-shaped channels-last tensor.  Under ``torch.no_grad()``, or when no input requires grad, only the forward runs and
     the result has no ``grad_fn``.  Gradients: x bf16 (rounded once), weight and bias float32, each computed only where asked; two runs
@@ -361,7 +378,7 @@ def conv_block(x, weight, bias=None, *, act="leaky", out_dtype=torch.bfloat16, s
         raise ValueError(f"conv_block: stride {stride} unsupported (the backward covers stride 1)")
     if out_dtype not in (torch.bfloat16, torch.float32):
         raise ValueError(f"conv_block: out_dtype must be torch.bfloat16 or torch.float32, not {out_dtype}")
-    return _conv_op("conv_block", (1, 3), 1, x, weight, bias, act, out_dtype)
+    return _conv_op("conv_block", (1, 3), 1, x, weight, bias, act, out_dtype, _ACTS_RELU)
 
 
 def down_block(x, weight, bias=None, *, act="leaky"):
@@ -587,3 +604,136 @@ def pool_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *
         raise ValueError("pool_bn_block: training=True only (the frozen layer is the models' inference path)")
     _check_pool("pool_bn_block", pool_stride, x.shape[2], x.shape[3])
     return _bn_op("pool_bn_block", (1, 3), 1, int(pool_stride), x, weight, gamma, beta, running_mean, running_var, True, momentum, eps, act)
+
+
+# ---- SqueezeNet 1.1 as it trains: the unpadded first layer, the ceil-mode pool and the Fire module ------------------------
+def stem_block(x, weight, bias=None, *, act="relu"):
+    """``act(conv2d(x, bf16(weight), stride=2, padding=0) + bias)`` on the device, differentiable once in weight and bias: features[0] of
+    SqueezeNet 1.1 (Conv2d(3, 64, 3, stride=2) + ReLU).  The output map is ``((h - 3) // 2 + 1, (w - 3) // 2 + 1)``: an even map's last row
+    and column are never read.  The forward is the launch the eval model runs for that layer.
+
+    x       [n, cin, h, w], h and w >= 3; converted as in conv_block (3 channels are zero-padded to 8).  The op is a first layer: an x
+            that requires grad raises NotImplementedError (there is no data gradient of the unpadded stride-2 conv).
+    weight  float32 [cout, cin, 3, 3] on the device, ``cout % 8 == 0``.      bias  float32 [cout] or None.
+    act     "relu", "leaky" (LeakyReLU(0.1)) or "none".
+    Returns an NCHW-shaped channels-last bfloat16 tensor.  Gradients: weight and bias float32, each computed only where asked; two runs
+    give the same bits.  Grad modes and errors are conv_block's."""
+    _check_conv("stem_block", x, weight, bias, act, (3,), True, _ACTS_RELU)
+    if x.shape[2] < 3 or x.shape[3] < 3:
+        raise ValueError(f"stem_block: a {x.shape[2]} x {x.shape[3]} map has no unpadded 3x3 window")
+    if x.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("stem_block is a first layer: its input is the image and gets no gradient (x.requires_grad is set)")
+    _need_device("stem_block", x, weight, bias)
+    x, weight = _to_kernel_layout(x.detach(), weight)
+    return _apply(_ConvFunction, _forward, (x, weight, bias), _ACTS_RELU[act], False, 2, 0)
+
+
+class _MaxPoolCeilFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        xn = x.permute(0, 2, 3, 1)
+        n, h, w, c = xn.shape
+        with torch.cuda.device(x.device):
+            y = torch.empty((n, h // 2, w // 2, c), dtype=torch.bfloat16, device=x.device)
+            idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+            K.maxpool3s2_train_fwd(xn, y, idx)
+        ctx.shape = tuple(xn.shape)
+        ctx.save_for_backward(idx)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        idx, = ctx.saved_tensors
+        with torch.cuda.device(idx.device):
+            dx = torch.empty(ctx.shape, dtype=torch.bfloat16, device=idx.device)
+            K.maxpool3s2_bwd(_dense_bf16(dy).permute(0, 2, 3, 1), idx, dx)
+        return dx.permute(0, 3, 1, 2)
+
+
+def max_pool_ceil(x):
+    """``max_pool2d(x, 3, 2, ceil_mode=True)`` on the device, differentiable once: the pool of SqueezeNet 1.1.  The output map is
+    ``(ceil((h - 3) / 2) + 1, ceil((w - 3) / 2) + 1)`` = ``(h // 2, w // 2)``; on an even map the last window is partial (its taps beyond
+    the map count as -inf).  x [n, c, h, w], ``c % 8 == 0``, h and w >= 2; bfloat16 dense channels-last is taken as it is, anything else
+    is converted by torch.  Returns bfloat16, channels-last.  The gradient of a window goes to its first maximum in row-major order
+    (torch's rule); the up to four terms of a pixel are summed in fp32 in row-major window order and rounded once.  x must hold no NaN.
+    Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no CPU fallback)."""
+    _check_map("max_pool_ceil", "x", x)
+    if x.shape[2] < 2 or x.shape[3] < 2:
+        raise ValueError(f"max_pool_ceil: the pool needs a map of at least 2 x 2, got {x.shape[2]} x {x.shape[3]}")
+    _need_device("max_pool_ceil", x)
+    return _MaxPoolCeilFunction.apply(_dense_bf16(x))
+
+
+def _fire_forward(x, sw, sb, w1, b1, w3, b3):
+    """The three launches of a Fire module: the squeeze, then the two expands into the channel views of one [n, h, w, e1 + e3] buffer.
+    Returns the NCHW-shaped result and what the backward keeps: the squeeze output and the three descriptors."""
+    s, ds = _forward(x, sw, sb, ACT_RELU, False)
+    e1, e3 = w1.shape[0], w3.shape[0]
+    with torch.cuda.device(x.device):
+        y = torch.empty((ds.n, ds.h, ds.w, e1 + e3), dtype=torch.bfloat16, device=x.device)
+    _, d1 = _forward(s, w1, b1, ACT_RELU, False, into=(y, 0))
+    _, d3 = _forward(s, w3, b3, ACT_RELU, False, into=(y, e1))
+    return y.permute(0, 3, 1, 2), s, (ds, d1, d3)
+
+
+class _FireFunction(torch.autograd.Function):
+    """_fire_forward with a backward: fire_bwd_split (the concat's gradient through the expands' ReLU, as two dense operands), _conv_grads
+    of the two expands, fire_bwd_join (their data gradients summed, through the squeeze's ReLU), _conv_grads of the squeeze.  x, the
+    weights, the squeeze output and the result are kept."""
+
+    @staticmethod
+    def forward(ctx, x, sw, sb, w1, b1, w3, b3):
+        out, s, ctx.descs = _fire_forward(x, sw, sb.detach(), w1, b1.detach(), w3, b3.detach())
+        ctx.save_for_backward(x, sw, w1, w3, s, out)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, sw, w1, w3, s, out = ctx.saved_tensors
+        ds, d1, d3 = ctx.descs
+        need_x, need_sw, need_sb, need_w1, need_b1, need_w3, need_b3 = ctx.needs_input_grad
+        need_s = need_x or need_sw or need_sb
+        dx = dsw = dsb = dw1 = db1 = dw3 = db3 = None
+        with torch.cuda.device(x.device):
+            dy = dy.permute(0, 2, 3, 1).contiguous()                    # dense [n, h, w, e1 + e3]; no copy for a channels-last dy
+            g1 = torch.empty((ds.n, ds.h, ds.w, d1.cout), dtype=torch.bfloat16, device=x.device)
+            g3 = torch.empty((ds.n, ds.h, ds.w, d3.cout), dtype=torch.bfloat16, device=x.device)
+            K.fire_bwd_split(dy, out.permute(0, 2, 3, 1), g1, g3)
+            ds1, dw1, db1 = _conv_grads(s, w1, g1, d1, need_s, need_w1, need_b1)
+            ds3, dw3, db3 = _conv_grads(s, w3, g3, d3, need_s, need_w3, need_b3)
+            if need_s:
+                gs = torch.empty((ds.n, ds.h, ds.w, ds.cout), dtype=torch.bfloat16, device=x.device)
+                K.fire_bwd_join(ds1.permute(0, 2, 3, 1), ds3.permute(0, 2, 3, 1), s.permute(0, 2, 3, 1), gs)
+                dx, dsw, dsb = _conv_grads(x, sw, gs, ds, need_x, need_sw, need_sb)
+        return dx, dsw, dsb, dw1, db1, dw3, db3
+
+
+def fire_block(x, squeeze_w, squeeze_b, e1_w, e1_b, e3_w, e3_b):
+    """SqueezeNet's Fire module on the device, differentiable once, as one op: ``s = relu(conv2d(x, squeeze_w) + squeeze_b)``, then
+    ``cat([relu(conv2d(s, e1_w) + e1_b), relu(conv2d(s, e3_w, padding=1) + e3_b)], 1)`` - the two expand convs write the channel views of
+    the result, so there is no concat copy.  Bit-equal, outputs and gradients, to three ``conv_block(act="relu")`` calls and ``torch.cat``.
+
+    x           [n, cin, h, w]; converted as in conv_block.
+    squeeze_w   float32 [sq, cin, 1, 1];  e1_w float32 [e1, sq, 1, 1];  e3_w float32 [e3, sq, 3, 3]; ``sq``, ``e1`` and ``e3`` multiples
+                of 8 (anything else would misalign a channel view: ValueError).  The biases: float32 [sq], [e1], [e3].
+    Returns bfloat16 [n, e1 + e3, h, w], channels-last.  The backward splits the incoming gradient through the expands' ReLU into the
+    two convs' dense operands in one pass (yolo_fire_bwd_split), runs their weight and data gradients, adds the two data gradients through
+    the squeeze's ReLU in one pass (yolo_fire_bwd_join) and runs the squeeze's gradients.  Gradients: x bf16, weights and biases float32,
+    each computed only where asked (with nothing asked of x and the squeeze conv, no expand data gradient runs); two runs give the same
+    bits.  Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no CPU fallback)."""
+    _check_conv("fire_block", x, squeeze_w, squeeze_b, "relu", (1,), True, _ACTS_RELU)
+    for what, w, b, k in (("e1", e1_w, e1_b, 1), ("e3", e3_w, e3_b, 3)):
+        if not isinstance(w, torch.Tensor) or w.dim() != 4 or tuple(w.shape[1:]) != (squeeze_w.shape[0], k, k) or w.shape[0] < 1:
+            raise ValueError(f"fire_block: {what}_w must be [{what}, sq, {k}, {k}] with sq = {squeeze_w.shape[0]}")
+        if w.shape[0] % 8:
+            raise ValueError(f"fire_block: {what} % 8 == 0 is required (the expand convs write channel views of one map; {what} {w.shape[0]})")
+        if w.dtype != torch.float32:
+            raise ValueError(f"fire_block: {what}_w must be float32")
+    for what, w, b in (("squeeze", squeeze_w, squeeze_b), ("e1", e1_w, e1_b), ("e3", e3_w, e3_b)):
+        if not isinstance(b, torch.Tensor) or b.dtype != torch.float32 or tuple(b.shape) != (w.shape[0],):
+            raise ValueError(f"fire_block: {what}_b must be float32 [{w.shape[0]}]")
+    _need_device("fire_block", x, squeeze_w, squeeze_b, e1_w, e1_b, e3_w, e3_b)
+    x, squeeze_w = _to_kernel_layout(x, squeeze_w)
+    return _apply(_FireFunction, _fire_forward, (x, squeeze_w, squeeze_b, e1_w.contiguous(), e1_b, e3_w.contiguous(), e3_b))
