@@ -325,6 +325,48 @@ YOLO_API int yolo_conv2d_stem_bwd_pick(const YoloConvDesc* d, char* out, int out
 YOLO_API int yolo_conv2d_stem_bwd_weight(const void* x, const void* g, float* dw_oihw, float* dbias, void* workspace, size_t ws_bytes,
                                          const YoloConvDesc* d, yolo_stream_t s);
 
+/* ---- the layers of a training step of MobileNetV2's inverted residual (torchvision's ConvBNReLU with ReLU6, dense and depthwise, and
+ *  the linear bottleneck; models/yolov3_tiny_mobilenet.py:11-34), bf16 mode: three entries of csrc/batchnorm.hip and csrc/dw_train.hip,
+ *  DESIGN.md 3.6j.  The conventions of the blocks above: bf16, DENSE NHWC, c % 8 == 0, a thread owns 8 channels (16 bytes) of a pixel, no
+ *  atomics, every output element and every used workspace byte written exactly once, every sum in a fixed order, no contraction; two runs
+ *  give the same bits.
+ *  yolo_bn_clamp_fwd / yolo_bn_clamp_bwd: yolo_bn_act_fwd / yolo_bn_act_bwd with a clamp for the activation (ReLU6: lo 0, hi 6; ReLU: lo 0,
+ *    hi +inf): a = f32(z) scale + shift; y = bf16_rne(min(max(a, lo), hi)).  Backward: slope = (a > lo && a < hi) ? 1 : 0 - zero AT both
+ *    bounds, torch's hardtanh_backward rule -, ga = f32(dy) slope, and from there 3.6d's arithmetic (xh, the float64 sums B and G, dbeta,
+ *    dgamma, c1, c2, g), workspace (yolo_bn_workspace_bytes), split rule (yolo_bn_pick) and NULL rules.  saved comes from
+ *    yolo_bn_train_stats / yolo_bn_eval_stats as it is.  lo must be finite, hi finite or +inf, lo < hi.
+ *  yolo_bn_add_rounded_fwd: the linear bottleneck's normalise pass with the block's add, act none: a = f32(z) scale + shift; y =
+ *    bf16_rne(f32(bf16_rne(a)) + f32(residual)).  The normalised value is rounded to bf16 BEFORE the add, so the pass is bit-equal to
+ *    yolo_bn_act_fwd(YOLO_ACT_NONE) followed by a bf16 add (an fp32 add rounded once) - unlike yolo_bn_act_add_fwd, which adds to the fp32
+ *    value and rounds once.  The backward needs no entry: dy goes to yolo_bn_act_bwd(YOLO_ACT_NONE) and, unchanged, to the residual.
+ *  The depthwise conv is Conv2d(c, c, 3, stride, 1, groups=c, bias=False), stride 1 or 2: x [n,h,w,c], z and g [n,ho,wo,c], ho = (h - 1) /
+ *    stride + 1, wo likewise.  w is f32 [9][c], tap-major (yolo_dwconv3x3_fwd's layout; 16-byte aligned, it is read in vectors); the
+ *    forward is yolo_dwconv3x3_fwd with act none and a zero bias.  The ops hand w over as bf16 values held in fp32, so that every fmaf
+ *    below is an exact product and one fp32 add.
+ *  yolo_dwconv3x3_bwd_data: dx [n,h,w,c], every element written, as a gather per INPUT pixel (ih, iw): acc = 0; for the taps (kh, kw) in
+ *    row-major order for which oh = (ih + 1 - kh) / stride is integral and in [0, ho), ow likewise: acc = fmaf(f32(g[n,oh,ow]), w[3 kh +
+ *    kw], acc); dx = bf16_rne(acc).
+ *  yolo_dwconv3x3_bwd_weight: dw f32 [c][3][3] (the parameter's layout), dw[ch][kh][kw] = sum_{n,oh,ow} f32(g[n,oh,ow,ch]) * f32(x[n,
+ *    stride oh + kh - 1, stride ow + kw - 1, ch]) over the in-bounds taps: fp32 products (exact: both factors are bf16 values), float64
+ *    sums.  The output pixels are split over workgroups that write float64 partials [split][9][c] into the caller's workspace; one thread
+ *    per (tap, channel) adds them in split order and rounds once to fp32.  Nothing in the workspace needs initialising.
+ *  yolo_dwconv3x3_bwd_weight_workspace_bytes: splits * 9 * c doubles; 0 with a message for a shape the entries do not take.  The split
+ *    count follows yolo_set_launch_cus.
+ *  yolo_dwconv3x3_bwd_weight_pick: "dw_wgrad<3x128x2,s1> grid 157x1 passes 1 last 1" - kernel rows x pixel slots x chunk columns of a pass
+ *    and the stride, grid (pixel splits x column tiles of 2048 channels), passes per split and those of the last split; no launch, no GPU.
+ *  YOLO_E_ARG (YOLO_E_WORKSPACE for a small workspace) before any launch for an empty shape, c % 8, a stride other than 1 or 2, clamp
+ *  bounds as above (a NaN included), pixels < 2 with batch statistics, a null or misaligned pointer (the maps, saved, w, ws: 16 bytes; the
+ *  other fp32 vectors: 4). */
+YOLO_API int yolo_bn_clamp_fwd(const void* z, const float* saved, void* y, long long pixels, int c, float lo, float hi, yolo_stream_t s);
+YOLO_API int yolo_bn_clamp_bwd(const void* dy, int dy_dtype, const void* z, const float* saved, long long pixels, int c, float lo, float hi,
+                               int batch_stats, void* g, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, yolo_stream_t s);
+YOLO_API int yolo_bn_add_rounded_fwd(const void* z, const float* saved, const void* residual, void* y, long long pixels, int c, yolo_stream_t s);
+YOLO_API int yolo_dwconv3x3_bwd_data(const void* g, const float* w, void* dx, int n, int h, int w_, int c, int stride, yolo_stream_t s);
+YOLO_API size_t yolo_dwconv3x3_bwd_weight_workspace_bytes(int n, int h, int w_, int c, int stride);
+YOLO_API int yolo_dwconv3x3_bwd_weight_pick(int n, int h, int w_, int c, int stride, char* out, int out_len);
+YOLO_API int yolo_dwconv3x3_bwd_weight(const void* x, const void* g, float* dw, void* ws, size_t ws_bytes, int n, int h, int w_, int c,
+                                       int stride, yolo_stream_t s);
+
 /* First layer fused with the input packing: x is the caller's f32 NCHW batch [n,cin_real,h,w] (cin_real <= 8),
  * w_packed / bias as for yolo_conv2d_fwd with d->cin = 8; 3x3 / pad 1, bf16 NHWC output: stride 1 with cout 16 or 32
  * (Darknet), or stride 2 with cout 32 (MobileNetV2's first layer). */

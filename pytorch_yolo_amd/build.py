@@ -42,6 +42,7 @@ SOURCES = {
     "route.hip": ["-ffp-contract=off"],
     "pool_train.hip": ["-ffp-contract=off"],
     "fire_train.hip": ["-ffp-contract=off"],
+    "dw_train.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
           "-Wall", "-Wno-unused-function"]

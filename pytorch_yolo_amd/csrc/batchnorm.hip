@@ -7,6 +7,9 @@
 //   act_pool_fwd_kernel                    act_fwd_kernel's pass with MaxPool2d(2, 2) inside: the pooled y and its argmax plane (3.6g)
 //   bwd_reduce_kernel + bwd_finalize_kernel  B = sum ga, G = sum ga xh in float64 -> dgamma, dbeta, c1, c2
 //   act_bwd_kernel                         g = bf16(scale ((ga - c1) - xh c2)), the operand of yolo_conv2d_bwd_weight / _data
+// yolo_bn_clamp_fwd / _bwd are act_fwd_kernel, bwd_reduce_kernel and act_bwd_kernel with the activation min(max(a, lo), hi)
+// (ReLU6: lo 0, hi 6; ReLU: hi +inf) and the slope (a > lo && a < hi) ? 1 : 0 - BnAct below; everything else is shared.
+// yolo_bn_add_rounded_fwd (add_rounded_fwd_kernel) is the linear bottleneck's add: y = bf16(f32(bf16(a)) + f32(residual)).
 // Every pass is a stream of 16-byte loads; a thread owns one chunk of 8 channels.  The two reductions split the rows over blockIdx.x
 // and write float64 partials [split][2][C] that one thread per channel adds in split order: no atomics, no read-modify-write, every
 // output and every used workspace byte written once per call in an order fixed by (M, C, launch_cus).
@@ -53,13 +56,22 @@ BnPick choose_bn(long m, int c, int n_cu) {
 // workspace: c1 | c2 (f32 [2][C], written by the backward's finalize), then the float64 partials [split][2][C]
 size_t bn_ws_bytes(int c, int splits) { return (size_t)2 * c * sizeof(float) + (size_t)splits * 2 * c * sizeof(double); }
 
+// The activation between the batch norm and the next layer: what the element passes apply and what slope the backward takes.
+// kBnLeaky is LeakyReLU(0.1), kBnClamp is min(max(a, lo), hi) with the slope 0 at both bounds (torch's hardtanh_backward rule).
+enum { kBnNone = 0, kBnLeaky = 1, kBnClamp = 2 };
+struct BnAct {
+  int kind;
+  float lo, hi;
+};
+
 struct ReduceArgs {
   const bf16_t* z;
   const void* dy;          // backward only
   const float* saved;      // backward only
   double* part;            // [splits][2][c]
   long m, rows_per_split;
-  int c, chunks, width, rows, leaky;
+  int c, chunks, width, rows;
+  BnAct act;
 };
 
 __device__ __forceinline__ void load8f(const float* p, float (&v)[8]) {
@@ -98,7 +110,15 @@ struct BnVecs {
   float mean[8], invstd[8], scale[8], shift[8];
 };
 
-__device__ __forceinline__ float bn_slope(float a, int leaky) { return (leaky && !(a > 0.f)) ? 0.1f : 1.f; }
+__device__ __forceinline__ float bn_slope(float a, const BnAct& t) {
+  if (t.kind == kBnClamp) return (a > t.lo && a < t.hi) ? 1.f : 0.f;
+  return (t.kind == kBnLeaky && !(a > 0.f)) ? 0.1f : 1.f;
+}
+
+__device__ __forceinline__ float bn_value(float a, const BnAct& t) {
+  if (t.kind == kBnClamp) return fminf(fmaxf(a, t.lo), t.hi);
+  return (t.kind != kBnLeaky || a > 0.f) ? a : 0.1f * a;
+}
 
 // adds the threads of a chunk column in row-slot order and writes the workgroup's partial
 __device__ __forceinline__ void column_sums(double* lds, const double (&s1)[8], const double (&s2)[8], const ReduceArgs& a, int slot, int chunk0) {
@@ -187,7 +207,7 @@ __global__ __launch_bounds__(256) void bwd_reduce_kernel(const ReduceArgs a) {
           for (int j = 0; j < 8; ++j) {
             const float zf = zr[u].at(j);
             const float act_in = zf * p.scale[j] + p.shift[j];
-            const float ga = dr[u].at(j) * bn_slope(act_in, a.leaky);
+            const float ga = dr[u].at(j) * bn_slope(act_in, a.act);
             const float xh = (zf - p.mean[j]) * p.invstd[j];
             s1[j] += (double)ga;
             s2[j] += (double)(ga * xh);
@@ -272,7 +292,7 @@ __global__ __launch_bounds__(256) void bwd_finalize_kernel(const double* __restr
 
 // ---- the two element streams: one thread per chunk of 8 channels of one row ---------------------------------------------------------
 __global__ __launch_bounds__(256) void act_fwd_kernel(const bf16_t* __restrict__ z, const float* __restrict__ saved, bf16_t* __restrict__ y,
-                                                      long total, int c, int chunks, int leaky) {
+                                                      long total, int c, int chunks, const BnAct act) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const int c0 = (int)(idx % chunks) * 8;
@@ -283,7 +303,7 @@ __global__ __launch_bounds__(256) void act_fwd_kernel(const bf16_t* __restrict__
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float a = zv[j] * scale[j] + shift[j];
-    out[j] = (bf16_t)((!leaky || a > 0.f) ? a : 0.1f * a);
+    out[j] = (bf16_t)bn_value(a, act);
   }
   *reinterpret_cast<bf16x8*>(y + idx * 8) = out;
 }
@@ -309,6 +329,25 @@ __global__ __launch_bounds__(256) void act_add_fwd_kernel(const bf16_t* __restri
   }
   *reinterpret_cast<bf16x8*>(y + idx * 8) = out;
   if (PREADD) *reinterpret_cast<bf16x8*>(y_preadd + idx * 8) = pre;
+}
+
+// The linear bottleneck's add: act none, and the normalised value is rounded to bf16 BEFORE the add, y = bf16(f32(bf16(a)) +
+// f32(residual)) - bit-equal to act_fwd_kernel (act none) followed by a bf16 add (an fp32 add rounded once), in one pass.
+__global__ __launch_bounds__(256) void add_rounded_fwd_kernel(const bf16_t* __restrict__ z, const float* __restrict__ saved,
+                                                              const bf16_t* __restrict__ res, bf16_t* __restrict__ y, long total, int c, int chunks) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c0 = (int)(idx % chunks) * 8;
+  float zv[8], rv[8], scale[8], shift[8];
+  load8(z + idx * 8, zv), load8(res + idx * 8, rv);
+  load8f(saved + 2 * (size_t)c + c0, scale), load8f(saved + 3 * (size_t)c + c0, shift);
+  bf16x8 out;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const bf16_t t = (bf16_t)(zv[j] * scale[j] + shift[j]);
+    out[j] = (bf16_t)((float)t + rv[j]);
+  }
+  *reinterpret_cast<bf16x8*>(y + idx * 8) = out;
 }
 
 // act_fwd_kernel's pass with MaxPool2d(2, 2) inside it (the ConvPoolBlock as it trains): one thread per chunk of one POOLED
@@ -354,7 +393,7 @@ __global__ __launch_bounds__(256) void act_pool_fwd_kernel(const bf16_t* __restr
 template <typename TDY>
 __global__ __launch_bounds__(256) void act_bwd_kernel(const TDY* __restrict__ dy, const bf16_t* __restrict__ z, const float* __restrict__ saved,
                                                       const float* __restrict__ c12, bf16_t* __restrict__ g, long total, int c, int chunks,
-                                                      int leaky) {
+                                                      const BnAct act) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= total) return;
   const size_t c0 = (size_t)(idx % chunks) * 8;
@@ -368,7 +407,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const TDY* __restrict__ dy
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     const float a = zv[j] * p.scale[j] + p.shift[j];
-    const float ga = dv[j] * bn_slope(a, leaky);
+    const float ga = dv[j] * bn_slope(a, act);
     const float xh = (zv[j] - p.mean[j]) * p.invstd[j];
     out[j] = (bf16_t)(p.scale[j] * ((ga - c1[j]) - xh * c2[j]));
   }
@@ -388,13 +427,22 @@ int act_check(int act, const char* fn) {
   return 0;
 }
 
+BnAct act_of(int act) { return BnAct{act == YOLO_ACT_LEAKY01 ? kBnLeaky : kBnNone, 0.f, 0.f}; }
+
+// the bounds of the clamp entries: lo finite, hi finite or +inf, lo < hi (a NaN fails every comparison)
+int clamp_check(float lo, float hi, const char* fn) {
+  YOLO_REQUIRE(lo - lo == 0.f && hi == hi && lo < hi, "%s: clamp bounds lo %g, hi %g (lo finite, hi finite or +inf, lo < hi)", fn, (double)lo,
+               (double)hi);
+  return 0;
+}
+
 bool al(const void* p, int n) { return (uintptr_t)p % n == 0; }
 
 ReduceArgs reduce_args(const BnPick& k, long m, int c) {
   ReduceArgs a;
   a.z = nullptr, a.dy = nullptr, a.saved = nullptr, a.part = nullptr;
   a.m = m, a.rows_per_split = k.pps * k.rows;
-  a.c = c, a.chunks = k.chunks, a.width = k.width, a.rows = k.rows, a.leaky = 0;
+  a.c = c, a.chunks = k.chunks, a.width = k.width, a.rows = k.rows, a.act = BnAct{kBnNone, 0.f, 0.f};
   return a;
 }
 
@@ -446,15 +494,26 @@ extern "C" int yolo_bn_eval_stats(const float* gamma, const float* beta, const f
   return yolo_check_launch("bn_eval_stats");
 }
 
+// yolo_bn_act_fwd and yolo_bn_clamp_fwd after their own activation check
+static int bn_fwd(const char* fn, const void* z, const float* saved, void* y, long long pixels, int c, const BnAct& act, yolo_stream_t s) {
+  YOLO_REQUIRE(z && saved && y, "%s: null pointer", fn);
+  YOLO_REQUIRE(al(z, 16) && al(saved, 16) && al(y, 16), "%s: misaligned pointer", fn);
+  const long total = (long)pixels * (c / 8);
+  hipLaunchKernelGGL(act_fwd_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)z, saved, (bf16_t*)y, total, c, c / 8,
+                     act);
+  return yolo_check_launch(fn);
+}
+
 extern "C" int yolo_bn_act_fwd(const void* z, const float* saved, void* y, long long pixels, int c, int act, yolo_stream_t s) {
   if (const int rc = bn_check(pixels, c, "bn_act_fwd")) return rc;
   if (const int rc = act_check(act, "bn_act_fwd")) return rc;
-  YOLO_REQUIRE(z && saved && y, "bn_act_fwd: null pointer");
-  YOLO_REQUIRE(al(z, 16) && al(saved, 16) && al(y, 16), "bn_act_fwd: misaligned pointer");
-  const long total = (long)pixels * (c / 8);
-  hipLaunchKernelGGL(act_fwd_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)z, saved, (bf16_t*)y, total, c, c / 8,
-                     act == YOLO_ACT_LEAKY01);
-  return yolo_check_launch("bn_act_fwd");
+  return bn_fwd("bn_act_fwd", z, saved, y, pixels, c, act_of(act), s);
+}
+
+extern "C" int yolo_bn_clamp_fwd(const void* z, const float* saved, void* y, long long pixels, int c, float lo, float hi, yolo_stream_t s) {
+  if (const int rc = bn_check(pixels, c, "bn_clamp_fwd")) return rc;
+  if (const int rc = clamp_check(lo, hi, "bn_clamp_fwd")) return rc;
+  return bn_fwd("bn_clamp_fwd", z, saved, y, pixels, c, BnAct{kBnClamp, lo, hi}, s);
 }
 
 extern "C" int yolo_bn_act_pool_fwd(const void* z, const float* saved, void* y, void* idx, int n, int h, int w, int c, int act, yolo_stream_t s) {
@@ -489,37 +548,59 @@ extern "C" int yolo_bn_act_add_fwd(const void* z, const float* saved, const void
   return yolo_check_launch("bn_act_add_fwd");
 }
 
-extern "C" int yolo_bn_act_bwd(const void* dy, int dy_dtype, const void* z, const float* saved, long long pixels, int c, int act, int batch_stats,
-                               void* g, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, yolo_stream_t s) {
-  if (const int rc = bn_check(pixels, c, "bn_act_bwd")) return rc;
-  if (const int rc = act_check(act, "bn_act_bwd")) return rc;
-  YOLO_REQUIRE(dy_dtype == YOLO_DT_BF16 || dy_dtype == YOLO_DT_F32, "bn_act_bwd: dy_dtype %d (YOLO_DT_BF16 or YOLO_DT_F32)", dy_dtype);
-  YOLO_REQUIRE(batch_stats == 0 || batch_stats == 1, "bn_act_bwd: batch_stats %d (0 or 1)", batch_stats);
-  YOLO_REQUIRE(!batch_stats || pixels >= 2, "bn_act_bwd: batch statistics need more than one value per channel (pixels %lld)", pixels);
-  YOLO_REQUIRE(dy && z && saved && ws, "bn_act_bwd: null pointer");
-  YOLO_REQUIRE(al(dy, 16) && al(z, 16) && al(saved, 16) && al(g, 16) && al(ws, 16) && al(dgamma, 4) && al(dbeta, 4), "bn_act_bwd: misaligned pointer");
+// yolo_bn_act_bwd and yolo_bn_clamp_bwd after their own activation check
+static int bn_bwd(const char* fn, const void* dy, int dy_dtype, const void* z, const float* saved, long long pixels, int c, const BnAct& act,
+                  int batch_stats, void* g, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, yolo_stream_t s) {
+  YOLO_REQUIRE(dy_dtype == YOLO_DT_BF16 || dy_dtype == YOLO_DT_F32, "%s: dy_dtype %d (YOLO_DT_BF16 or YOLO_DT_F32)", fn, dy_dtype);
+  YOLO_REQUIRE(batch_stats == 0 || batch_stats == 1, "%s: batch_stats %d (0 or 1)", fn, batch_stats);
+  YOLO_REQUIRE(!batch_stats || pixels >= 2, "%s: batch statistics need more than one value per channel (pixels %lld)", fn, pixels);
+  YOLO_REQUIRE(dy && z && saved && ws, "%s: null pointer", fn);
+  YOLO_REQUIRE(al(dy, 16) && al(z, 16) && al(saved, 16) && al(g, 16) && al(ws, 16) && al(dgamma, 4) && al(dbeta, 4), "%s: misaligned pointer", fn);
   const BnPick k = choose_bn(pixels, c, yolo_conv::launch_cus());
   const size_t need = bn_ws_bytes(c, k.splits);
-  if (ws_bytes < need) return yolo_set_error(YOLO_E_WORKSPACE, "bn_act_bwd: workspace %zu < %zu bytes", ws_bytes, need);
-  const int leaky = act == YOLO_ACT_LEAKY01;
+  if (ws_bytes < need) return yolo_set_error(YOLO_E_WORKSPACE, "%s: workspace %zu < %zu bytes", fn, ws_bytes, need);
   float* const c12 = (float*)ws;
   ReduceArgs a = reduce_args(k, pixels, c);
-  a.z = (const bf16_t*)z, a.dy = dy, a.saved = saved, a.leaky = leaky;
+  a.z = (const bf16_t*)z, a.dy = dy, a.saved = saved, a.act = act;
   a.part = reinterpret_cast<double*>((char*)ws + (size_t)2 * c * sizeof(float));
   const bool f32 = dy_dtype == YOLO_DT_F32;
   if (f32) hipLaunchKernelGGL(bwd_reduce_kernel<float>, dim3(k.splits, k.tiles_y), dim3(256), 0, (hipStream_t)s, a);
   else hipLaunchKernelGGL(bwd_reduce_kernel<bf16_t>, dim3(k.splits, k.tiles_y), dim3(256), 0, (hipStream_t)s, a);
-  if (const int rc = yolo_check_launch("bn_act_bwd", " (reduce)")) return rc;
+  if (const int rc = yolo_check_launch(fn, " (reduce)")) return rc;
   hipLaunchKernelGGL(bwd_finalize_kernel, dim3(blocks_for(c)), dim3(256), 0, (hipStream_t)s, (const double*)a.part, k.splits, c, (long)pixels,
                      batch_stats, dgamma, dbeta, c12);
-  if (const int rc = yolo_check_launch("bn_act_bwd", " (finalize)")) return rc;
+  if (const int rc = yolo_check_launch(fn, " (finalize)")) return rc;
   if (!g) return 0;                  // only dgamma / dbeta were asked for
   const long total = (long)pixels * (c / 8);
   if (f32)
     hipLaunchKernelGGL(act_bwd_kernel<float>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const float*)dy, (const bf16_t*)z, saved,
-                       (const float*)c12, (bf16_t*)g, total, c, c / 8, leaky);
+                       (const float*)c12, (bf16_t*)g, total, c, c / 8, act);
   else
     hipLaunchKernelGGL(act_bwd_kernel<bf16_t>, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)dy, (const bf16_t*)z, saved,
-                       (const float*)c12, (bf16_t*)g, total, c, c / 8, leaky);
-  return yolo_check_launch("bn_act_bwd", " (apply)");
+                       (const float*)c12, (bf16_t*)g, total, c, c / 8, act);
+  return yolo_check_launch(fn, " (apply)");
+}
+
+extern "C" int yolo_bn_add_rounded_fwd(const void* z, const float* saved, const void* residual, void* y, long long pixels, int c, yolo_stream_t s) {
+  if (const int rc = bn_check(pixels, c, "bn_add_rounded_fwd")) return rc;
+  YOLO_REQUIRE(z && saved && residual && y, "bn_add_rounded_fwd: null pointer");
+  YOLO_REQUIRE(al(z, 16) && al(saved, 16) && al(residual, 16) && al(y, 16), "bn_add_rounded_fwd: misaligned pointer");
+  const long total = (long)pixels * (c / 8);
+  hipLaunchKernelGGL(add_rounded_fwd_kernel, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)s, (const bf16_t*)z, saved,
+                     (const bf16_t*)residual, (bf16_t*)y, total, c, c / 8);
+  return yolo_check_launch("bn_add_rounded_fwd");
+}
+
+extern "C" int yolo_bn_act_bwd(const void* dy, int dy_dtype, const void* z, const float* saved, long long pixels, int c, int act, int batch_stats,
+                               void* g, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, yolo_stream_t s) {
+  if (const int rc = bn_check(pixels, c, "bn_act_bwd")) return rc;
+  if (const int rc = act_check(act, "bn_act_bwd")) return rc;
+  return bn_bwd("bn_act_bwd", dy, dy_dtype, z, saved, pixels, c, act_of(act), batch_stats, g, dgamma, dbeta, ws, ws_bytes, s);
+}
+
+extern "C" int yolo_bn_clamp_bwd(const void* dy, int dy_dtype, const void* z, const float* saved, long long pixels, int c, float lo, float hi,
+                                 int batch_stats, void* g, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, yolo_stream_t s) {
+  if (const int rc = bn_check(pixels, c, "bn_clamp_bwd")) return rc;
+  if (const int rc = clamp_check(lo, hi, "bn_clamp_bwd")) return rc;
+  return bn_bwd("bn_clamp_bwd", dy, dy_dtype, z, saved, pixels, c, BnAct{kBnClamp, lo, hi}, batch_stats, g, dgamma, dbeta, ws, ws_bytes, s);
 }

@@ -22,7 +22,9 @@ __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pic
            "bn_act_add_fwd", "spp_train_fwd", "spp_bwd", "upsample2_concat_fwd", "upsample2_concat_bwd",
            "maxpool_train_fwd", "maxpool_bwd", "bn_act_pool_fwd", "concat_upsample2_fwd", "concat_upsample2_bwd",
            "maxpool3s2_train_fwd", "maxpool3s2_bwd", "fire_bwd_split", "fire_bwd_join",
-           "conv2d_stem_bwd_workspace_bytes", "conv2d_stem_bwd_pick", "conv2d_stem_bwd_weight"]
+           "conv2d_stem_bwd_workspace_bytes", "conv2d_stem_bwd_pick", "conv2d_stem_bwd_weight",
+           "bn_clamp_fwd", "bn_clamp_bwd", "bn_add_rounded_fwd", "dwconv3x3_bwd_data", "dwconv3x3_bwd_weight_workspace_bytes", "dwconv3x3_bwd_weight_pick",
+           "dwconv3x3_bwd_weight"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -753,6 +755,99 @@ def conv2d_stem_bwd_weight(x, g, dw, dbias, workspace, desc: YoloConvDesc):
     check(load().yolo_conv2d_stem_bwd_weight(_ptr(x), _ptr(g), _ptr(dw), _ptr(dbias), _ptr(workspace), workspace.numel() * workspace.element_size(),
                                              C.byref(desc), stream_ptr()), "conv2d_stem_bwd_weight")
     return dw, dbias
+
+
+# ---- MobileNetV2's inverted residual as it trains (csrc/batchnorm.hip's clamp entries, csrc/dw_train.hip) ---------------
+def bn_clamp_fwd(z, saved, y, lo, hi):
+    """bn_act_fwd with a clamp: y = bf16(min(max(f32(z) scale + shift, lo), hi)) on dense [..., c] bf16 maps (ReLU6: 0, 6)."""
+    _need_cuda(z, saved, y)
+    c = z.shape[-1]
+    pixels = z.numel() // c
+    _bn_map(z, pixels, c, "bn_clamp_fwd: z")
+    _bn_map(y, pixels, c, "bn_clamp_fwd: y")
+    _bn_vec(saved, c, "bn_clamp_fwd: saved", 4)
+    check(load().yolo_bn_clamp_fwd(_ptr(z), _ptr(saved), _ptr(y), pixels, c, float(lo), float(hi), stream_ptr()), "bn_clamp_fwd")
+    return y
+
+
+def bn_clamp_bwd(dy, z, saved, lo, hi, batch_stats, g, dgamma, dbeta, workspace):
+    """bn_act_bwd with the clamp's slope ((a > lo and a < hi) ? 1 : 0, torch's hardtanh rule); arguments, workspace (bn_workspace_bytes)
+    and results as bn_act_bwd."""
+    _need_cuda(dy, z, saved, g, dgamma, dbeta, workspace)
+    c = z.shape[-1]
+    pixels = z.numel() // c
+    _bn_map(z, pixels, c, "bn_clamp_bwd: z")
+    _bn_map(dy, pixels, c, "bn_clamp_bwd: dy", (torch.bfloat16, torch.float32))
+    if g is not None:
+        _bn_map(g, pixels, c, "bn_clamp_bwd: g")
+    _bn_vec(saved, c, "bn_clamp_bwd: saved", 4)
+    _bn_vec(dgamma, c, "bn_clamp_bwd: dgamma")
+    _bn_vec(dbeta, c, "bn_clamp_bwd: dbeta")
+    check(load().yolo_bn_clamp_bwd(_ptr(dy), _dt_of(dy, "dy"), _ptr(z), _ptr(saved), pixels, c, float(lo), float(hi), int(bool(batch_stats)),
+                                   _ptr(g), _ptr(dgamma), _ptr(dbeta), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                   stream_ptr()), "bn_clamp_bwd")
+    return g, dgamma, dbeta
+
+
+def bn_add_rounded_fwd(z, saved, residual, y):
+    """The linear bottleneck's normalise pass with its add (act none): y = bf16(f32(bf16(f32(z) scale + shift)) + f32(residual)) on dense
+    [..., c] bf16 maps - bit-equal to bn_act_fwd(ACT_NONE) followed by a bf16 add."""
+    _need_cuda(z, saved, residual, y)
+    c = z.shape[-1]
+    pixels = z.numel() // c
+    _bn_map(z, pixels, c, "bn_add_rounded_fwd: z")
+    _bn_map(residual, pixels, c, "bn_add_rounded_fwd: residual")
+    _bn_map(y, pixels, c, "bn_add_rounded_fwd: y")
+    _bn_vec(saved, c, "bn_add_rounded_fwd: saved", 4)
+    check(load().yolo_bn_add_rounded_fwd(_ptr(z), _ptr(saved), _ptr(residual), _ptr(y), pixels, c, stream_ptr()), "bn_add_rounded_fwd")
+    return y
+
+
+def _dw_out(h, w, stride):
+    return (h - 1) // stride + 1, (w - 1) // stride + 1
+
+
+def dwconv3x3_bwd_weight_workspace_bytes(n, h, w, c, stride) -> int:
+    """Bytes of caller-owned workspace dwconv3x3_bwd_weight needs for the depthwise conv on x [n, h, w, c] (no launch, works without a
+    GPU): the splits' float64 partials [9][c]."""
+    nbytes = load().yolo_dwconv3x3_bwd_weight_workspace_bytes(int(n), int(h), int(w), int(c), int(stride))
+    if nbytes == 0:
+        check(-1, "dwconv3x3_bwd_weight_workspace_bytes")
+    return int(nbytes)
+
+
+def dwconv3x3_bwd_weight_pick(n, h, w, c, stride) -> str:
+    """Pass shape, grid and passes per split of the depthwise weight gradient (no launch, works without a GPU)."""
+    buf = C.create_string_buffer(256)
+    check(load().yolo_dwconv3x3_bwd_weight_pick(int(n), int(h), int(w), int(c), int(stride), buf, 256), "dwconv3x3_bwd_weight_pick")
+    return buf.value.decode()
+
+
+def dwconv3x3_bwd_data(g, w9c, dx, stride):
+    """dx (bf16 [n, h, w, c], every element written) of the depthwise 3x3 conv (pad 1) from ``g`` (bf16 [n, ho, wo, c]) and ``w9c`` (f32
+    [9, c], tap-major): an fmaf chain in tap order, rounded once."""
+    _need_cuda(g, w9c, dx)
+    n, h, w, c = dx.shape
+    _nhwc(dx, (n, h, w, c), "dwconv3x3_bwd_data: dx")
+    _nhwc(g, (n,) + _dw_out(h, w, stride) + (c,), "dwconv3x3_bwd_data: g")
+    _nhwc(w9c, (9, c), "dwconv3x3_bwd_data: w9c", torch.float32)
+    check(load().yolo_dwconv3x3_bwd_data(_ptr(g), _ptr(w9c), _ptr(dx), n, h, w, c, int(stride), stream_ptr()), "dwconv3x3_bwd_data")
+    return dx
+
+
+def dwconv3x3_bwd_weight(x, g, dw, workspace, stride):
+    """dw (f32, 9 c elements laid out [c, 3, 3]: the [c, 1, 3, 3] parameter) of the depthwise 3x3 conv (pad 1) from ``x`` (bf16 [n, h, w,
+    c]) and ``g`` (bf16 [n, ho, wo, c]): float64 sums of exact fp32 products; ``workspace``: at least
+    dwconv3x3_bwd_weight_workspace_bytes bytes, content irrelevant."""
+    _need_cuda(x, g, dw, workspace)
+    n, h, w, c = x.shape
+    _nhwc(x, (n, h, w, c), "dwconv3x3_bwd_weight: x")
+    _nhwc(g, (n,) + _dw_out(h, w, stride) + (c,), "dwconv3x3_bwd_weight: g")
+    if dw.dtype != torch.float32 or not dw.is_contiguous() or dw.numel() != 9 * c:
+        raise RuntimeError("dwconv3x3_bwd_weight: dw must be contiguous float32 [c, 1, 3, 3]")
+    check(load().yolo_dwconv3x3_bwd_weight(_ptr(x), _ptr(g), _ptr(dw), _ptr(workspace), workspace.numel() * workspace.element_size(), n, h, w,
+                                           c, int(stride), stream_ptr()), "dwconv3x3_bwd_weight")
+    return dw
 
 
 def conv2d_splitk_plan(desc: YoloConvDesc, has_residual=False, has_preadd=False):

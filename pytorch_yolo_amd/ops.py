@@ -9,6 +9,8 @@ The ops (contracts in their docstrings; the kernels in DESIGN.md 3.6c-g):
     spp_concat, upsample_concat     the SPP pyramid, the FPN's upsample + concat
     stem_block, fire_block, max_pool_ceil   SqueezeNet 1.1's unpadded stride-2 first layer, Fire module and MaxPool2d(3, 2, ceil_mode=True)
                                     (DESIGN.md 3.6i); ``conv_block(act="relu")`` is its plain conv
+    conv_bn_relu6_block, dw_bn_block, project_bn_block   MobileNetV2's inverted residual: the dense ConvBNReLU (expand, first and last
+                                    layer), the depthwise ConvBNReLU and the linear bottleneck with its add
 models/train.py wires the training-mode forward of the models from them; the models' eval forward stays inference-only.
 
 The structure - every launch has one owner:
@@ -17,7 +19,8 @@ The structure - every launch has one owner:
                     (csrc/conv_bwd.hip, csrc/conv_down_bwd.hip) and is the only caller of those bindings
     _conv_stats     conv with act none, then the batch statistics: the only caller of bn_train_stats
     _bn_forward     _conv_stats and the tail: bn_act_fwd, bn_act_pool_fwd (pool stride 2) or bn_act_fwd + the stride-1 pool
-    _bn_grads       the batch-norm + activation backward (g, dgamma, dbeta by need): the only caller of bn_act_bwd
+    _bn_act         the normalise-and-activate launch: bn_act_fwd, or bn_clamp_fwd where the activation is a (lo, hi) clamp
+    _bn_grads       the batch-norm + activation backward (g, dgamma, dbeta by need): the only caller of bn_act_bwd / bn_clamp_bwd
     _pool_forward, _pool_backward   the max-pool launches
     _ConvFunction(stride)               conv_block, down_block:  _forward / conv2d_bwd_prepare, _conv_grads
     _ConvBnFunction(stride, pool_stride)  conv_bn_block, down_bn_block, pool_bn_block:  _bn_forward / [_pool_backward,] _bn_grads, _conv_grads
@@ -26,6 +29,10 @@ The structure - every launch has one owner:
     _FireFunction                       fire_block:  three _forward (the expands into one buffer) / fire_bwd_split, _conv_grads twice,
                                         fire_bwd_join, _conv_grads
     _MaxPoolCeilFunction                max_pool_ceil (csrc/fire_train.hip)
+    _DwBnFunction                       dw_bn_block:  _dw_forward (dwconv3x3, bn_train_stats, _bn_act) / _bn_grads, dwconv3x3_bwd_data,
+                                        dwconv3x3_bwd_weight (csrc/dw_train.hip)
+    _ProjectBnFunction                  project_bn_block with a residual:  _conv_stats, bn_add_rounded_fwd / _bn_grads, _conv_grads;
+                                        dy passes through to the residual.  Without one it is _ConvBnFunction
     _check_conv, _check_bn, _need_device    the argument checks: every ValueError, then the RuntimeError, then the first allocation
     _apply          Function.apply where a gradient can be asked for, the plain forward on detached inputs otherwise
 tests/test_ops_trace_gpu.py pins every op's launch list (tests/golden/ops_trace.json).
@@ -38,10 +45,12 @@ from . import kernels as K
 from ._lib import ACT_LEAKY01, ACT_NONE, ACT_RELU, DT_BF16, DT_F32
 
 __all__ = ["conv_block", "conv_bn_block", "down_block", "down_bn_block", "res_bn_block", "spp_concat", "upsample_concat", "max_pool",
-           "pool_bn_block", "stem_block", "fire_block", "max_pool_ceil"]
+           "pool_bn_block", "stem_block", "fire_block", "max_pool_ceil", "conv_bn_relu6_block", "dw_bn_block", "project_bn_block"]
 
 _ACTS = {"leaky": ACT_LEAKY01, "none": ACT_NONE}
 _ACTS_RELU = {**_ACTS, "relu": ACT_RELU}          # the ops without a batch norm at stride 1, and the unpadded first layer
+_RELU6 = (0.0, 6.0)                               # an activation given as (lo, hi) is a clamp: bn_clamp_fwd / bn_clamp_bwd
+_ACTS_DW = {"relu6": _RELU6, "none": ACT_NONE}    # dw_bn_block
 
 
 # ---- the launches and their owners -------------------------------------------------------------------------------------------------------
@@ -124,8 +133,21 @@ def _bn_grads(dy, z, saved, act_id, need_x, need_w, need_g, need_b):
     dgamma = torch.empty((c,), dtype=torch.float32, device=z.device) if need_g else None
     dbeta = torch.empty((c,), dtype=torch.float32, device=z.device) if need_b else None
     ws = torch.empty((K.bn_workspace_bytes(z.numel() // c, c),), dtype=torch.uint8, device=z.device)
-    K.bn_act_bwd(dy, z, saved, act_id, True, g, dgamma, dbeta, ws)
+    if isinstance(act_id, tuple):
+        K.bn_clamp_bwd(dy, z, saved, act_id[0], act_id[1], True, g, dgamma, dbeta, ws)
+    else:
+        K.bn_act_bwd(dy, z, saved, act_id, True, g, dgamma, dbeta, ws)
     return g, dgamma, dbeta
+
+
+def _bn_act(z, saved, act_id):
+    """y = bf16(act(f32(z) scale + shift)) in a new dense map; ``act_id``: an ACT_* value or a (lo, hi) clamp."""
+    y = torch.empty_like(z)
+    if isinstance(act_id, tuple):
+        K.bn_clamp_fwd(z, saved, y, act_id[0], act_id[1])
+    else:
+        K.bn_act_fwd(z, saved, y, act_id)
+    return y
 
 
 def _pool_forward(xn, stride):
@@ -157,8 +179,7 @@ def _bn_forward(x, weight, gamma, beta, running, momentum, eps, act_id, stride=1
             idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
             K.bn_act_pool_fwd(z, saved, y, idx, act_id)
         else:
-            y = torch.empty_like(z)
-            K.bn_act_fwd(z, saved, y, act_id)
+            y = _bn_act(z, saved, act_id)
             if pool_stride == 1:
                 y, idx = _pool_forward(y, 1)
     return y.permute(0, 3, 1, 2), d, z, saved, idx
@@ -737,3 +758,173 @@ def fire_block(x, squeeze_w, squeeze_b, e1_w, e1_b, e3_w, e3_b):
     _need_device("fire_block", x, squeeze_w, squeeze_b, e1_w, e1_b, e3_w, e3_b)
     x, squeeze_w = _to_kernel_layout(x, squeeze_w)
     return _apply(_FireFunction, _fire_forward, (x, squeeze_w, squeeze_b, e1_w.contiguous(), e1_b, e3_w.contiguous(), e3_b))
+
+
+# ---- MobileNetV2's inverted residual as it trains: ConvBNReLU dense and depthwise, the linear bottleneck ------------------
+def conv_bn_relu6_block(x, weight, gamma, beta, running_mean=None, running_var=None, *, stride=1, momentum=0.1, eps=1e-5, training=True):
+    """``relu6(batch_norm(conv2d(x, bf16(weight), stride=stride, padding=k // 2)))`` on the device, differentiable once: torchvision's dense
+    ConvBNReLU (Conv2d(bias=False) -> BatchNorm2d -> ReLU6) as it trains - 1x1 at stride 1 (an inverted residual's expand, the last
+    layer), 3x3 at stride 1 or 2 (the first layer; its 3 input channels are zero-padded to 8 as in conv_block).
+
+    conv_bn_block's contract (down_bn_block's at stride 2) with ``training=True`` (anything else raises ValueError): the same launches but
+    for the two batch-norm passes, which clamp (yolo_bn_clamp_fwd / yolo_bn_clamp_bwd with lo 0, hi 6).  The gradient is 0 where the
+    normalised value is <= 0 or >= 6 (torch's hardtanh rule).
+    Gradients: x bf16, weight, gamma and beta float32, each computed only where asked; two runs give the same bits."""
+    if isinstance(stride, bool) or stride not in (1, 2):
+        raise ValueError(f"conv_bn_relu6_block: stride {stride!r} unsupported (1 or 2)")
+    _check_conv("conv_bn_relu6_block", x, weight, None, "none", (1, 3) if stride == 1 else (3,), True)
+    if not training:
+        raise ValueError("conv_bn_relu6_block: training=True only (the frozen layer is the models' inference path)")
+    running = _check_bn("conv_bn_relu6_block", x, weight, stride, gamma, beta, running_mean, running_var, True, momentum, eps)
+    _need_device("conv_bn_relu6_block", x, weight, gamma, beta, running_mean, running_var)
+    x, weight = _to_kernel_layout(x, weight)
+    return _apply(_ConvBnFunction, _bn_forward, (x, weight, gamma.contiguous(), beta.contiguous()), running, float(momentum), float(eps),
+                  _RELU6, int(stride), 0)
+
+
+def _dw_forward(x, weight, gamma, beta, running, momentum, eps, act_id, stride):
+    """The depthwise conv (act none, zero bias) on the weight rounded once to bf16 and laid out [9, c], the batch statistics of its output
+    map and the normalise-and-activate pass.  Returns the NCHW-shaped result and what the backward keeps: z, saved and the [9, c] weight."""
+    xn = x.permute(0, 2, 3, 1)
+    n, h, w, c = xn.shape
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    with torch.cuda.device(x.device):
+        w9c = weight.detach().to(torch.bfloat16).to(torch.float32).reshape(c, 9).t().contiguous()
+        z = torch.empty((n, ho, wo, c), dtype=torch.bfloat16, device=x.device)
+        K.dwconv3x3(xn, w9c, torch.zeros((c,), dtype=torch.float32, device=x.device), z, n=n, h=h, w=w, c=c, in_view=(c, 0), out_view=(c, 0),
+                    stride=stride, act=ACT_NONE)
+        saved = torch.empty((4, c), dtype=torch.float32, device=x.device)
+        ws = torch.empty((K.bn_workspace_bytes(n * ho * wo, c),), dtype=torch.uint8, device=x.device)
+        K.bn_train_stats(z, gamma, beta, eps, momentum, running[0], running[1], saved, ws)
+        y = _bn_act(z, saved, act_id)
+    return y.permute(0, 3, 1, 2), z, saved, w9c
+
+
+class _DwBnFunction(torch.autograd.Function):
+    """_dw_forward with a backward: _bn_grads, then the depthwise data and weight gradients on its g, each only where asked.  x, the
+    [9, c] weight, z and saved are kept, y is not."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, running, momentum, eps, act_id, stride):
+        out, z, saved, w9c = _dw_forward(x, weight, gamma.detach(), beta.detach(), running, momentum, eps, act_id, stride)
+        ctx.act_id, ctx.stride = act_id, stride
+        ctx.save_for_backward(x, w9c, z, saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w9c, z, saved = ctx.saved_tensors
+        need_x, need_w, need_g, need_b = ctx.needs_input_grad[:4]
+        dx = dw = None
+        with torch.cuda.device(x.device):
+            g, dgamma, dbeta = _bn_grads(dy, z, saved, ctx.act_id, need_x, need_w, need_g, need_b)
+            xn = x.permute(0, 2, 3, 1)
+            n, h, w, c = xn.shape
+            if need_x:
+                buf = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=x.device)
+                K.dwconv3x3_bwd_data(g, w9c, buf, ctx.stride)
+                dx = buf.permute(0, 3, 1, 2)
+            if need_w:
+                dw = torch.empty((c, 1, 3, 3), dtype=torch.float32, device=x.device)
+                ws = torch.empty((K.dwconv3x3_bwd_weight_workspace_bytes(n, h, w, c, ctx.stride),), dtype=torch.uint8, device=x.device)
+                K.dwconv3x3_bwd_weight(xn, g, dw, ws, ctx.stride)
+        return dx, dw, dgamma, dbeta, None, None, None, None, None
+
+
+def dw_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *, stride=1, act="relu6", momentum=0.1, eps=1e-5, training=True):
+    """``act(batch_norm(conv2d(x, bf16(weight), stride=stride, padding=1, groups=c)))`` on the device, differentiable once: the depthwise
+    ConvBNReLU of an inverted residual (Conv2d(c, c, 3, stride, 1, groups=c, bias=False) -> BatchNorm2d -> ReLU6) as it trains.
+
+    x       [n, c, h, w], ``c % 8 == 0`` (a depthwise conv has no channel padding); bfloat16 dense channels-last is taken as it is,
+            anything else is converted by torch.
+    weight  float32 [c, 1, 3, 3] on the device; rounded to bf16 once for the products, in the forward and in the data gradient.
+    stride  1 or 2; the output map is ``((h - 1) // stride + 1, (w - 1) // stride + 1)``.
+    act     "relu6", or "none" (ShuffleNetV2's linear depthwise stage).
+    gamma, beta, the running tensors, momentum and eps as in conv_bn_block; ``training=True`` only (anything else raises ValueError).
+    Returns an NCHW-shaped channels-last bfloat16 tensor.  The forward conv is the launch the eval models run (yolo_dwconv3x3_fwd).
+    Gradients: x bf16 (an fp32 chain in tap order, rounded once), weight float32 [c, 1, 3, 3] (float64 sums of exact products), gamma
+    and beta float32, each computed only where asked; two runs give the same bits.
+    Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no CPU fallback)."""
+    name = "dw_bn_block"
+    if not isinstance(x, torch.Tensor) or not isinstance(weight, torch.Tensor) or x.dim() != 4 or weight.dim() != 4:
+        raise ValueError(f"{name}: x must be [n, c, h, w] and weight [c, 1, 3, 3]")
+    if act not in _ACTS_DW:
+        raise ValueError(f"{name}: act must be 'relu6' or 'none', not {act!r}")
+    if isinstance(stride, bool) or stride not in (1, 2):
+        raise ValueError(f"{name}: stride {stride!r} unsupported (1 or 2)")
+    if min(x.shape) < 1:
+        raise ValueError(f"{name}: empty tensor")
+    c = x.shape[1]
+    if tuple(weight.shape) != (c, 1, 3, 3):
+        raise ValueError(f"{name}: weight must be [c, 1, 3, 3] with c = {c} (a 3x3 depthwise conv), not {list(weight.shape)}")
+    if c % 8:
+        raise ValueError(f"{name}: c % 8 == 0 is required (c {c})")
+    if weight.dtype != torch.float32:
+        raise ValueError(f"{name}: weight must be float32 [c, 1, 3, 3]")
+    if not training:
+        raise ValueError(f"{name}: training=True only (the frozen layer is the models' inference path)")
+    running = _check_bn(name, x, weight, stride, gamma, beta, running_mean, running_var, True, momentum, eps)
+    _need_device(name, x, weight, gamma, beta, running_mean, running_var)
+    return _apply(_DwBnFunction, _dw_forward, (_dense_bf16(x), weight.contiguous(), gamma.contiguous(), beta.contiguous()), running,
+                  float(momentum), float(eps), _ACTS_DW[act], int(stride))
+
+
+def _project_forward(x, weight, gamma, beta, residual, running, momentum, eps):
+    """_conv_stats -> normalise and add the residual in one pass (yolo_bn_add_rounded_fwd: the normalised value is rounded to bf16 before
+    the add, as conv_bn_block(act="none") followed by a bf16 add would)."""
+    z, d, saved = _conv_stats(x, weight, gamma, beta, running, momentum, eps)
+    with torch.cuda.device(x.device):
+        y = torch.empty_like(z)
+        K.bn_add_rounded_fwd(z, saved, residual.permute(0, 2, 3, 1), y)
+    return y.permute(0, 3, 1, 2), d, z, saved
+
+
+class _ProjectBnFunction(torch.autograd.Function):
+    """_project_forward with a backward: _ConvBnFunction's with act none on dy; dy itself is the residual's."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, residual, running, momentum, eps):
+        out, ctx.desc, z, saved = _project_forward(x, weight, gamma.detach(), beta.detach(), residual.detach(), running, momentum, eps)
+        ctx.save_for_backward(x, weight, z, saved)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, z, saved = ctx.saved_tensors
+        need_x, need_w, need_g, need_b, need_r = ctx.needs_input_grad[:5]
+        dx = dw = dgamma = dbeta = None
+        if need_x or need_w or need_g or need_b:
+            with torch.cuda.device(x.device):
+                g, dgamma, dbeta = _bn_grads(dy, z, saved, ACT_NONE, need_x, need_w, need_g, need_b)
+                dx, dw, _ = _conv_grads(x, weight, g, ctx.desc, need_x, need_w, False)
+        return dx, dw, dgamma, dbeta, (dy if need_r else None), None, None, None
+
+
+def project_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, residual=None, *, momentum=0.1, eps=1e-5, training=True):
+    """``batch_norm(conv2d(x, bf16(weight)))`` with a 1x1 weight and no activation, plus ``residual`` where one is given, on the device,
+    differentiable once: the linear bottleneck that closes an inverted residual (Conv2d(hidden, cout, 1, bias=False) -> BatchNorm2d, and
+    the block's ``x + conv(x)`` at stride 1 with cin == cout) as it trains.
+
+    conv_bn_block's contract with a 1x1 weight, ``act="none"`` and ``training=True`` (anything else raises ValueError).
+    residual    None, or [n, cout, h, w]: the add is fused into the normalise pass (yolo_bn_add_rounded_fwd): ``y = bf16(f32(bf16(a)) +
+                f32(residual))`` with ``a`` the normalised fp32 value - bit-equal to ``conv_bn_block(act="none")`` followed by a bf16 add
+                (one fp32 add, one rounding), in one launch.
+                bfloat16 dense channels-last is taken as it is, anything else is converted by torch.
+    Gradients: x bf16, weight, gamma and beta float32, residual the incoming gradient unchanged; each computed only where asked."""
+    name = "project_bn_block"
+    _check_conv(name, x, weight, None, "none", (1,), True)
+    if not training:
+        raise ValueError(f"{name}: training=True only (the frozen layer is the models' inference path)")
+    if residual is not None and (not isinstance(residual, torch.Tensor) or
+                                 tuple(residual.shape) != (x.shape[0], weight.shape[0], x.shape[2], x.shape[3])):
+        raise ValueError(f"{name}: residual must be [n, cout, h, w]")
+    running = _check_bn(name, x, weight, 1, gamma, beta, running_mean, running_var, True, momentum, eps)
+    _need_device(name, x, weight, residual, gamma, beta, running_mean, running_var)
+    x, weight = _to_kernel_layout(x, weight)
+    if residual is None:
+        return _apply(_ConvBnFunction, _bn_forward, (x, weight, gamma.contiguous(), beta.contiguous()), running, float(momentum), float(eps),
+                      ACT_NONE, 1, 0)
+    return _apply(_ProjectBnFunction, _project_forward, (x, weight, gamma.contiguous(), beta.contiguous(), _dense_bf16(residual)), running,
+                  float(momentum), float(eps))
