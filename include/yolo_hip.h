@@ -533,7 +533,10 @@ YOLO_API int yolo_head_decode_fwd(const void* x, const void* w_packed, const flo
  *  out_dets [bs,cap,7] (x1,y1,x2,y2,conf,cls_conf,cls), out_idx [bs,cap] = pivot row of each output,
  *  out_count [bs].  Rows are ordered by conf descending (ties: class, then pivot order).
  *  cap >= min(rows, nc*max_per_class) guarantees nothing is dropped; if an image would exceed cap,
- *  out_count holds the true count and only the first cap rows are written. */
+ *  out_count holds the true count and only the first cap rows are written.
+ *  Staging rule: inside the workspace every image has a staging area of min(rows, nc*128) rows (128 = the largest max_per_class),
+ *  which is every row the class loops can emit, so no kept row is ever lost before the final order - also when an image keeps more
+ *  than 8192 rows (nc*max_per_class > 8192), in which case the final sort runs in the workspace instead of LDS. */
 YOLO_API size_t yolo_nms_workspace_bytes(int bs, int rows, int nc);
 YOLO_API int yolo_nms_merge(float* pred, int bs, int rows, int nc, float conf_thres, float nms_thres, float min_wh,
                    int max_per_class, int mutate_conf, float* out_dets, int32_t* out_idx,

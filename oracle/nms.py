@@ -43,12 +43,13 @@ def _iou_1_to_n(b, boxes):
         return inter / union
 
 
-def nms_image(pred, conf_thres, nms_thres, mutate=True):
+def nms_image(pred, conf_thres, nms_thres, mutate=True, max_per_class=MAX_PER_CLASS):
     """One image: pred [N, 5+nc] float32 (xywh, obj, cls...).
 
     Returns (dets [n,7] float32, kept_idx [n] int64) or (None, None).
     With ``mutate`` the input's column 4 is overwritten with obj*max_cls like
-    the reference does at utils.py:213.
+    the reference does at utils.py:213.  ``max_per_class`` is the cap of
+    utils.py:247-250 (the reference's constant 100 by default).
     """
     assert pred.dtype == np.float32 and pred.ndim == 2
     conf_thres = F32(conf_thres)
@@ -78,7 +79,7 @@ def nms_image(pred, conf_thres, nms_thres, mutate=True):
 
     out_rows, out_idx = [], []
     for c in np.unique(cpred):                               # ascending, :241
-        sel = np.nonzero(cpred == c)[0][:MAX_PER_CLASS]      # :242,:247-250
+        sel = np.nonzero(cpred == c)[0][:max_per_class]      # :242,:247-250
         b, s, cc, ii = boxes[sel].copy(), conf[sel], cconf[sel], idx[sel]
         alive = np.ones(len(sel), dtype=bool)
         while alive.any():                                   # :267
@@ -109,12 +110,12 @@ def nms_image(pred, conf_thres, nms_thres, mutate=True):
     return dets[final], kept[final]
 
 
-def non_max_suppression(prediction, conf_thres=0.5, nms_thres=0.5, mutate=True):
+def non_max_suppression(prediction, conf_thres=0.5, nms_thres=0.5, mutate=True, max_per_class=MAX_PER_CLASS):
     """Batch wrapper with the reference's signature/return (utils.py:200-206,293):
     list (len bs) of float32 [n,7] arrays or None, plus the kept-index lists."""
     dets, kept = [], []
     for pred in prediction:
-        d, k = nms_image(pred, conf_thres, nms_thres, mutate=mutate)
+        d, k = nms_image(pred, conf_thres, nms_thres, mutate=mutate, max_per_class=max_per_class)
         dets.append(d)
         kept.append(k)
     return dets, kept

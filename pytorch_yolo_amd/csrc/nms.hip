@@ -14,7 +14,8 @@
 //                appended (wave-aggregated atomic) as 64-bit sort keys  class | ~conf | row.
 //   nms_merge  : one 1024-thread workgroup per image: bitonic sort of the keys (LDS up to 8192 keys,
 //                global workspace beyond), class segments, one wave per class runs the sequential
-//                MERGE over its first max_per_class rows with ballot masks, final sort by conf.
+//                MERGE over its first max_per_class rows with ballot masks, final sort by conf (in LDS
+//                up to 8192 kept rows, in the image's key row of the workspace beyond).
 //                The per-class loop is the kernel's template parameter: one instantiation per suppression style of the
 //                reference (YOLO_NMS_MERGE :266-275, _OR :253-259, _AND :260-265, _SOFT :277-287); everything around it - filter,
 //                key sort, class segments, work queue, final order - is the same code for all four.  The decisions of OR and
@@ -510,8 +511,36 @@ __global__ __launch_bounds__(kMergeThreads) void nms_merge_kernel(const MergeArg
   __syncthreads();
 
   // ---- final order: conf descending, ties by class then pivot order (utils.py:289-291) -------------
-  const int n_out = min(s_nout, a.stage_cap);
+  const int n_out = min(s_nout, a.stage_cap);       // (stage_cap >= min(rows, nc * max_per_class) >= s_nout: nothing is cut here)
   __threadfence_block();
+  if (n_out > kLdsKeys) {
+    // more kept rows than s_keys holds (nc * max_per_class > 8192, e.g. 90 classes under 'SOFT'): the final keys are built and
+    // sorted in the image's own key row of the workspace.  n_out > kLdsKeys implies n > kLdsKeys, so the class loop read its
+    // candidates from that row (keys == gkeys), every wave is past it (the barrier above), and the row has
+    // key_pitch >= n_pad >= g_pad slots.
+    int g_pad = 2 * kLdsKeys;
+    while (g_pad < n_out) g_pad <<= 1;
+    for (int i = tid; i < g_pad; i += kMergeThreads) {
+      u64 k = ~0ull;
+      if (i < n_out) {
+        const float* o = stage + (long)i * 8;
+        k = ((u64)(~f32_sortable(o[4])) << 32) | ((u64)(uint32_t)o[6] << 20) | (u64)i;
+      }
+      gkeys[i] = k;
+    }
+    __syncthreads();
+    block_bitonic_sort(gkeys, g_pad, false);
+    for (int i = tid; i < n_out && i < a.cap; i += kMergeThreads) {
+      const int slot = (int)(gkeys[i] & 0xfffffu);
+      const float* o = stage + (long)slot * 8;
+      float* d = a.out_dets + ((long)b * a.cap + i) * 7;
+#pragma unroll
+      for (int e = 0; e < 7; ++e) d[e] = o[e];
+      a.out_idx[(long)b * a.cap + i] = __float_as_int(o[7]);
+    }
+    if (tid == 0) a.out_count[b] = s_nout;
+    return;
+  }
   int f_pad = 1;
   while (f_pad < n_out) f_pad <<= 1;
   const bool small_final = f_pad <= 512;            // few kept rows: the plain LDS network (mostly wave-local) is cheaper
@@ -521,7 +550,7 @@ __global__ __launch_bounds__(kMergeThreads) void nms_merge_kernel(const MergeArg
     if (i < n_out) {
       const float* o = stage + (long)i * 8;
       const uint32_t dconf = ~f32_sortable(o[4]);
-      // conf:32 | class:12 | slot:13 (slot order within a class follows pivot order because each
+      // conf:32 | class:12 | slot:20 (slot order within a class follows pivot order because each
       // class is emitted by one wave in sequence)  -> compare on conf, class first; slot breaks ties
       k = ((u64)dconf << 32) | ((u64)(uint32_t)o[6] << 20) | (u64)i;
     }
@@ -636,6 +665,8 @@ extern "C" int yolo_nms_styled(float* pred, int bs, int rows, int nc, float conf
   if (int rc = nms_check(bs, rows, nc, nms_thres, max_per_class, cap, style)) return rc;
   const int no = nc + 5;
   const size_t tile_bytes = (size_t)kFilterRows * no * 4;
+  // (nc = 251 asks for exactly 64 KiB of dynamic LDS beside the filter's two static ints; a gfx950 workgroup has 160 KiB and the launch
+  // needs no attribute: tests/test_nms_edges_gpu.py::test_wide_rows runs it, nc = 252 is refused here)
   YOLO_REQUIRE(tile_bytes <= 64 * 1024, "nms: row of %d floats too wide", no);
   if (workspace_bytes < yolo_nms_workspace_bytes(bs, rows, nc))
     return yolo_set_error(YOLO_E_WORKSPACE, "nms: workspace %zu < %zu bytes", workspace_bytes,

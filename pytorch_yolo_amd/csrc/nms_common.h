@@ -36,10 +36,12 @@ inline size_t pow2_at_least(size_t v) {
   while (p < v) p <<= 1;
   return p;
 }
+// Rows of the staging area per image: every row the class loops can emit, min(rows, nc * max_per_class).  It is NOT clamped to
+// kLdsKeys: an image that keeps more than 8192 rows sorts its final keys in the workspace's key row (nms_merge_kernel), and a
+// smaller staging area would lose whichever emitted rows drew the slots beyond it.
 inline int stage_cap_for(int rows, int nc, int max_per_class) {
   long c = (long)nc * max_per_class;
   if (c > rows) c = rows;
-  if (c > kLdsKeys) c = kLdsKeys;
   return (int)c;
 }
 

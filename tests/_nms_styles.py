@@ -48,8 +48,9 @@ def candidates(pred, conf_thres):
     return idx[order], boxes[order], conf[order], cconf[order], cpred[order]
 
 
-def nms_image(pred, conf_thres, nms_thres, style):
-    """One image in style 'OR' | 'AND' | 'SOFT': (dets [n,7] float32, kept input rows [n] int64) or (None, None)."""
+def nms_image(pred, conf_thres, nms_thres, style, max_per_class=MAX_PER_CLASS):
+    """One image in style 'OR' | 'AND' | 'SOFT': (dets [n,7] float32, kept input rows [n] int64) or (None, None).  ``max_per_class``:
+    the cap of :247-250, the reference's 100 by default."""
     assert style in STYLES
     nms_thres = F32(nms_thres)
     cand = candidates(pred, conf_thres)
@@ -69,7 +70,7 @@ def nms_image(pred, conf_thres, nms_thres, style):
             k = sel[0]
             emit(boxes[k], conf[k], cconf[k], c, idx[k])
             continue
-        sel = sel[:MAX_PER_CLASS]                                            # :247-250
+        sel = sel[:max_per_class]                                            # :247-250
         b, s, cc, ii = boxes[sel], conf[sel].copy(), cconf[sel], idx[sel]
         left = np.arange(len(sel))                                           # dc, as positions in the capped class list
         if style == "OR":
@@ -103,11 +104,11 @@ def nms_image(pred, conf_thres, nms_thres, style):
     return dets[final], kept[final]
 
 
-def non_max_suppression(prediction, conf_thres, nms_thres, style):
+def non_max_suppression(prediction, conf_thres, nms_thres, style, max_per_class=MAX_PER_CLASS):
     """Batch wrapper: (list of dets or None, list of kept-index arrays or None)."""
     dets, kept = [], []
     for pred in prediction:
-        d, k = nms_image(pred, conf_thres, nms_thres, style)
+        d, k = nms_image(pred, conf_thres, nms_thres, style, max_per_class)
         dets.append(d)
         kept.append(k)
     return dets, kept
