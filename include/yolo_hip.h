@@ -367,6 +367,23 @@ YOLO_API int yolo_dwconv3x3_bwd_weight_pick(int n, int h, int w_, int c, int str
 YOLO_API int yolo_dwconv3x3_bwd_weight(const void* x, const void* g, float* dw, void* ws, size_t ws_bytes, int n, int h, int w_, int c,
                                        int stride, yolo_stream_t s);
 
+/* ---- the depthwise conv of an expanding inverted residual on the expand conv's output, the batch norm and clamp of that output applied as
+ *  the operand is loaded (csrc/dw_train.hip): the activation y between the two convs is never written.  zin [n,h,w,c] is
+ *  the expand conv's bf16 output, saved_in f32 [4][c] = mean, invstd, scale, shift as yolo_bn_train_stats wrote it.  Both entries use ONE
+ *  definition of the operand: inside the map a = fl(fl(f32(zin) * scale) + shift) - two fp32 roundings, no fma, yolo_bn_clamp_fwd's - and
+ *  y = bf16_rne(fminf(fmaxf(a, lo), hi)); outside the map y = 0: the padding is a zero of y, NOT the clamp of a zero zin (clamp(shift)).
+ *  yolo_dwconv3x3_bnin_fwd: z [n,ho,wo,c], bit-equal to yolo_dwconv3x3_fwd(y, w, zero bias, act none) on the materialised y: acc = 0, the
+ *    taps row by row, one fmaf a tap, one rounding to bf16.  w as above (f32 [9][c]).
+ *  yolo_dwconv3x3_bnin_bwd_weight: dw f32 [c][3][3], bit-equal to yolo_dwconv3x3_bwd_weight(y, g, ..): the same split rule, workspace
+ *    (yolo_dwconv3x3_bwd_weight_workspace_bytes), pick (yolo_dwconv3x3_bwd_weight_pick) and finalize.
+ *  The data gradient needs no entry: yolo_dwconv3x3_bwd_data gives the gradient with respect to y, yolo_bn_clamp_bwd takes it from there
+ *  on zin and saved_in.  YOLO_E_ARG / YOLO_E_WORKSPACE before any launch as for the entries above; lo, hi as for yolo_bn_clamp_fwd; the
+ *  maps, saved_in, w and ws 16-byte aligned. */
+YOLO_API int yolo_dwconv3x3_bnin_fwd(const void* zin, const float* saved_in, float lo, float hi, const float* w, void* z, int n, int h, int w_,
+                                     int c, int stride, yolo_stream_t s);
+YOLO_API int yolo_dwconv3x3_bnin_bwd_weight(const void* zin, const float* saved_in, float lo, float hi, const void* g, float* dw, void* ws,
+                                            size_t ws_bytes, int n, int h, int w_, int c, int stride, yolo_stream_t s);
+
 /* First layer fused with the input packing: x is the caller's f32 NCHW batch [n,cin_real,h,w] (cin_real <= 8),
  * w_packed / bias as for yolo_conv2d_fwd with d->cin = 8; 3x3 / pad 1, bf16 NHWC output: stride 1 with cout 16 or 32
  * (Darknet), or stride 2 with cout 32 (MobileNetV2's first layer). */

@@ -11,6 +11,7 @@ from typing import List, Optional
 import torch
 
 from . import kernels as K
+from .utils.torch_utils import fold_conv_bn
 
 
 @dataclass(eq=False)
@@ -138,6 +139,24 @@ class Recorder:
             w_, b_ = wb(conv)
             return pad(w_, (0, 0, 0, 0, 0, sp - sq)), b_
         return self.concat([self.conv(s, widen(fire.expand1x1), act="relu"), self.conv(s, widen(fire.expand3x3), act="relu")])
+
+    # MobileNetV2's two layers (models/yolov3_tiny_mobilenet.py); they are what models/train.MobileTracer adds to the trainable vocabulary.
+    def conv_bn_relu6(self, module, x: Sym):
+        """torchvision's ConvBNReLU (Conv2d(bias=False) -> BatchNorm2d -> ReLU6) with its BN folded: dense or depthwise."""
+        conv, bn = module[0], module[1]
+        w = fold_conv_bn(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+        if module.depthwise:
+            return self.dwconv(x, w, stride=module.stride, act="relu6")
+        return self.conv(x, w, stride=module.stride, act="relu6")
+
+    def inverted_residual(self, block, x: Sym):
+        """An inverted residual: [expand 1x1 ->] depthwise 3x3 -> the linear bottleneck (no activation) with the block's add."""
+        y = x
+        for m in list(block.conv)[:-2]:
+            y = self.conv_bn_relu6(m, y)
+        conv, bn = block.conv[-2], block.conv[-1]
+        proj = fold_conv_bn(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+        return self.conv(y, proj, stride=1, act="none", residual=x if block.use_res_connect else None)
 
     def dwconv(self, x: Sym, weight, stride=1, act="relu6", tf_same=False):
         """Depthwise k x k conv.  Default: 3x3 / pad 1 (MobileNetV2).  ``tf_same``: k = 3 or 5 with TensorFlow "same" padding

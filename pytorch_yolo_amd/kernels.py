@@ -24,7 +24,7 @@ __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pic
            "maxpool3s2_train_fwd", "maxpool3s2_bwd", "fire_bwd_split", "fire_bwd_join",
            "conv2d_stem_bwd_workspace_bytes", "conv2d_stem_bwd_pick", "conv2d_stem_bwd_weight",
            "bn_clamp_fwd", "bn_clamp_bwd", "bn_add_rounded_fwd", "dwconv3x3_bwd_data", "dwconv3x3_bwd_weight_workspace_bytes", "dwconv3x3_bwd_weight_pick",
-           "dwconv3x3_bwd_weight"]
+           "dwconv3x3_bwd_weight", "dwconv3x3_bnin_fwd", "dwconv3x3_bnin_bwd_weight"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -847,6 +847,37 @@ def dwconv3x3_bwd_weight(x, g, dw, workspace, stride):
         raise RuntimeError("dwconv3x3_bwd_weight: dw must be contiguous float32 [c, 1, 3, 3]")
     check(load().yolo_dwconv3x3_bwd_weight(_ptr(x), _ptr(g), _ptr(dw), _ptr(workspace), workspace.numel() * workspace.element_size(), n, h, w,
                                            c, int(stride), stream_ptr()), "dwconv3x3_bwd_weight")
+    return dw
+
+
+def dwconv3x3_bnin_fwd(zin, saved, lo, hi, w9c, z, stride):
+    """z (bf16 [n, ho, wo, c]) of the depthwise 3x3 conv (pad 1, no bias, no activation) on y = bf16(min(max(f32(zin) scale + shift, lo),
+    hi)) - bn_clamp_fwd's value of ``zin`` (bf16 [n, h, w, c]) and ``saved`` (f32 [4, c]), zero outside the map - without writing y:
+    bit-equal to dwconv3x3 on the materialised y."""
+    _need_cuda(zin, saved, w9c, z)
+    n, h, w, c = zin.shape
+    _nhwc(zin, (n, h, w, c), "dwconv3x3_bnin_fwd: zin")
+    _nhwc(z, (n,) + _dw_out(h, w, stride) + (c,), "dwconv3x3_bnin_fwd: z")
+    _nhwc(w9c, (9, c), "dwconv3x3_bnin_fwd: w9c", torch.float32)
+    _bn_vec(saved, c, "dwconv3x3_bnin_fwd: saved", 4)
+    check(load().yolo_dwconv3x3_bnin_fwd(_ptr(zin), _ptr(saved), float(lo), float(hi), _ptr(w9c), _ptr(z), n, h, w, c, int(stride),
+                                         stream_ptr()), "dwconv3x3_bnin_fwd")
+    return z
+
+
+def dwconv3x3_bnin_bwd_weight(zin, saved, lo, hi, g, dw, workspace, stride):
+    """dwconv3x3_bwd_weight on the same y of ``zin`` and ``saved`` as dwconv3x3_bnin_fwd, without writing it: bit-equal to
+    dwconv3x3_bwd_weight on the materialised y; workspace and pick are dwconv3x3_bwd_weight's."""
+    _need_cuda(zin, saved, g, dw, workspace)
+    n, h, w, c = zin.shape
+    _nhwc(zin, (n, h, w, c), "dwconv3x3_bnin_bwd_weight: zin")
+    _nhwc(g, (n,) + _dw_out(h, w, stride) + (c,), "dwconv3x3_bnin_bwd_weight: g")
+    _bn_vec(saved, c, "dwconv3x3_bnin_bwd_weight: saved", 4)
+    if dw.dtype != torch.float32 or not dw.is_contiguous() or dw.numel() != 9 * c:
+        raise RuntimeError("dwconv3x3_bnin_bwd_weight: dw must be contiguous float32 [c, 1, 3, 3]")
+    check(load().yolo_dwconv3x3_bnin_bwd_weight(_ptr(zin), _ptr(saved), float(lo), float(hi), _ptr(g), _ptr(dw), _ptr(workspace),
+                                                workspace.numel() * workspace.element_size(), n, h, w, c, int(stride), stream_ptr()),
+          "dwconv3x3_bnin_bwd_weight")
     return dw
 
 

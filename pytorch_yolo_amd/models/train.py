@@ -1,6 +1,6 @@
-"""Training-mode forward of the Darknet-53 models (YOLOv3, YOLOv3-SPP), of the max-pool models (YOLOv3-tiny, LiteYOLOv3) and of
-YOLOv3-tiny/SqueezeNet: the reference's ``model.train()(x)`` - batch-statistics BN, the raw ``p`` list with a ``grad_fn`` - wired from the
-differentiable ops of pytorch_yolo_amd.ops (DESIGN.md 3.6f, 3.6g, 3.6i).
+"""Training-mode forward of the Darknet-53 models (YOLOv3, YOLOv3-SPP), of the max-pool models (YOLOv3-tiny, LiteYOLOv3), of
+YOLOv3-tiny/SqueezeNet and of YOLOv3-tiny/MobileNetV2: the reference's ``model.train()(x)`` - batch-statistics BN, the raw ``p`` list with a ``grad_fn`` - wired from the
+differentiable ops of pytorch_yolo_amd.ops (DESIGN.md 3.6f, 3.6g, 3.6i, 3.6k).
 
 A model states its layer graph once, in ``_trace``.  For inference graph.Recorder records it; for training ``wiring`` (every trainable
 class's ``_train_wiring``) runs the same ``_trace`` through a ``TrainTracer``, which has the Recorder's method names and runs each call at
@@ -10,11 +10,15 @@ GPU.  A table function has the signature of the op it stands for.  ``DEVICE_OPS`
 ``DEVICE_OPS_POOL`` adds ``max_pool`` and ``pool_bn_block`` and is the table ``forward_train`` runs by default (the ``up_first`` keyword
 of ``upsample_concat`` goes through both).  ``DEVICE_OPS_FIRE`` adds ``stem_block``, ``fire_block``, ``max_pool_ceil`` and a ``concat``:
 the table of YOLOv3-tiny/SqueezeNet, whose ``_trace`` runs through ``FireTracer`` - a model names its tracer class in ``_train_tracer``
-and its default table in ``_train_ops``.
+and its default table in ``_train_ops``.  ``DEVICE_OPS_MOBILE`` (``mobile_ops()``) adds ``conv_bn_relu6_block``, ``dw_bn_block``,
+``project_bn_block`` and ``expand_dw_bn_block`` to the pool table: the table of YOLOv3-tiny/MobileNetV2, whose ``_trace`` runs through
+``MobileTracer``.
 
 ``forward_train(model, x)`` is the public entry for all five classes.  ``model.train()(x)`` delegates to it for the classes whose
 ``_train_in_forward`` is True (YOLOv3, YOLOv3-SPP); YOLOv3-tiny and LiteYOLOv3 keep raising from the module call and train through the
-function (DESIGN.md 3.6g says why: flipping their switch is a one-line change).
+function (DESIGN.md 3.6g says why: flipping their switch is a one-line change).  YOLOv3-tiny/MobileNetV2 is opt-in one step further: its
+class sets ``_train_ops_by_name``, and it trains through ``forward_train(model, x, ops=DEVICE_OPS_MOBILE)`` only - without the table the
+call raises what it raised before the class had a wiring.
 """
 from __future__ import annotations
 
@@ -39,6 +43,26 @@ def _concat(xs):
 
 DEVICE_OPS_FIRE = SimpleNamespace(**vars(DEVICE_OPS_POOL), stem_block=_ops.stem_block, fire_block=_ops.fire_block,
                                   max_pool_ceil=_ops.max_pool_ceil, concat=_concat)
+
+
+def _composed_expand_dw(x, w_expand, gamma1, beta1, running_mean1, running_var1, w_dw, gamma2, beta2, running_mean2, running_var2, *,
+                        stride=1, momentum=0.1, eps=1e-5, training=True):
+    """``expand_dw_bn_block`` as the two ops it fuses: what ``mobile_ops(fused=False)`` puts under that name."""
+    (m1, m2), (e1, e2) = (v if isinstance(v, (tuple, list)) else (v, v) for v in (momentum, eps))
+    y1 = _ops.conv_bn_relu6_block(x, w_expand, gamma1, beta1, running_mean1, running_var1, momentum=m1, eps=e1, training=training)
+    return _ops.dw_bn_block(y1, w_dw, gamma2, beta2, running_mean2, running_var2, stride=stride, momentum=m2, eps=e2, training=training)
+
+
+def mobile_ops(fused=True):
+    """The table of YOLOv3-tiny/MobileNetV2: the pool table's functions plus the three ops of an inverted residual and, under the name
+    ``expand_dw_bn_block``, the fused expand + depthwise op - or, with ``fused=False``, the two-op composition it is bit-equal to (the
+    form the timings and the tests compare it with)."""
+    return SimpleNamespace(**vars(DEVICE_OPS_POOL), conv_bn_relu6_block=_ops.conv_bn_relu6_block, dw_bn_block=_ops.dw_bn_block,
+                           project_bn_block=_ops.project_bn_block,
+                           expand_dw_bn_block=_ops.expand_dw_bn_block if fused else _composed_expand_dw)
+
+
+DEVICE_OPS_MOBILE = mobile_ops()
 
 
 def conv_bn(ops, block, x, residual=None, want_preadd=False):
@@ -129,6 +153,38 @@ class FireTracer(TrainTracer):
         return self.ops.concat(xs)
 
 
+def _bn_args(bn):
+    """A BatchNorm2d's tensors in an op's order; the call counts in num_batches_tracked, as conv_bn's does."""
+    with torch.no_grad():
+        bn.num_batches_tracked += 1
+    return bn.weight, bn.bias, bn.running_mean, bn.running_var
+
+
+class MobileTracer(TrainTracer):
+    """TrainTracer plus what YOLOv3-tiny/MobileNetV2's ``_trace`` calls: graph.Recorder's ``conv_bn_relu6`` and ``inverted_residual``.  The
+    ops take the modules' own parameters and each BatchNorm2d's own momentum and eps (the Recorder's side of the same methods folds
+    detached copies)."""
+
+    def conv_bn_relu6(self, module, x):
+        conv, bn = module[0], module[1]
+        kw = dict(stride=module.stride, momentum=bn.momentum, eps=bn.eps)
+        if module.depthwise:
+            return self.ops.dw_bn_block(x, conv.weight, *_bn_args(bn), **kw)
+        return self.ops.conv_bn_relu6_block(x, conv.weight, *_bn_args(bn), **kw)
+
+    def inverted_residual(self, block, x):
+        layers = list(block.conv)
+        if len(layers) == 4:                                             # the block expands: expand + depthwise as one op
+            (ce, be, _), (cd, bd, _) = layers[0], layers[1]
+            y = self.ops.expand_dw_bn_block(x, ce.weight, *_bn_args(be), cd.weight, *_bn_args(bd), stride=layers[1].stride,
+                                            momentum=(be.momentum, bd.momentum), eps=(be.eps, bd.eps))
+        else:
+            y = self.conv_bn_relu6(layers[0], x)
+        conv, bn = layers[-2], layers[-1]
+        return self.ops.project_bn_block(y, conv.weight, *_bn_args(bn), residual=x if block.use_res_connect else None,
+                                         momentum=bn.momentum, eps=bn.eps)
+
+
 def wiring(model, ops, x):
     """``model._train_wiring``: the raw head maps [bs, 3 (5 + nc), ny, nx] of ``model._trace`` run on the ops of a table, through the
     tracer class the model names (``_train_tracer``; TrainTracer without one)."""
@@ -140,8 +196,10 @@ def wiring(model, ops, x):
 def forward_train(model, x, ops=None):
     """``[p1, p2, p3]`` (``[p1, p2]`` for YOLOv3-tiny), each ``[bs, 3, ny, nx, 5 + nc]`` contiguous with a grad_fn, as the reference's
     training-mode forward returns.  With the default table: float32 on the device; x float32 NCHW, H and W multiples of 32 (YOLOv3-tiny:
-    at least 64), bf16 mode, BN not fused."""
-    if not hasattr(model, "_train_wiring"):
+    at least 64), bf16 mode, BN not fused.  YOLOv3-tiny/MobileNetV2 has no default: ``ops=DEVICE_OPS_MOBILE`` runs it on the device under
+    the same checks, ``ops=None`` raises NotImplementedError."""
+    by_name = getattr(model, "_train_ops_by_name", False)                # the class trains only with its table named by the caller
+    if not hasattr(model, "_train_wiring") or (by_name and ops is None):
         raise NotImplementedError(
             "training-mode forward (batch-statistics BN, raw p list) is outside the inference hot path; "
             "call .eval() first")
@@ -158,7 +216,7 @@ def forward_train(model, x, ops=None):
         raise ValueError(f"the training-mode forward of {type(model).__name__} needs H and W of at least {min_size}, got "
                          f"{tuple(x.shape[2:])}: on a smaller input its stride-1 max-pool sees a 1x1 map, whose window is all padding "
                          "(the reference itself returns -inf there)")
-    if ops is None:
+    if ops is None or (by_name and ops is model._train_ops):
         if x.dtype != torch.float32:
             raise ValueError(f"the training-mode forward takes a float32 NCHW batch, got {x.dtype}")
         if not x.is_cuda:

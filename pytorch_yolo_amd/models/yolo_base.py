@@ -224,7 +224,7 @@ class YOLOBase(nn.Module):
         (yolov3_spp.py:141-164, yolov3_tiny.py:79-100).  training (YOLOv3 and YOLOv3-SPP, the classes with a ``_train_wiring`` whose
         ``_train_in_forward`` is set; every other class raises): the raw list [p_k] with a grad_fn (models/train.py)."""
         if self.training:
-            if not self._train_in_forward:
+            if not self._train_in_forward and not getattr(self, "_train_ops_by_name", False):   # (by name: forward_train refuses, as before)
                 raise NotImplementedError(
                     "training-mode forward through the module call is switched off for this class: call "
                     "pytorch_yolo_amd.forward_train(model, x), or .eval() first")

@@ -11,6 +11,8 @@ The ops (contracts in their docstrings; the kernels in DESIGN.md 3.6c-g):
                                     (DESIGN.md 3.6i); ``conv_block(act="relu")`` is its plain conv
     conv_bn_relu6_block, dw_bn_block, project_bn_block   MobileNetV2's inverted residual: the dense ConvBNReLU (expand, first and last
                                     layer), the depthwise ConvBNReLU and the linear bottleneck with its add
+    expand_dw_bn_block              the expand and the depthwise ConvBNReLU of an expanding inverted residual as one op: bit-equal to
+                                    dw_bn_block(conv_bn_relu6_block(..)), the hidden activation never written
 models/train.py wires the training-mode forward of the models from them; the models' eval forward stays inference-only.
 
 The structure - every launch has one owner:
@@ -31,6 +33,8 @@ The structure - every launch has one owner:
     _MaxPoolCeilFunction                max_pool_ceil (csrc/fire_train.hip)
     _DwBnFunction                       dw_bn_block:  _dw_forward (dwconv3x3, bn_train_stats, _bn_act) / _bn_grads, dwconv3x3_bwd_data,
                                         dwconv3x3_bwd_weight (csrc/dw_train.hip)
+    _ExpandDwBnFunction                 expand_dw_bn_block:  _conv_stats, dwconv3x3_bnin_fwd, bn_train_stats, _bn_act / _bn_grads,
+                                        dwconv3x3_bwd_data, dwconv3x3_bnin_bwd_weight, _bn_grads, _conv_grads
     _ProjectBnFunction                  project_bn_block with a residual:  _conv_stats, bn_add_rounded_fwd / _bn_grads, _conv_grads;
                                         dy passes through to the residual.  Without one it is _ConvBnFunction
     _check_conv, _check_bn, _need_device    the argument checks: every ValueError, then the RuntimeError, then the first allocation
@@ -45,7 +49,8 @@ from . import kernels as K
 from ._lib import ACT_LEAKY01, ACT_NONE, ACT_RELU, DT_BF16, DT_F32
 
 __all__ = ["conv_block", "conv_bn_block", "down_block", "down_bn_block", "res_bn_block", "spp_concat", "upsample_concat", "max_pool",
-           "pool_bn_block", "stem_block", "fire_block", "max_pool_ceil", "conv_bn_relu6_block", "dw_bn_block", "project_bn_block"]
+           "pool_bn_block", "stem_block", "fire_block", "max_pool_ceil", "conv_bn_relu6_block", "dw_bn_block", "project_bn_block",
+           "expand_dw_bn_block"]
 
 _ACTS = {"leaky": ACT_LEAKY01, "none": ACT_NONE}
 _ACTS_RELU = {**_ACTS, "relu": ACT_RELU}          # the ops without a batch norm at stride 1, and the unpadded first layer
@@ -928,3 +933,110 @@ def project_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None
                       ACT_NONE, 1, 0)
     return _apply(_ProjectBnFunction, _project_forward, (x, weight, gamma.contiguous(), beta.contiguous(), _dense_bf16(residual)), running,
                   float(momentum), float(eps))
+
+
+# ---- the expand + depthwise pair of an expanding inverted residual as one op: the hidden activation is never written ------
+def _expand_dw_forward(x, w_expand, gamma1, beta1, w_dw, gamma2, beta2, running1, running2, momentum1, eps1, momentum2, eps2, stride):
+    """_conv_stats of the expand conv, the depthwise conv on its batch-normed and clamped output (yolo_dwconv3x3_bnin_fwd: the operand is
+    transformed as it is loaded), the statistics of that conv's output and the normalise-and-clamp pass.  Returns the NCHW-shaped result
+    and what the backward keeps: the expand conv's descriptor, z1, saved1, the [9, c] weight, z2 and saved2."""
+    z1, d, saved1 = _conv_stats(x, w_expand, gamma1, beta1, running1, momentum1, eps1)
+    n, h, w, c = z1.shape
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    with torch.cuda.device(x.device):
+        w9c = w_dw.detach().to(torch.bfloat16).to(torch.float32).reshape(c, 9).t().contiguous()
+        z2 = torch.empty((n, ho, wo, c), dtype=torch.bfloat16, device=x.device)
+        K.dwconv3x3_bnin_fwd(z1, saved1, _RELU6[0], _RELU6[1], w9c, z2, stride)
+        saved2 = torch.empty((4, c), dtype=torch.float32, device=x.device)
+        ws = torch.empty((K.bn_workspace_bytes(n * ho * wo, c),), dtype=torch.uint8, device=x.device)
+        K.bn_train_stats(z2, gamma2, beta2, eps2, momentum2, running2[0], running2[1], saved2, ws)
+        y = _bn_act(z2, saved2, _RELU6)
+    return y.permute(0, 3, 1, 2), d, z1, saved1, w9c, z2, saved2
+
+
+class _ExpandDwBnFunction(torch.autograd.Function):
+    """_expand_dw_forward with a backward: _bn_grads on z2, the depthwise data gradient, the depthwise weight gradient on the transformed
+    z1 (yolo_dwconv3x3_bnin_bwd_weight), _bn_grads (clamp) on z1, _conv_grads; each only where asked.  x, the expand weight, z1, saved1,
+    the [9, c] weight, z2 and saved2 are kept; y1, the activation between the convs, is neither written nor kept."""
+
+    @staticmethod
+    def forward(ctx, x, w_expand, gamma1, beta1, w_dw, gamma2, beta2, running1, running2, momentum1, eps1, momentum2, eps2, stride):
+        out, ctx.desc, z1, saved1, w9c, z2, saved2 = _expand_dw_forward(x, w_expand, gamma1.detach(), beta1.detach(), w_dw, gamma2.detach(),
+                                                                        beta2.detach(), running1, running2, momentum1, eps1, momentum2,
+                                                                        eps2, stride)
+        ctx.stride = stride
+        ctx.save_for_backward(x, w_expand, z1, saved1, w9c, z2, saved2)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w_expand, z1, saved1, w9c, z2, saved2 = ctx.saved_tensors
+        need_x, need_we, need_g1, need_b1, need_wd, need_g2, need_b2 = ctx.needs_input_grad[:7]
+        need_y1 = need_x or need_we or need_g1 or need_b1               # what dw_bn_block's x would ask for
+        dx = dwe = dgamma1 = dbeta1 = dwd = None
+        with torch.cuda.device(x.device):
+            g2, dgamma2, dbeta2 = _bn_grads(dy, z2, saved2, _RELU6, need_y1, need_wd, need_g2, need_b2)
+            n, h, w, c = z1.shape
+            if need_y1:
+                d1 = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=x.device)
+                K.dwconv3x3_bwd_data(g2, w9c, d1, ctx.stride)
+            if need_wd:
+                dwd = torch.empty((c, 1, 3, 3), dtype=torch.float32, device=x.device)
+                ws = torch.empty((K.dwconv3x3_bwd_weight_workspace_bytes(n, h, w, c, ctx.stride),), dtype=torch.uint8, device=x.device)
+                K.dwconv3x3_bnin_bwd_weight(z1, saved1, _RELU6[0], _RELU6[1], g2, dwd, ws, ctx.stride)
+            if need_y1:
+                g1, dgamma1, dbeta1 = _bn_grads(d1.permute(0, 3, 1, 2), z1, saved1, _RELU6, need_x, need_we, need_g1, need_b1)
+                dx, dwe, _ = _conv_grads(x, w_expand, g1, ctx.desc, need_x, need_we, False)
+        return (dx, dwe, dgamma1, dbeta1, dwd, dgamma2, dbeta2) + (None,) * 7
+
+
+def _pair(name, what, v):
+    """``v`` as (the expand's, the depthwise's): a number for both, or a pair."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError(f"{name}: {what} must be a number or a pair (expand's, depthwise's), not {v!r}")
+        return v[0], v[1]
+    return v, v
+
+
+def expand_dw_bn_block(x, w_expand, gamma1, beta1, running_mean1, running_var1, w_dw, gamma2, beta2, running_mean2, running_var2, *,
+                       stride=1, momentum=0.1, eps=1e-5, training=True):
+    """``dw_bn_block(conv_bn_relu6_block(x, w_expand, gamma1, beta1, running_mean1, running_var1), w_dw, gamma2, beta2, running_mean2,
+    running_var2, stride=stride)`` on the device as one op, differentiable once: the expand and the depthwise ConvBNReLU of an expanding
+    inverted residual.  Bit-equal to that composition - the output, the seven gradients and the four running tensors.
+
+    The hidden activation ``y1 = relu6(batch_norm(z1))`` between the two convs is never written: the depthwise conv reads the expand conv's
+    output z1 and normalises and clamps it as it loads it (yolo_dwconv3x3_bnin_fwd; the padding is a zero of y1), and so does the depthwise
+    weight gradient (yolo_dwconv3x3_bnin_bwd_weight).  One launch and one hidden map kept for the backward less than the composition.
+
+    x           [n, cin, h, w]; converted as in conv_block.
+    w_expand    float32 [hidden, cin, 1, 1], ``hidden % 8 == 0``.      w_dw  float32 [hidden, 1, 3, 3].
+    gamma1, beta1, running_mean1, running_var1      the expand's BatchNorm2d, float32 [hidden]; the running tensors may be None.
+    gamma2, beta2, running_mean2, running_var2      the depthwise's.
+    stride      the depthwise conv's, 1 or 2.
+    momentum, eps   a number for both batch norms, or a pair (the expand's, the depthwise's).
+    ``training=True`` only (anything else raises ValueError).  Returns an NCHW-shaped channels-last bfloat16 tensor
+    [n, hidden, ho, wo].  Gradients: x bf16, the weights, gammas and betas float32, each computed only where asked; two runs give the same
+    bits.  Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no CPU fallback)."""
+    name = "expand_dw_bn_block"
+    _check_conv(name, x, w_expand, None, "none", (1,), True)
+    if isinstance(stride, bool) or stride not in (1, 2):
+        raise ValueError(f"{name}: stride {stride!r} unsupported (1 or 2)")
+    if not training:
+        raise ValueError(f"{name}: training=True only (the frozen layer is the models' inference path)")
+    hidden = w_expand.shape[0]
+    if not isinstance(w_dw, torch.Tensor) or tuple(w_dw.shape) != (hidden, 1, 3, 3):
+        raise ValueError(f"{name}: w_dw must be [hidden, 1, 3, 3] with hidden = {hidden} (a 3x3 depthwise conv), not "
+                         f"{list(getattr(w_dw, 'shape', ()))}")
+    if w_dw.dtype != torch.float32:
+        raise ValueError(f"{name}: w_dw must be float32 [hidden, 1, 3, 3]")
+    (momentum1, momentum2), (eps1, eps2) = _pair(name, "momentum", momentum), _pair(name, "eps", eps)
+    running1 = _check_bn(name, x, w_expand, 1, gamma1, beta1, running_mean1, running_var1, True, momentum1, eps1)
+    hidden_map = torch.empty((x.shape[0], hidden, x.shape[2], x.shape[3]), device="meta")        # (shape only: the depthwise conv's input)
+    running2 = _check_bn(name, hidden_map, w_dw, stride, gamma2, beta2, running_mean2, running_var2, True, momentum2, eps2)
+    _need_device(name, x, w_expand, gamma1, beta1, running_mean1, running_var1, w_dw, gamma2, beta2, running_mean2, running_var2)
+    x, w_expand = _to_kernel_layout(x, w_expand)
+    return _apply(_ExpandDwBnFunction, _expand_dw_forward,
+                  (x, w_expand, gamma1.contiguous(), beta1.contiguous(), w_dw.contiguous(), gamma2.contiguous(), beta2.contiguous()),
+                  running1, running2, float(momentum1), float(eps1), float(momentum2), float(eps2), int(stride))
