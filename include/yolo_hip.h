@@ -384,6 +384,33 @@ YOLO_API int yolo_dwconv3x3_bnin_fwd(const void* zin, const float* saved_in, flo
 YOLO_API int yolo_dwconv3x3_bnin_bwd_weight(const void* zin, const float* saved_in, float lo, float hi, const void* g, float* dw, void* ws,
                                             size_t ws_bytes, int n, int h, int w_, int c, int stride, yolo_stream_t s);
 
+/* ---- The layers of a training step of YOLOv3-tiny/ShuffleNetV2 that are no conv (models/yolov3_tiny_shuffle.py), bf16 mode:
+ *  csrc/shuffle_train.hip, DESIGN.md 3.6l.  The conventions of the blocks above: bf16 NHWC, every physical channel count % 8 == 0, a
+ *  thread per 8-channel chunk of a pixel, no atomics, no LDS, no workspace, every output element written exactly once, every fp32 sum in a
+ *  fixed order, no contraction; two runs give the same bits.  The dense ConvBNReLU needs no entry: yolo_bn_clamp_fwd / _bwd with lo 0 and
+ *  hi +inf are ReLU.
+ *  yolo_maxpool3s2p1_train_fwd: y [n,ho,wo,c] = MaxPool2d(3, 2, padding=1)(x) of the dense x [n,h,w,c]: ho = (h - 1) / 2 + 1, wo likewise;
+ *    any h, w >= 1.  Tap 3i + j of the window at (oy, ox) is the pixel (2oy - 1 + i, 2ox - 1 + j); a tap outside the map is never a
+ *    candidate (it acts as -inf, not as 0: a map of negative values pools to negative values); tap 4, the centre, is always inside.  idx
+ *    (uint8, y's shape) is the tap number 0..8 of the window's FIRST maximum among its in-bounds taps in row-major order: a later tap
+ *    replaces the running maximum only when strictly greater (torch's rule, yolo_maxpool3s2_train_fwd's).  A NaN is never greater.
+ *  yolo_maxpool3s2p1_bwd: dx [n,h,w,c], every element written, from dy and idx (y's shape), as a gather: pixel (py, px) can sit in the
+ *    windows oy in [ceil((py - 1) / 2), floor((py + 1) / 2)] and [0, ho), ox likewise - at most four.  acc = 0; for those windows in
+ *    row-major (oy, ox) order: acc = acc + f32(dy[q]) where idx[q] == 3 (py - 2oy + 1) + (px - 2ox + 1); dx = bf16_rne(acc).
+ *  yolo_channel_shuffle2_bwd: the inverse of yolo_channel_shuffle2_fwd on its two-slot layout.  dy, da and db are channel views
+ *    (c_total, c_offset) of NHWC buffers: dy 2 c_slot channels wide, da and db c_slot.  Logical channel j of dy (j < 2 half) sits at
+ *    physical (j / half) c_slot + j % half.  For q < half: da[q] = dy_logical[2q], db[q] = dy_logical[2q + 1]; the channels [half, c_slot)
+ *    of da and db are written as zero; the pad channels of dy are never read.  Any 1 <= half <= c_slot, c_slot % 8 == 0; dy is read one
+ *    channel at a time (any view inside its buffer), the views of da and db start and end on 8 channels.  da or db may be null: that
+ *    output is not written (not both).
+ *  YOLO_E_ARG before any launch for an empty shape, a channel count that is no positive multiple of 8, half outside [1, c_slot], a view
+ *  that leaves its buffer or (da, db) is not 8-channel aligned, a null or misaligned pointer (the maps: 16 bytes; idx: 8; dy of the
+ *  shuffle: 2). */
+YOLO_API int yolo_maxpool3s2p1_train_fwd(const void* x, void* y, void* idx, int n, int h, int w, int c, yolo_stream_t s);
+YOLO_API int yolo_maxpool3s2p1_bwd(const void* dy, const void* idx, void* dx, int n, int h, int w, int c, yolo_stream_t s);
+YOLO_API int yolo_channel_shuffle2_bwd(const void* dy, void* da, void* db, int n, int h, int w, int half, int c_slot, int dy_c_total,
+                                       int dy_c_offset, int da_c_total, int da_c_offset, int db_c_total, int db_c_offset, yolo_stream_t s);
+
 /* First layer fused with the input packing: x is the caller's f32 NCHW batch [n,cin_real,h,w] (cin_real <= 8),
  * w_packed / bias as for yolo_conv2d_fwd with d->cin = 8; 3x3 / pad 1, bf16 NHWC output: stride 1 with cout 16 or 32
  * (Darknet), or stride 2 with cout 32 (MobileNetV2's first layer). */

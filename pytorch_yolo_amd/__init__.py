@@ -27,10 +27,10 @@ if "GPU_MAX_HW_QUEUES" not in _os.environ:
 
 from .models import (LiteYOLOv3, YOLOv3, YOLOv3SPP, YOLOv3Tiny, YOLOv3TinyEfficient, YOLOv3TinyMobile, YOLOv3TinyShuffle,
                      YOLOv3TinySqueeze)
-from .models.train import DEVICE_OPS_MOBILE, forward_train
-from .ops import (conv_block, conv_bn_block, conv_bn_relu6_block, down_block, down_bn_block, dw_bn_block, expand_dw_bn_block, fire_block, max_pool,
-                  max_pool_ceil,
-                  pool_bn_block, project_bn_block, res_bn_block, spp_concat, stem_block, upsample_concat)
+from .models.train import DEVICE_OPS_MOBILE, DEVICE_OPS_SHUFFLE, forward_train
+from .ops import (channel_shuffle2, conv_block, conv_bn_block, conv_bn_relu6_block, conv_bn_relu_block, down_block, down_bn_block, dw_bn_block, expand_dw_bn_block, fire_block, max_pool,
+                  max_pool_321, max_pool_ceil,
+                  pool_bn_block, project_bn_block, res_bn_block, shuffle_unit_block, spp_concat, stem_block, upsample_concat)
 from .utils.coco_eval import coco_eval
 from .utils.utils import (bbox_iou, bench_results, build_targets, compute_loss, loss_grad_raw, non_max_suppression, test_model,
                           wh_iou, xyxy2xywh)
@@ -39,4 +39,5 @@ __all__ = ["YOLOv3SPP", "YOLOv3Tiny", "YOLOv3TinyMobile", "YOLOv3TinySqueeze", "
            "compute_loss", "loss_grad_raw", "build_targets", "wh_iou", "bbox_iou", "xyxy2xywh", "bench_results", "test_model", "coco_eval",
            "conv_block", "conv_bn_block", "down_block", "down_bn_block", "res_bn_block", "spp_concat", "upsample_concat",
            "max_pool", "pool_bn_block", "stem_block", "fire_block", "max_pool_ceil", "forward_train",
-           "conv_bn_relu6_block", "dw_bn_block", "project_bn_block", "expand_dw_bn_block", "DEVICE_OPS_MOBILE"]
+           "conv_bn_relu6_block", "dw_bn_block", "project_bn_block", "expand_dw_bn_block", "DEVICE_OPS_MOBILE",
+           "conv_bn_relu_block", "max_pool_321", "channel_shuffle2", "shuffle_unit_block", "DEVICE_OPS_SHUFFLE"]

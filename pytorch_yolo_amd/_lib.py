@@ -119,6 +119,9 @@ SIGNATURES = {
     "yolo_dwconv3x3_bnin_fwd": (C.c_int, [C.c_void_p] * 2 + [C.c_float] * 2 + [C.c_void_p] * 2 + [C.c_int] * 5 + [C.c_void_p]),
     "yolo_dwconv3x3_bnin_bwd_weight": (C.c_int, [C.c_void_p] * 2 + [C.c_float] * 2 + [C.c_void_p] * 3 + [C.c_size_t] + [C.c_int] * 5 +
                                        [C.c_void_p]),
+    "yolo_maxpool3s2p1_train_fwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    "yolo_maxpool3s2p1_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    "yolo_channel_shuffle2_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 11 + [C.c_void_p]),
     "yolo_pack_conv_weight_dev": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
     "yolo_conv1_nchw_f32_fwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.POINTER(YoloConvDesc), C.c_void_p]),

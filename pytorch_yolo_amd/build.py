@@ -43,6 +43,7 @@ SOURCES = {
     "pool_train.hip": ["-ffp-contract=off"],
     "fire_train.hip": ["-ffp-contract=off"],
     "dw_train.hip": ["-ffp-contract=off"],
+    "shuffle_train.hip": ["-ffp-contract=off"],
 }
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden",
           "-Wall", "-Wno-unused-function"]

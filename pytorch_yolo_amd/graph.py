@@ -14,6 +14,34 @@ from . import kernels as K
 from .utils.torch_utils import fold_conv_bn
 
 
+SHUFFLE_SLOT = 32     # ShuffleNetV2's slot granule: 8 channels would do for the views; 32 keeps every 1x1 / 3x3 conv on the LDS-DMA fast path
+
+
+def shuffle_slot(half: int) -> int:
+    """Physical channels of the slot that holds ``half`` logical channels of a ShuffleNetV2 unit (58 / 116 / 232 -> 64 / 128 / 256)."""
+    return K.roundup(half, SHUFFLE_SLOT)
+
+
+def _fold(conv, bn):
+    return fold_conv_bn(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+
+
+def scatter_weight(wb, out_map, out_phys, in_map=None, in_phys=None):
+    """Logical folded (weight OIHW, bias) -> the same conv in physical channels: row o goes to out_map[o], input channel i (full convs
+    only) to in_map[i]; everything else is zero."""
+    w, b = wb
+    cout, cin, k, _ = w.shape
+    if in_map is None:                                      # depthwise: [c, 1, 3, 3]
+        wp = torch.zeros((out_phys, 1, k, k), dtype=torch.float32)
+        wp[out_map] = w
+    else:
+        wp = torch.zeros((out_phys, in_phys, k, k), dtype=torch.float32)
+        wp[torch.as_tensor(out_map)[:, None], torch.as_tensor(in_map)[None, :]] = w
+    bp = torch.zeros(out_phys, dtype=torch.float32)
+    bp[out_map] = b
+    return wp, bp
+
+
 @dataclass(eq=False)
 class Sym:
     """A logical NHWC activation."""
@@ -28,6 +56,11 @@ class Sym:
     buf: Optional["Buf"] = None
     c_offset: int = 0
     consumers: List["Node"] = field(default_factory=list)
+
+    @property
+    def shape(self):
+        """(n, c, h, w): what the tensor in its place has under models/train.TrainTracer, so a ``_trace`` can ask either for its channels."""
+        return self.n, self.c, self.h, self.w
 
 
 @dataclass(eq=False)
@@ -157,6 +190,42 @@ class Recorder:
         conv, bn = block.conv[-2], block.conv[-1]
         proj = fold_conv_bn(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
         return self.conv(y, proj, stride=1, act="none", residual=x if block.use_res_connect else None)
+
+    # ShuffleNetV2's layers (models/yolov3_tiny_shuffle.py) in the padded physical space of that module's docstring; with
+    # maxpool(3, 2) they are what models/train.ShuffleTracer adds to the trainable vocabulary.  ``in_map[i]`` is the physical channel of
+    # x that holds logical input channel i.
+    def conv_bn_relu(self, module, x: Sym, in_map, out_phys):
+        """Conv2d(bias=False) -> BatchNorm2d -> ReLU with its BN folded, dense: the cout logical outputs in [0, cout) of ``out_phys``."""
+        conv, bn = module[0], module[1]
+        in_phys = len(in_map) if x is self.input else x.c               # (the first layer's weight keeps the image's channel count)
+        w = scatter_weight(_fold(conv, bn), list(range(conv.out_channels)), out_phys, in_map, in_phys)
+        return self.conv(x, w, stride=conv.stride[0], act="relu")
+
+    def shuffle_unit(self, unit, x: Sym, in_map):
+        """A ShuffleNetV2 unit: at stride 1 ``shuffle(cat(x1, branch2(x2)))`` with ``x.chunk(2)`` as the two slot views of x, at stride 2
+        ``shuffle(cat(branch1(x), branch2(x)))``.  Returns (y, the map of y): two slots of ``shuffle_slot(half)`` channels."""
+        h, hp = unit.bf, shuffle_slot(unit.bf)
+        rows = list(range(h))
+
+        def branch2(t, t_map):
+            b2 = unit.branch2
+            u = self.conv(t, scatter_weight(_fold(b2[0], b2[1]), rows, hp, t_map, t.c), act="relu")
+            v = self.dwconv(u, scatter_weight(_fold(b2[3], b2[4]), rows, hp), stride=unit.stride, act="none")
+            return self.conv(v, scatter_weight(_fold(b2[5], b2[6]), rows, hp, rows, hp), act="relu")
+        if unit.stride > 1:
+            b1 = unit.branch1
+            t = self.dwconv(x, scatter_weight(_fold(b1[0], b1[1]), in_map, x.c), stride=unit.stride, act="none")
+            a = self.conv(t, scatter_weight(_fold(b1[2], b1[3]), rows, hp, in_map, x.c), act="relu")
+            b = branch2(x, in_map)
+        else:
+            a = self.slice(x, 0, hp)                                     # x.chunk(2): the two slots
+            b = branch2(self.slice(x, hp, hp), rows)
+        return self.shuffle2(a, b, h), rows + [hp + i for i in rows]
+
+    def conv_block_mapped(self, block, x: Sym, in_map):
+        """A ConvBlock whose logical input channels sit at ``in_map`` of a wider physical x (the head conv on cat(route1, up))."""
+        cout = block.out_channels
+        return self.conv(x, scatter_weight(block.folded(), list(range(cout)), cout, in_map, x.c), act="leaky")
 
     def dwconv(self, x: Sym, weight, stride=1, act="relu6", tf_same=False):
         """Depthwise k x k conv.  Default: 3x3 / pad 1 (MobileNetV2).  ``tf_same``: k = 3 or 5 with TensorFlow "same" padding

@@ -24,7 +24,8 @@ __all__ = ["stream_ptr", "pack_input", "conv2d", "conv2d_pick", "head_decode_pic
            "maxpool3s2_train_fwd", "maxpool3s2_bwd", "fire_bwd_split", "fire_bwd_join",
            "conv2d_stem_bwd_workspace_bytes", "conv2d_stem_bwd_pick", "conv2d_stem_bwd_weight",
            "bn_clamp_fwd", "bn_clamp_bwd", "bn_add_rounded_fwd", "dwconv3x3_bwd_data", "dwconv3x3_bwd_weight_workspace_bytes", "dwconv3x3_bwd_weight_pick",
-           "dwconv3x3_bwd_weight", "dwconv3x3_bnin_fwd", "dwconv3x3_bnin_bwd_weight"]
+           "dwconv3x3_bwd_weight", "dwconv3x3_bnin_fwd", "dwconv3x3_bnin_bwd_weight",
+           "maxpool3s2p1_train_fwd", "maxpool3s2p1_bwd", "channel_shuffle2_fwd", "channel_shuffle2_bwd"]
 
 
 def roundup(v: int, m: int) -> int:
@@ -879,6 +880,91 @@ def dwconv3x3_bnin_bwd_weight(zin, saved, lo, hi, g, dw, workspace, stride):
                                                 workspace.numel() * workspace.element_size(), n, h, w, c, int(stride), stream_ptr()),
           "dwconv3x3_bnin_bwd_weight")
     return dw
+
+
+# ---- the layers of a training step of YOLOv3-tiny/ShuffleNetV2 that are no conv (csrc/shuffle_train.hip, and the forward shuffle of
+# csrc/pointwise.hip) ---------------------------------------------------------------------------------------------------
+def _pool321_out(h, w):
+    return (h - 1) // 2 + 1, (w - 1) // 2 + 1
+
+
+def maxpool3s2p1_train_fwd(x, y, idx):
+    """y [n,ho,wo,c] = MaxPool2d(3, 2, padding=1)(x) of the dense bf16 x [n,h,w,c], ho = (h - 1) // 2 + 1; the taps outside the map are no
+    candidates (-inf).  idx uint8 of y's shape: the tap 3i + j (0..8) of each window's first maximum among its in-bounds taps."""
+    _need_cuda(x, y, idx)
+    if x.dim() != 4:
+        raise RuntimeError("maxpool3s2p1_train_fwd: x must be [n, h, w, c]")
+    n, h, w, c = x.shape
+    _nhwc(x, (n, h, w, c), "maxpool3s2p1_train_fwd: x")
+    _nhwc(y, (n,) + _pool321_out(h, w) + (c,), "maxpool3s2p1_train_fwd: y")
+    _nhwc(idx, (n,) + _pool321_out(h, w) + (c,), "maxpool3s2p1_train_fwd: idx", torch.uint8)
+    check(load().yolo_maxpool3s2p1_train_fwd(_ptr(x), _ptr(y), _ptr(idx), n, h, w, c, stream_ptr()), "maxpool3s2p1_train_fwd")
+    return y, idx
+
+
+def maxpool3s2p1_bwd(dy, idx, dx):
+    """dx [n,h,w,c] (every element written) from dy and maxpool3s2p1_train_fwd's idx: a gather of up to four terms with a fixed fp32
+    summation order, rounded once."""
+    _need_cuda(dy, idx, dx)
+    if dx.dim() != 4:
+        raise RuntimeError("maxpool3s2p1_bwd: dx must be [n, h, w, c]")
+    n, h, w, c = dx.shape
+    _nhwc(dx, (n, h, w, c), "maxpool3s2p1_bwd: dx")
+    _nhwc(dy, (n,) + _pool321_out(h, w) + (c,), "maxpool3s2p1_bwd: dy")
+    _nhwc(idx, (n,) + _pool321_out(h, w) + (c,), "maxpool3s2p1_bwd: idx", torch.uint8)
+    check(load().yolo_maxpool3s2p1_bwd(_ptr(dy), _ptr(idx), _ptr(dx), n, h, w, c, stream_ptr()), "maxpool3s2p1_bwd")
+    return dx
+
+
+def _shuffle_views(fn, nhw, bufs):
+    """The (c_total, c_offset) of each (name, buffer [n,h,w,c_total] or None, channel offset, view width, alignment): dense bf16 buffers of
+    one pixel grid, each view inside its buffer."""
+    views = []
+    for what, t, off, width, v in bufs:
+        if t is None:
+            views.append((width, 0))
+            continue
+        if t.dim() != 4 or tuple(t.shape[:3]) != nhw:
+            raise RuntimeError(f"{fn}: {what} must be [n, h, w, c_total] on the grid {nhw}")
+        _nhwc(t, tuple(t.shape), f"{fn}: {what}")
+        ct = t.shape[3]
+        if off < 0 or off + width > ct or off % v or ct % v:
+            raise RuntimeError(f"{fn}: the view of {what} ({width} channels at {off} of {ct}) leaves its buffer or is not {v}-channel aligned")
+        views.append((ct, off))
+    return views
+
+
+def channel_shuffle2_fwd(a, b, y, half, c_slot, a_offset=0, b_offset=0, y_offset=0):
+    """channel_shuffle(cat(a, b), 2) in the two-slot layout (yolo_channel_shuffle2_fwd): ``a`` and ``b`` are the views [offset, offset +
+    c_slot) of dense bf16 [n,h,w,c_total] buffers holding ``half`` logical channels each, ``y`` the view [y_offset, y_offset + 2 c_slot):
+    every channel of it is written, the pad channels as zero."""
+    _need_cuda(a, b, y)
+    if y.dim() != 4:
+        raise RuntimeError("channel_shuffle2_fwd: y must be [n, h, w, c_total]")
+    n, h, w = y.shape[:3]
+    (a_v, b_v, y_v) = _shuffle_views("channel_shuffle2_fwd", (n, h, w), (("a", a, a_offset, c_slot, 1), ("b", b, b_offset, c_slot, 1),
+                                                                         ("y", y, y_offset, 2 * c_slot, 8)))
+    check(load().yolo_channel_shuffle2_fwd(_ptr(a), _ptr(b), _ptr(y), n, h, w, int(half), int(c_slot), a_v[0], a_v[1], b_v[0], b_v[1], y_v[0],
+                                           y_v[1], stream_ptr()), "channel_shuffle2_fwd")
+    return y
+
+
+def channel_shuffle2_bwd(dy, da, db, half, c_slot, dy_offset=0, da_offset=0, db_offset=0):
+    """The inverse of channel_shuffle2_fwd (yolo_channel_shuffle2_bwd): da[q] = dy_logical[2q], db[q] = dy_logical[2q + 1] for q < half,
+    zero for the pad channels [half, c_slot).  ``dy`` is the view [dy_offset, dy_offset + 2 c_slot) of a dense bf16 [n,h,w,c_total] buffer
+    (its pad channels are never read), ``da`` and ``db`` the 8-channel aligned views [offset, offset + c_slot) of theirs - every channel of
+    a view is written, nothing outside it.  ``da`` or ``db`` may be None (not both)."""
+    _need_cuda(dy, da, db)
+    if dy.dim() != 4:
+        raise RuntimeError("channel_shuffle2_bwd: dy must be [n, h, w, c_total]")
+    if da is None and db is None:
+        raise RuntimeError("channel_shuffle2_bwd: one of da and db is needed")
+    n, h, w = dy.shape[:3]
+    (y_v, a_v, b_v) = _shuffle_views("channel_shuffle2_bwd", (n, h, w), (("dy", dy, dy_offset, 2 * c_slot, 1), ("da", da, da_offset, c_slot, 8),
+                                                                         ("db", db, db_offset, c_slot, 8)))
+    check(load().yolo_channel_shuffle2_bwd(_ptr(dy), _ptr(da), _ptr(db), n, h, w, int(half), int(c_slot), y_v[0], y_v[1], a_v[0], a_v[1],
+                                           b_v[0], b_v[1], stream_ptr()), "channel_shuffle2_bwd")
+    return da, db
 
 
 def conv2d_splitk_plan(desc: YoloConvDesc, has_residual=False, has_preadd=False):

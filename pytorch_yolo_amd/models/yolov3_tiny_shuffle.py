@@ -14,41 +14,26 @@ a unit's output keeps its two halves in two slots of 64 / 128 / 256 physical cha
 keeps every conv on the fast LDS-DMA path); the weights recorded for every
 conv are the logical ones scattered into that space (zero rows, columns and biases for the pad channels, which ReLU
 and the linear depthwise stage keep at zero), the stride-1 split ``x.chunk(2)`` is two channel views, and
-``channel_shuffle(cat(a, b), 2)`` is one copy kernel (``yolo_channel_shuffle2_fwd``).
+``channel_shuffle(cat(a, b), 2)`` is one copy kernel (``yolo_channel_shuffle2_fwd``).  graph.Recorder's ``conv_bn_relu``,
+``shuffle_unit`` and ``conv_block_mapped`` hold that layout; models/train.ShuffleTracer has the same names and trains the
+model in it.
 """
 from __future__ import annotations
 
-import torch
 from torch import nn
 
 from .. import engine
-from ..kernels import roundup
+from ..graph import shuffle_slot
 from ..utils.torch_utils import fold_conv_bn
+from . import train as T
 from .yolo_base import ConvBlock, YOLOBase
 from .yolo_layer import Concat, Upsample
 
 _STAGES = ((4, 116), (8, 232), (4, 464))
-_SLOT = 32      # slot granule: 8 channels would do for the views; 32 keeps every 1x1 / 3x3 conv on the LDS-DMA fast path
 
 
 def _folded(conv: nn.Conv2d, bn: nn.BatchNorm2d):
     return fold_conv_bn(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-
-
-def _scatter(wb, out_map, out_phys, in_map=None, in_phys=None):
-    """Logical folded (weight OIHW, bias) -> the same conv in physical channels: row o goes to out_map[o], input
-    channel i (full convs only) to in_map[i]; everything else is zero."""
-    w, b = wb
-    cout, cin, k, _ = w.shape
-    if in_map is None:                                      # depthwise: [c, 1, 3, 3]
-        wp = torch.zeros((out_phys, 1, k, k), dtype=torch.float32)
-        wp[out_map] = w
-    else:
-        wp = torch.zeros((out_phys, in_phys, k, k), dtype=torch.float32)
-        wp[torch.as_tensor(out_map)[:, None], torch.as_tensor(in_map)[None, :]] = w
-    bp = torch.zeros(out_phys, dtype=torch.float32)
-    bp[out_map] = b
-    return wp, bp
 
 
 class _ConvBNReLU(nn.Sequential):
@@ -77,26 +62,9 @@ class InvertedResidual(nn.Module):
                                      nn.Conv2d(bf, bf, 1, 1, 0, bias=False), nn.BatchNorm2d(bf), nn.ReLU(inplace=True))
         self.bf = bf
 
-    def _branch2(self, g, x, in_map, hp):
-        h, b2 = self.bf, self.branch2
-        rows = list(range(h))
-        u = g.conv(x, _scatter(_folded(b2[0], b2[1]), rows, hp, in_map, x.c), act="relu")
-        v = g.dwconv(u, _scatter(_folded(b2[3], b2[4]), rows, hp), stride=self.stride, act="none")
-        return g.conv(v, _scatter(_folded(b2[5], b2[6]), rows, hp, rows, hp), act="relu")
-
     def _trace(self, g, x, in_map):
         """x: the physical tensor, in_map[i] = physical channel of logical input channel i.  Returns (y, map of y)."""
-        h, hp = self.bf, roundup(self.bf, _SLOT)
-        rows = list(range(h))
-        if self.stride > 1:
-            b1 = self.branch1
-            t = g.dwconv(x, _scatter(_folded(b1[0], b1[1]), in_map, x.c), stride=self.stride, act="none")
-            a = g.conv(t, _scatter(_folded(b1[2], b1[3]), rows, hp, in_map, x.c), act="relu")
-            b = self._branch2(g, x, in_map, hp)
-        else:
-            a = g.slice(x, 0, hp)                                 # x.chunk(2): the two slots
-            b = self._branch2(g, g.slice(x, hp, hp), rows, hp)
-        return g.shuffle2(a, b, h), rows + [hp + i for i in rows]
+        return g.shuffle_unit(self, x, in_map)
 
 
 class ShuffleEncoder(nn.Module):
@@ -120,8 +88,7 @@ class ShuffleEncoder(nn.Module):
         """Returns (route1 physical tensor, its channel map, route2)."""
         c1 = self.sequence1[0]
         cmap = list(range(24))
-        x = g.conv(x, _scatter(_folded(c1[0], c1[1]), cmap, roundup(24, _SLOT), list(range(c1[0].in_channels)), c1[0].in_channels),
-                   stride=2, act="relu")                       # 24 real channels in a 32-channel tensor
+        x = g.conv_bn_relu(c1, x, list(range(c1[0].in_channels)), shuffle_slot(24))    # 24 real channels in a 32-channel tensor
         x = g.maxpool(x, 3, 2)
         for stage in (self.sequence1[2], self.sequence1[3]):
             for unit in stage:
@@ -129,12 +96,19 @@ class ShuffleEncoder(nn.Module):
         route1, map1 = x, cmap
         for unit in self.sequence2[0]:
             x, cmap = unit._trace(g, x, cmap)
-        c5 = self.sequence2[1]
-        route2 = g.conv(x, _scatter(_folded(c5[0], c5[1]), list(range(1024)), 1024, cmap, x.c), act="relu")
+        route2 = g.conv_bn_relu(self.sequence2[1], x, cmap, 1024)
         return route1, map1, route2
 
 
 class YOLOv3TinyShuffle(YOLOBase):
+    # trains through pytorch_yolo_amd.forward_train(model, x, ops=DEVICE_OPS_SHUFFLE) only: with ops=None forward_train keeps raising what
+    # it raised before the class had a wiring, and so does model.train()(x) (the flip is the one-line follow-up of 3.6k)
+    _train_in_forward = False
+    _train_ops_by_name = True         # the caller names the table: forward_train(model, x) without one refuses this class
+    _train_tracer = T.ShuffleTracer   # conv_bn_relu, shuffle_unit and conv_block_mapped beside TrainTracer's vocabulary
+    _train_ops = T.DEVICE_OPS_SHUFFLE
+    _train_wiring = T.wiring          # training runs the same _trace on the ops of a table (models/train.py)
+
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         kd = self.kernels_divider
@@ -168,11 +142,11 @@ class YOLOv3TinyShuffle(YOLOBase):
     def _trace(self, g: engine.Recorder, x):
         """Reference _forward_encoder + forward (yolov3_tiny_shuffle.py:79-110)."""
         route1, map1, route2 = self.features._trace(g, x)
-        up = g.upsample2(self.sequence_branch1_1.branch1_conv1._trace(g, route2))
-        cat = g.concat([route1, up])                                     # [x_route1, x_branch1] (:83)
-        blk = self.sequence_branch1_2.branch1_conv2                      # its weights see 232 + 128 logical channels
-        cmap = map1 + [route1.c + i for i in range(up.c)]
-        b1 = g.conv(cat, _scatter(blk.folded(), list(range(blk.out_channels)), blk.out_channels, cmap, cat.c), act="leaky")
+        b = self.sequence_branch1_1.branch1_conv1._trace(g, route2)
+        cat = g.upsample_concat(b, route1, up_first=False)               # [x_route1, x_branch1] (:83)
+        n_route1, n_up = cat.shape[1] - b.shape[1], b.shape[1]           # (physical channels of the two parts)
+        cmap = map1 + [n_route1 + i for i in range(n_up)]
+        b1 = g.conv_block_mapped(self.sequence_branch1_2.branch1_conv2, cat, cmap)   # its weights see 232 + 128 logical channels
         g.head(g.plain_conv(self.sequence_branch1_2.branch1_conv3, b1), self.yolo1)
         b2 = self.sequence_branch2.branch2_conv1._trace(g, route2)
         g.head(g.plain_conv(self.sequence_branch2.branch2_conv2, b2), self.yolo2)

@@ -13,6 +13,9 @@ The ops (contracts in their docstrings; the kernels in DESIGN.md 3.6c-g):
                                     layer), the depthwise ConvBNReLU and the linear bottleneck with its add
     expand_dw_bn_block              the expand and the depthwise ConvBNReLU of an expanding inverted residual as one op: bit-equal to
                                     dw_bn_block(conv_bn_relu6_block(..)), the hidden activation never written
+    conv_bn_relu_block, max_pool_321, channel_shuffle2, shuffle_unit_block   ShuffleNetV2: the dense ConvBNReLU, MaxPool2d(3, 2, 1), the
+                                    channel shuffle in the two-slot layout and the stride-1 unit as one op, its halves read and its
+                                    gradient written as channel views
 models/train.py wires the training-mode forward of the models from them; the models' eval forward stays inference-only.
 
 The structure - every launch has one owner:
@@ -37,6 +40,10 @@ The structure - every launch has one owner:
                                         dwconv3x3_bwd_data, dwconv3x3_bnin_bwd_weight, _bn_grads, _conv_grads
     _ProjectBnFunction                  project_bn_block with a residual:  _conv_stats, bn_add_rounded_fwd / _bn_grads, _conv_grads;
                                         dy passes through to the residual.  Without one it is _ConvBnFunction
+    _MaxPool321Function, _ChannelShuffle2Function   max_pool_321, channel_shuffle2 (csrc/shuffle_train.hip, csrc/pointwise.hip)
+    _ShuffleUnitFunction                shuffle_unit_block:  _conv_stats on slot 1 of x (``in_offset``), _bn_act, _dw_forward, _conv_stats,
+                                        _bn_act, channel_shuffle2_fwd / channel_shuffle2_bwd, _bn_grads, _conv_grads, _bn_grads, the
+                                        depthwise gradients, _bn_grads, _conv_grads into slot 1 of the dx buffer (``dx_into``)
     _check_conv, _check_bn, _need_device    the argument checks: every ValueError, then the RuntimeError, then the first allocation
     _apply          Function.apply where a gradient can be asked for, the plain forward on detached inputs otherwise
 tests/test_ops_trace_gpu.py pins every op's launch list (tests/golden/ops_trace.json).
@@ -50,29 +57,33 @@ from ._lib import ACT_LEAKY01, ACT_NONE, ACT_RELU, DT_BF16, DT_F32
 
 __all__ = ["conv_block", "conv_bn_block", "down_block", "down_bn_block", "res_bn_block", "spp_concat", "upsample_concat", "max_pool",
            "pool_bn_block", "stem_block", "fire_block", "max_pool_ceil", "conv_bn_relu6_block", "dw_bn_block", "project_bn_block",
-           "expand_dw_bn_block"]
+           "expand_dw_bn_block", "conv_bn_relu_block", "max_pool_321", "channel_shuffle2", "shuffle_unit_block"]
 
 _ACTS = {"leaky": ACT_LEAKY01, "none": ACT_NONE}
 _ACTS_RELU = {**_ACTS, "relu": ACT_RELU}          # the ops without a batch norm at stride 1, and the unpadded first layer
 _RELU6 = (0.0, 6.0)                               # an activation given as (lo, hi) is a clamp: bn_clamp_fwd / bn_clamp_bwd
+_RELU = (0.0, float("inf"))                       # ReLU after a batch norm: the clamp without an upper bound
 _ACTS_DW = {"relu6": _RELU6, "none": ACT_NONE}    # dw_bn_block
 
 
 # ---- the launches and their owners -------------------------------------------------------------------------------------------------------
-def _desc(x, weight, act_id, out_f32, stride=1, pad=None, view=None):
-    n, c, h, w = x.shape
+def _desc(x, weight, act_id, out_f32, stride=1, pad=None, view=None, in_offset=None):
+    """``in_offset``: the conv reads the channel view [in_offset, in_offset + weight's cin) of the wider x (None: x is the operand)."""
+    n, ct_in, h, w = x.shape
     cout, _, k, _ = weight.shape
+    c, in_off = (ct_in, 0) if in_offset is None else (weight.shape[1], in_offset)
     ct, off = view if view is not None else (K.roundup(cout, 4) if out_f32 else cout, 0)
-    return K.conv_desc(n=n, h=h, w=w, cin=c, in_c_total=c, in_c_offset=0, cout=cout, out_c_total=ct, out_c_offset=off, ksize=k, stride=stride,
+    return K.conv_desc(n=n, h=h, w=w, cin=c, in_c_total=ct_in, in_c_offset=in_off, cout=cout, out_c_total=ct, out_c_offset=off, ksize=k, stride=stride,
                        act=act_id, kpad=K.roundup(k * k * c, 64), cout_pad=K.roundup(cout, 128), out_dtype=DT_F32 if out_f32 else DT_BF16,
                        pad=pad)
 
 
-def _forward(x, weight, bias, act_id, out_f32, stride=1, pad=None, into=None):
+def _forward(x, weight, bias, act_id, out_f32, stride=1, pad=None, into=None, in_offset=None):
     """The forward launch on a device-packed weight.  x: bf16, NCHW-shaped, dense channels-last.  Returns the NCHW-shaped
     channels-last result (a view of the [n, ho, wo, out_c_total] buffer the kernel wrote) and the descriptor.  ``pad``: None is k // 2.
-    ``into`` = (buffer [n, ho, wo, c_total], channel offset): the conv writes that channel view of a buffer the caller owns."""
-    d = _desc(x, weight, act_id, out_f32, stride, pad, None if into is None else (into[0].shape[3], into[1]))
+    ``into`` = (buffer [n, ho, wo, c_total], channel offset): the conv writes that channel view of a buffer the caller owns.
+    ``in_offset``: the conv reads the channel view of x that starts there, cin = the weight's (addresses only: no copy of the view)."""
+    d = _desc(x, weight, act_id, out_f32, stride, pad, None if into is None else (into[0].shape[3], into[1]), in_offset)
     with torch.cuda.device(x.device):
         packed, _, cout_pad = K.pack_conv_weight_dev(weight, d.cin)
         b = torch.zeros((cout_pad,), dtype=torch.float32, device=x.device)
@@ -84,10 +95,11 @@ def _forward(x, weight, bias, act_id, out_f32, stride=1, pad=None, into=None):
     return y[..., d.out_c_offset:d.out_c_offset + d.cout].permute(0, 3, 1, 2), d
 
 
-def _conv_grads(x, weight, g, d, need_x, need_w, need_b):
+def _conv_grads(x, weight, g, d, need_x, need_w, need_b, dx_into=None):
     """The gradients of the conv ``d`` on the dense bf16 g [n, ho, wo, roundup(cout, 8)], each only where asked: (dx, dw, db).  Stride 1
     runs csrc/conv_bwd.hip, stride 2 csrc/conv_down_bwd.hip: the downsample's entries at pad 1, the unpadded first layer's (a weight
-    gradient only) at pad 0.  Every buffer is allocated per call and fully written by its kernel."""
+    gradient only) at pad 0.  Every buffer is allocated per call and fully written by its kernel.  Where ``d`` reads an input view (stride
+    1), x is the wider buffer and ``dx_into`` the [n, h, w, in_c_total] buffer whose same view the data gradient writes: dx is that buffer."""
     down = d.stride == 2
     stem = down and d.pad == 0
     if stem and need_x:
@@ -108,7 +120,7 @@ def _conv_grads(x, weight, g, d, need_x, need_w, need_b):
         if not need_w:
             dw = None
     if need_x:
-        buf = torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=x.device)
+        buf = dx_into if dx_into is not None else torch.empty((d.n, d.h, d.w, d.cin), dtype=torch.bfloat16, device=x.device)
         if down:
             K.conv2d_down_bwd_data(g, K.pack_conv_weight_down_dev(weight), buf, d)
         else:
@@ -117,10 +129,10 @@ def _conv_grads(x, weight, g, d, need_x, need_w, need_b):
     return dx, dw, db
 
 
-def _conv_stats(x, weight, gamma, beta, running, momentum, eps, stride=1):
+def _conv_stats(x, weight, gamma, beta, running, momentum, eps, stride=1, in_offset=None):
     """conv (act none, zero bias) -> batch statistics over its output map; the running tensors that are given are updated in place.
     Returns the dense NHWC z the conv wrote, the conv's descriptor and the saved [4, cout] vectors (mean, invstd, scale, shift)."""
-    z, d = _forward(x, weight, None, ACT_NONE, False, stride)
+    z, d = _forward(x, weight, None, ACT_NONE, False, stride, in_offset=in_offset)
     z = z.permute(0, 2, 3, 1)
     with torch.cuda.device(x.device):
         saved = torch.empty((4, d.cout), dtype=torch.float32, device=x.device)
@@ -1040,3 +1052,252 @@ def expand_dw_bn_block(x, w_expand, gamma1, beta1, running_mean1, running_var1, 
     return _apply(_ExpandDwBnFunction, _expand_dw_forward,
                   (x, w_expand, gamma1.contiguous(), beta1.contiguous(), w_dw.contiguous(), gamma2.contiguous(), beta2.contiguous()),
                   running1, running2, float(momentum1), float(eps1), float(momentum2), float(eps2), int(stride))
+
+
+# ---- ShuffleNetV2 as it trains: the dense ConvBNReLU, MaxPool2d(3, 2, 1), the channel shuffle and the stride-1 unit -------
+def conv_bn_relu_block(x, weight, gamma, beta, running_mean=None, running_var=None, *, stride=1, momentum=0.1, eps=1e-5, training=True):
+    """``relu(batch_norm(conv2d(x, bf16(weight), stride=stride, padding=k // 2)))`` on the device, differentiable once: ShuffleNetV2's dense
+    Conv2d(bias=False) -> BatchNorm2d -> ReLU as it trains - 1x1 at stride 1 (the units' pointwise convs, conv5), 3x3 at stride 1 or 2
+    (conv1; its 3 input channels are zero-padded to 8 as in conv_block).
+
+    conv_bn_relu6_block's contract and launches with the clamp (0, +inf): yolo_bn_clamp_fwd / yolo_bn_clamp_bwd with lo 0 and hi +inf.
+    The gradient is 0 where the normalised value is <= 0 (torch's rule for ReLU).
+    Gradients: x bf16, weight, gamma and beta float32, each computed only where asked; two runs give the same bits."""
+    name = "conv_bn_relu_block"
+    if isinstance(stride, bool) or stride not in (1, 2):
+        raise ValueError(f"{name}: stride {stride!r} unsupported (1 or 2)")
+    _check_conv(name, x, weight, None, "none", (1, 3) if stride == 1 else (3,), True)
+    if not training:
+        raise ValueError(f"{name}: training=True only (the frozen layer is the models' inference path)")
+    running = _check_bn(name, x, weight, stride, gamma, beta, running_mean, running_var, True, momentum, eps)
+    _need_device(name, x, weight, gamma, beta, running_mean, running_var)
+    x, weight = _to_kernel_layout(x, weight)
+    return _apply(_ConvBnFunction, _bn_forward, (x, weight, gamma.contiguous(), beta.contiguous()), running, float(momentum), float(eps),
+                  _RELU, int(stride), 0)
+
+
+def _pool321_forward(x):
+    """The pool launch on the dense bf16 NCHW-shaped x: the NCHW-shaped result and idx (dense NHWC)."""
+    xn = x.permute(0, 2, 3, 1)
+    n, h, w, c = xn.shape
+    with torch.cuda.device(x.device):
+        y = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), dtype=torch.bfloat16, device=x.device)
+        idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+        K.maxpool3s2p1_train_fwd(xn, y, idx)
+    return y.permute(0, 3, 1, 2), idx
+
+
+class _MaxPool321Function(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        y, idx = _pool321_forward(x)
+        ctx.shape = tuple(x.permute(0, 2, 3, 1).shape)
+        ctx.save_for_backward(idx)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        idx, = ctx.saved_tensors
+        with torch.cuda.device(idx.device):
+            dx = torch.empty(ctx.shape, dtype=torch.bfloat16, device=idx.device)
+            K.maxpool3s2p1_bwd(_dense_bf16(dy).permute(0, 2, 3, 1), idx, dx)
+        return dx.permute(0, 3, 1, 2)
+
+
+def max_pool_321(x):
+    """``max_pool2d(x, 3, 2, padding=1)`` on the device, differentiable once: the pool of ShuffleNetV2.  The output map is
+    ``((h - 1) // 2 + 1, (w - 1) // 2 + 1)``; the taps of a window that lie outside the map are no candidates (-inf, not 0: a map of
+    negative values pools to negative values).  x [n, c, h, w], ``c % 8 == 0``, any h, w >= 1; bfloat16 dense channels-last is taken as it
+    is, anything else is converted by torch.  Returns bfloat16, channels-last.  The backward keeps the windows' tap numbers (uint8), not
+    x.  The gradient of a window goes to its first maximum in row-major order (torch's rule); the up to four terms of a pixel are summed
+    in fp32 in row-major window order and rounded once.  x must hold no NaN.  Under ``torch.no_grad()``, or when x does not require
+    grad, only the forward runs.  Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no CPU
+    fallback)."""
+    _check_map("max_pool_321", "x", x)
+    _need_device("max_pool_321", x)
+    return _apply(_MaxPool321Function, _pool321_forward, (_dense_bf16(x),))
+
+
+def _shuffle2_forward(a, b, half):
+    """The forward shuffle launch on two dense slot maps: the NCHW-shaped [n, 2 slot, h, w] result."""
+    an, bn = a.permute(0, 2, 3, 1), b.permute(0, 2, 3, 1)
+    n, h, w, slot = an.shape
+    with torch.cuda.device(a.device):
+        y = torch.empty((n, h, w, 2 * slot), dtype=torch.bfloat16, device=a.device)
+        K.channel_shuffle2_fwd(an, bn, y, half, slot)
+    return (y.permute(0, 3, 1, 2),)
+
+
+class _ChannelShuffle2Function(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, half):
+        ctx.half = half
+        return _shuffle2_forward(a, b, half)[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        need_a, need_b = ctx.needs_input_grad[:2]
+        da = db = None
+        if not (need_a or need_b):
+            return None, None, None
+        with torch.cuda.device(dy.device):
+            dy = _dense_bf16(dy).permute(0, 2, 3, 1)
+            n, h, w, c2 = dy.shape
+            if need_a:
+                da = torch.empty((n, h, w, c2 // 2), dtype=torch.bfloat16, device=dy.device)
+            if need_b:
+                db = torch.empty((n, h, w, c2 // 2), dtype=torch.bfloat16, device=dy.device)
+            K.channel_shuffle2_bwd(dy, da, db, ctx.half, c2 // 2)
+        return (None if da is None else da.permute(0, 3, 1, 2)), (None if db is None else db.permute(0, 3, 1, 2)), None
+
+
+def _check_half(name, half, slot):
+    if isinstance(half, bool) or not isinstance(half, int) or not 1 <= half <= slot:
+        raise ValueError(f"{name}: half must be an integer in [1, slot] (slot {slot}), not {half!r}")
+
+
+def channel_shuffle2(a, b, half):
+    """ShuffleNetV2's ``channel_shuffle(cat(a, b), groups=2)`` on the device, differentiable once, in the two-slot layout of the eval
+    trace: a and b [n, slot, h, w] hold ``half`` logical channels each in ``slot`` physical ones (``slot % 8 == 0``, zero beyond
+    ``half``); the result [n, 2 slot, h, w] holds logical channel j = (a, b)[j % 2][j // 2] at physical ``(j // half) slot + j % half``,
+    its pad channels zero.  bfloat16 dense channels-last maps are taken as they are, anything else is converted by torch.  The forward is
+    the copy kernel the eval models run (yolo_channel_shuffle2_fwd), the backward its inverse (yolo_channel_shuffle2_bwd): a copy, the
+    pad channels of both gradients written as zero; each gradient only where asked.  Wrong shapes raise ValueError before any launch; a
+    CPU tensor raises RuntimeError (there is no CPU fallback)."""
+    name = "channel_shuffle2"
+    _check_map(name, "a", a)
+    _check_map(name, "b", b)
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"{name}: a {tuple(a.shape)} and b {tuple(b.shape)} must have one shape [n, slot, h, w]")
+    _check_half(name, half, a.shape[1])
+    _need_device(name, a, b)
+    return _apply(_ChannelShuffle2Function, _shuffle2_forward, (_dense_bf16(a), _dense_bf16(b)), int(half))
+
+
+def _shuffle_unit_forward(x, w1, gamma1, beta1, w_dw, gamma2, beta2, w3, gamma3, beta3, half, running, momentum, eps):
+    """The launches of a stride-1 unit on the two-slot map x: the first 1x1 conv reads slot 1 of x as an input view, its batch norm + ReLU,
+    dw_bn_block's launches without an activation, the second 1x1 conv + batch norm + ReLU, and the shuffle with a = slot 0 of x read as a
+    view.  Returns the NCHW-shaped result and what the backward keeps."""
+    slot = w1.shape[0]
+    z1, d1, saved1 = _conv_stats(x, w1, gamma1, beta1, running[0], momentum[0], eps[0], in_offset=slot)
+    with torch.cuda.device(x.device):
+        y1 = _bn_act(z1, saved1, _RELU)
+    y2, z2, saved2, w9c = _dw_forward(y1.permute(0, 3, 1, 2), w_dw, gamma2, beta2, running[1], momentum[1], eps[1], ACT_NONE, 1)
+    z3, d3, saved3 = _conv_stats(y2, w3, gamma3, beta3, running[2], momentum[2], eps[2])
+    with torch.cuda.device(x.device):
+        y3 = _bn_act(z3, saved3, _RELU)
+        out = torch.empty((d1.n, d1.h, d1.w, 2 * slot), dtype=torch.bfloat16, device=x.device)
+        K.channel_shuffle2_fwd(x.permute(0, 2, 3, 1), y3, out, half, slot)
+    return out.permute(0, 3, 1, 2), (d1, d3), (z1, saved1, y1, w9c, z2, saved2, y2, z3, saved3)
+
+
+class _ShuffleUnitFunction(torch.autograd.Function):
+    """_shuffle_unit_forward with a backward: channel_shuffle2_bwd (da into slot 0 of the dx buffer, db dense), _bn_grads and _conv_grads of
+    the second 1x1 conv, _bn_grads and the depthwise gradients, _bn_grads and _conv_grads of the first 1x1 conv, whose data gradient
+    writes slot 1 of the dx buffer; each only where asked.  x, the weights, z and saved of the three layers and the two activations
+    between them are kept; neither half of x is copied."""
+
+    @staticmethod
+    def forward(ctx, x, w1, gamma1, beta1, w_dw, gamma2, beta2, w3, gamma3, beta3, half, running, momentum, eps):
+        out, ctx.descs, keep = _shuffle_unit_forward(x, w1, gamma1.detach(), beta1.detach(), w_dw, gamma2.detach(), beta2.detach(), w3,
+                                                     gamma3.detach(), beta3.detach(), half, running, momentum, eps)
+        ctx.half = half
+        ctx.save_for_backward(x, w1, w3, *keep)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, w1, w3, z1, saved1, y1, w9c, z2, saved2, y2, z3, saved3 = ctx.saved_tensors
+        d1, d3 = ctx.descs
+        need_x, need_w1, need_g1, need_b1, need_wd, need_g2, need_b2, need_w3, need_g3, need_b3 = ctx.needs_input_grad[:10]
+        need_y1 = need_x or need_w1 or need_g1 or need_b1               # what dw_bn_block's x would ask for
+        need_y2 = need_y1 or need_wd or need_g2 or need_b2              # what the second 1x1 conv's x would ask for
+        need_y3 = need_y2 or need_w3 or need_g3 or need_b3
+        dx = dw1 = dgamma1 = dbeta1 = dwd = dgamma2 = dbeta2 = dw3 = dgamma3 = dbeta3 = None
+        if not (need_x or need_y3):
+            return (None,) * 14
+        slot = d1.cin
+        with torch.cuda.device(x.device):
+            dy = _dense_bf16(dy).permute(0, 2, 3, 1)
+            n, h, w, _ = dy.shape
+            dxb = torch.empty((n, h, w, 2 * slot), dtype=torch.bfloat16, device=x.device) if need_x else None
+            db = torch.empty((n, h, w, slot), dtype=torch.bfloat16, device=x.device) if need_y3 else None
+            K.channel_shuffle2_bwd(dy, dxb, db, ctx.half, slot)
+            if need_y3:
+                g3, dgamma3, dbeta3 = _bn_grads(db.permute(0, 3, 1, 2), z3, saved3, _RELU, need_y2, need_w3, need_g3, need_b3)
+                dy2, dw3, _ = _conv_grads(y2, w3, g3, d3, need_y2, need_w3, False)
+            if need_y2:
+                g2, dgamma2, dbeta2 = _bn_grads(dy2, z2, saved2, ACT_NONE, need_y1, need_wd, need_g2, need_b2)
+                if need_y1:
+                    dy1 = torch.empty((n, h, w, slot), dtype=torch.bfloat16, device=x.device)
+                    K.dwconv3x3_bwd_data(g2, w9c, dy1, 1)
+                if need_wd:
+                    dwd = torch.empty((slot, 1, 3, 3), dtype=torch.float32, device=x.device)
+                    ws = torch.empty((K.dwconv3x3_bwd_weight_workspace_bytes(n, h, w, slot, 1),), dtype=torch.uint8, device=x.device)
+                    K.dwconv3x3_bwd_weight(y1, g2, dwd, ws, 1)
+            if need_y1:
+                g1, dgamma1, dbeta1 = _bn_grads(dy1.permute(0, 3, 1, 2), z1, saved1, _RELU, need_x, need_w1, need_g1, need_b1)
+                _, dw1, _ = _conv_grads(x, w1, g1, d1, need_x, need_w1, False, dx_into=dxb)
+            if need_x:
+                dx = dxb.permute(0, 3, 1, 2)
+        return (dx, dw1, dgamma1, dbeta1, dwd, dgamma2, dbeta2, dw3, dgamma3, dbeta3) + (None,) * 4
+
+
+def _triple(name, what, v):
+    """``v`` as (the first 1x1 conv's, the depthwise's, the second 1x1 conv's): a number for all three, or a triple."""
+    if isinstance(v, (tuple, list)):
+        if len(v) != 3:
+            raise ValueError(f"{name}: {what} must be a number or a triple (first 1x1's, depthwise's, second 1x1's), not {v!r}")
+        return tuple(v)
+    return v, v, v
+
+
+def shuffle_unit_block(x, half, w1, gamma1, beta1, running_mean1, running_var1, w_dw, gamma2, beta2, running_mean2, running_var2, w3, gamma3,
+                       beta3, running_mean3, running_var3, *, momentum=0.1, eps=1e-5):
+    """The stride-1 ShuffleNetV2 unit on the device as one op, differentiable once: with ``a, b = x[:, :slot], x[:, slot:]`` (``x.chunk(2)``
+    in the two-slot layout of channel_shuffle2) it is ``channel_shuffle2(a, conv_bn_relu_block(dw_bn_block(conv_bn_relu_block(b, w1, ..),
+    w_dw, .., act="none"), w3, ..), half)``, bit-equal to that composition - the output, the ten gradients and the six running tensors.
+
+    Neither half of x is copied: the first 1x1 conv reads slot 1 of x as an input view of the conv descriptor, and the shuffle reads slot
+    0 as a view.  In the backward the shuffle's inverse writes a's gradient straight into slot 0 of one [n, h, w, 2 slot] buffer and the
+    first conv's data gradient writes slot 1 of it: every element of x's gradient is written by exactly one of the two, with no zero-fill
+    and no add (autograd's slice backward fills two full maps with zeros and adds them).
+
+    x       [n, 2 slot, h, w], ``slot % 8 == 0``: ``half`` logical channels in each slot, zero beyond; bfloat16 dense channels-last is
+            taken as it is, anything else is converted by torch.
+    half    an integer in [1, slot].
+    w1, w3  float32 [slot, slot, 1, 1];  w_dw float32 [slot, 1, 3, 3].
+    gamma, beta, running_mean, running_var (1: the first 1x1 conv's BatchNorm2d, 2: the depthwise's, 3: the second 1x1 conv's)
+            float32 [slot]; the running tensors may be None, and those given are updated in place.
+    momentum, eps   a number for the three batch norms, or a triple.
+    Returns bfloat16 [n, 2 slot, h, w], channels-last.  Gradients: x bf16, the weights, gammas and betas float32, each computed only where
+    asked; two runs give the same bits.  Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no
+    CPU fallback)."""
+    name = "shuffle_unit_block"
+    _check_map(name, "x", x)
+    if x.shape[1] % 16:
+        raise ValueError(f"{name}: x needs two slots of a multiple of 8 channels (c {x.shape[1]})")
+    slot = x.shape[1] // 2
+    _check_half(name, half, slot)
+    slot_map = torch.empty((x.shape[0], slot, x.shape[2], x.shape[3]), device="meta")            # (shape only: a conv's operand)
+    for what, w_, k in (("w1", w1, 1), ("w3", w3, 1)):
+        if not isinstance(w_, torch.Tensor) or tuple(w_.shape) != (slot, slot, k, k):
+            raise ValueError(f"{name}: {what} must be [slot, slot, 1, 1] with slot = {slot}, not {list(getattr(w_, 'shape', ()))}")
+        _check_conv(name, slot_map, w_, None, "none", (1,), True)
+    if not isinstance(w_dw, torch.Tensor) or tuple(w_dw.shape) != (slot, 1, 3, 3):
+        raise ValueError(f"{name}: w_dw must be [slot, 1, 3, 3] with slot = {slot} (a 3x3 depthwise conv), not "
+                         f"{list(getattr(w_dw, 'shape', ()))}")
+    if w_dw.dtype != torch.float32:
+        raise ValueError(f"{name}: w_dw must be float32 [slot, 1, 3, 3]")
+    momentum, eps = _triple(name, "momentum", momentum), _triple(name, "eps", eps)
+    bns = ((w1, gamma1, beta1, running_mean1, running_var1), (w_dw, gamma2, beta2, running_mean2, running_var2),
+           (w3, gamma3, beta3, running_mean3, running_var3))
+    running = tuple(_check_bn(name, slot_map, w_, 1, g_, b_, rm, rv, True, momentum[i], eps[i]) for i, (w_, g_, b_, rm, rv) in enumerate(bns))
+    _need_device(name, x, *(t for bn in bns for t in bn))
+    return _apply(_ShuffleUnitFunction, _shuffle_unit_forward,
+                  (_dense_bf16(x), w1.contiguous(), gamma1.contiguous(), beta1.contiguous(), w_dw.contiguous(), gamma2.contiguous(),
+                   beta2.contiguous(), w3.contiguous(), gamma3.contiguous(), beta3.contiguous()),
+                  int(half), running, tuple(float(m) for m in momentum), tuple(float(e) for e in eps))
