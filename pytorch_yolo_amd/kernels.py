@@ -533,8 +533,9 @@ def bn_act_add_fwd(z, saved, residual, y, y_preadd, act):
 
 
 def _nhwc(t, shape, what, dtype=torch.bfloat16):
+    """``what``: the tensor's name in the message, or its parts (binding, name), joined only when the message is raised."""
     if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise RuntimeError(f"{what} must be contiguous {dtype} {list(shape)}")
+        raise RuntimeError(f"{what if isinstance(what, str) else ': '.join(what)} must be contiguous {dtype} {list(shape)}")
 
 
 def spp_train_fwd(x, y, idx):
@@ -590,41 +591,49 @@ def upsample2_concat_bwd(dy, da, db, *, n, h, w, ca, cb):
     return da, db
 
 
-# ---- the max-pools of a training step of YOLOv3-tiny / LiteYOLOv3 (csrc/pool_train.hip, one entry of csrc/batchnorm.hip, two of
-# csrc/route.hip) ---------------------------------------------------------------------------------------------------------
-def _pooled(h, w, stride):
-    if stride not in (1, 2):
-        raise RuntimeError(f"max-pool stride {stride} unsupported (1 or 2)")
-    return (h // 2, w // 2) if stride == 2 else (h, w)
+# ---- the max-pools of a training step: YOLOv3-tiny / LiteYOLOv3's here, SqueezeNet's and ShuffleNetV2's below (csrc/pool_train.hip, one
+# entry of csrc/batchnorm.hip, two of csrc/route.hip) ---------------------------------------------------------------------
+# the window pools of a training step (csrc/pool_train.hip): form -> the output map of an h x w input
+POOL_OUT = {"2/2": lambda h, w: (h // 2, w // 2),                           # MaxPool2d(2, 2): floor
+            "2/1": lambda h, w: (h, w),                                     # MaxPool2d(2, 1, padding=1, dilation=2)
+            "3/2 ceil": lambda h, w: (h // 2, w // 2),                      # MaxPool2d(3, 2, ceil_mode=True), h and w >= 2
+            "3/2/1": lambda h, w: ((h - 1) // 2 + 1, (w - 1) // 2 + 1)}     # MaxPool2d(3, 2, 1)
+
+
+def _pool(entry, fn, form, backward, x, y, idx, stride=None):
+    """The checks and the call of the six window-pool bindings ``fn``, library entry ``entry``.  ``x``: the unpooled map (dx where ``backward``),
+    ``y`` the pooled one (dy) and ``idx`` of its shape, all dense NHWC.  The maxpool pair gives its ``stride`` (the entry's last argument)
+    in place of a form."""
+    big, small = ("dx", "dy") if backward else ("x", "y")
+    _need_cuda(x, y, idx)
+    if x.dim() != 4:
+        raise RuntimeError(f"{fn}: {big} must be [n, h, w, c]")
+    n, h, w, c = x.shape
+    rest = ()
+    if stride is not None:
+        if stride not in (1, 2):
+            raise RuntimeError(f"max-pool stride {stride} unsupported (1 or 2)")
+        form, rest = "2/2" if stride == 2 else "2/1", (int(stride),)
+    ho, wo = POOL_OUT[form](h, w)
+    out = (n, ho, wo, c)
+    _nhwc(x, (n, h, w, c), (fn, big))
+    _nhwc(y, out, (fn, small))
+    _nhwc(idx, out, (fn, "idx"), torch.uint8)
+    ptrs = (_ptr(y), _ptr(idx), _ptr(x)) if backward else (_ptr(x), _ptr(y), _ptr(idx))
+    check(entry(*ptrs, n, h, w, c, *rest, stream_ptr()), fn)
 
 
 def maxpool_train_fwd(x, y, idx, stride):
     """The reference's MaxPool of the dense bf16 x [n,h,w,c].  stride 2: y [n,h/2,w/2,c] = MaxPool2d(2, 2)(x); stride 1: y [n,h,w,c] =
     MaxPool2d(2, 1, padding=1, dilation=2)(x).  idx uint8 of y's shape: the tap 0..3 of each window's first maximum."""
-    _need_cuda(x, y, idx)
-    if x.dim() != 4:
-        raise RuntimeError("maxpool_train_fwd: x must be [n, h, w, c]")
-    n, h, w, c = x.shape
-    ho, wo = _pooled(h, w, stride)
-    _nhwc(x, (n, h, w, c), "maxpool_train_fwd: x")
-    _nhwc(y, (n, ho, wo, c), "maxpool_train_fwd: y")
-    _nhwc(idx, (n, ho, wo, c), "maxpool_train_fwd: idx", torch.uint8)
-    check(load().yolo_maxpool_train_fwd(_ptr(x), _ptr(y), _ptr(idx), n, h, w, c, int(stride), stream_ptr()), "maxpool_train_fwd")
+    _pool(load().yolo_maxpool_train_fwd, "maxpool_train_fwd", None, False, x, y, idx, stride)
     return y, idx
 
 
 def maxpool_bwd(dy, idx, dx, stride):
     """dx [n,h,w,c] (every element written) from dy and maxpool_train_fwd's idx: a copy at stride 2, a gather of up to four terms with a
     fixed fp32 summation order, rounded once, at stride 1."""
-    _need_cuda(dy, idx, dx)
-    if dx.dim() != 4:
-        raise RuntimeError("maxpool_bwd: dx must be [n, h, w, c]")
-    n, h, w, c = dx.shape
-    ho, wo = _pooled(h, w, stride)
-    _nhwc(dx, (n, h, w, c), "maxpool_bwd: dx")
-    _nhwc(dy, (n, ho, wo, c), "maxpool_bwd: dy")
-    _nhwc(idx, (n, ho, wo, c), "maxpool_bwd: idx", torch.uint8)
-    check(load().yolo_maxpool_bwd(_ptr(dy), _ptr(idx), _ptr(dx), n, h, w, c, int(stride), stream_ptr()), "maxpool_bwd")
+    _pool(load().yolo_maxpool_bwd, "maxpool_bwd", None, True, dx, dy, idx, stride)
     return dx
 
 
@@ -669,33 +678,19 @@ def concat_upsample2_bwd(dy, db, da, *, n, h, w, cb, ca):
     return db, da
 
 
-# ---- the layers of a training step of YOLOv3-tiny/SqueezeNet (csrc/fire_train.hip, three entries of csrc/conv_down_bwd.hip; DESIGN.md
-# 3.6i) ---------------------------------------------------------------------------------------------------------------------------------
+# ---- the layers of a training step of YOLOv3-tiny/SqueezeNet (an instance of csrc/pool_train.hip, csrc/fire_train.hip, three entries of
+# csrc/conv_down_bwd.hip) -------------------------------------------------------------------------------------------------
 def maxpool3s2_train_fwd(x, y, idx):
     """y [n,h//2,w//2,c] = MaxPool2d(3, 2, ceil_mode=True)(x) of the dense bf16 x [n,h,w,c] (h, w >= 2; ceil((h - 3) / 2) + 1 = h // 2);
     idx uint8 of y's shape: the tap 3i + j (0..8) of each window's first maximum among its in-bounds taps."""
-    _need_cuda(x, y, idx)
-    if x.dim() != 4:
-        raise RuntimeError("maxpool3s2_train_fwd: x must be [n, h, w, c]")
-    n, h, w, c = x.shape
-    _nhwc(x, (n, h, w, c), "maxpool3s2_train_fwd: x")
-    _nhwc(y, (n, h // 2, w // 2, c), "maxpool3s2_train_fwd: y")
-    _nhwc(idx, (n, h // 2, w // 2, c), "maxpool3s2_train_fwd: idx", torch.uint8)
-    check(load().yolo_maxpool3s2_train_fwd(_ptr(x), _ptr(y), _ptr(idx), n, h, w, c, stream_ptr()), "maxpool3s2_train_fwd")
+    _pool(load().yolo_maxpool3s2_train_fwd, "maxpool3s2_train_fwd", "3/2 ceil", False, x, y, idx)
     return y, idx
 
 
 def maxpool3s2_bwd(dy, idx, dx):
     """dx [n,h,w,c] (every element written) from dy and maxpool3s2_train_fwd's idx: a gather of up to four terms with a fixed fp32
     summation order, rounded once."""
-    _need_cuda(dy, idx, dx)
-    if dx.dim() != 4:
-        raise RuntimeError("maxpool3s2_bwd: dx must be [n, h, w, c]")
-    n, h, w, c = dx.shape
-    _nhwc(dx, (n, h, w, c), "maxpool3s2_bwd: dx")
-    _nhwc(dy, (n, h // 2, w // 2, c), "maxpool3s2_bwd: dy")
-    _nhwc(idx, (n, h // 2, w // 2, c), "maxpool3s2_bwd: idx", torch.uint8)
-    check(load().yolo_maxpool3s2_bwd(_ptr(dy), _ptr(idx), _ptr(dx), n, h, w, c, stream_ptr()), "maxpool3s2_bwd")
+    _pool(load().yolo_maxpool3s2_bwd, "maxpool3s2_bwd", "3/2 ceil", True, dx, dy, idx)
     return dx
 
 
@@ -882,37 +877,19 @@ def dwconv3x3_bnin_bwd_weight(zin, saved, lo, hi, g, dw, workspace, stride):
     return dw
 
 
-# ---- the layers of a training step of YOLOv3-tiny/ShuffleNetV2 that are no conv (csrc/shuffle_train.hip, and the forward shuffle of
-# csrc/pointwise.hip) ---------------------------------------------------------------------------------------------------
-def _pool321_out(h, w):
-    return (h - 1) // 2 + 1, (w - 1) // 2 + 1
-
-
+# ---- the layers of a training step of YOLOv3-tiny/ShuffleNetV2 that are no conv (an instance of csrc/pool_train.hip, csrc/shuffle_train.hip,
+# and the forward shuffle of csrc/pointwise.hip) ----------------------------------------------------------------------------
 def maxpool3s2p1_train_fwd(x, y, idx):
     """y [n,ho,wo,c] = MaxPool2d(3, 2, padding=1)(x) of the dense bf16 x [n,h,w,c], ho = (h - 1) // 2 + 1; the taps outside the map are no
     candidates (-inf).  idx uint8 of y's shape: the tap 3i + j (0..8) of each window's first maximum among its in-bounds taps."""
-    _need_cuda(x, y, idx)
-    if x.dim() != 4:
-        raise RuntimeError("maxpool3s2p1_train_fwd: x must be [n, h, w, c]")
-    n, h, w, c = x.shape
-    _nhwc(x, (n, h, w, c), "maxpool3s2p1_train_fwd: x")
-    _nhwc(y, (n,) + _pool321_out(h, w) + (c,), "maxpool3s2p1_train_fwd: y")
-    _nhwc(idx, (n,) + _pool321_out(h, w) + (c,), "maxpool3s2p1_train_fwd: idx", torch.uint8)
-    check(load().yolo_maxpool3s2p1_train_fwd(_ptr(x), _ptr(y), _ptr(idx), n, h, w, c, stream_ptr()), "maxpool3s2p1_train_fwd")
+    _pool(load().yolo_maxpool3s2p1_train_fwd, "maxpool3s2p1_train_fwd", "3/2/1", False, x, y, idx)
     return y, idx
 
 
 def maxpool3s2p1_bwd(dy, idx, dx):
     """dx [n,h,w,c] (every element written) from dy and maxpool3s2p1_train_fwd's idx: a gather of up to four terms with a fixed fp32
     summation order, rounded once."""
-    _need_cuda(dy, idx, dx)
-    if dx.dim() != 4:
-        raise RuntimeError("maxpool3s2p1_bwd: dx must be [n, h, w, c]")
-    n, h, w, c = dx.shape
-    _nhwc(dx, (n, h, w, c), "maxpool3s2p1_bwd: dx")
-    _nhwc(dy, (n,) + _pool321_out(h, w) + (c,), "maxpool3s2p1_bwd: dy")
-    _nhwc(idx, (n,) + _pool321_out(h, w) + (c,), "maxpool3s2p1_bwd: idx", torch.uint8)
-    check(load().yolo_maxpool3s2p1_bwd(_ptr(dy), _ptr(idx), _ptr(dx), n, h, w, c, stream_ptr()), "maxpool3s2p1_bwd")
+    _pool(load().yolo_maxpool3s2p1_bwd, "maxpool3s2p1_bwd", "3/2/1", True, dx, dy, idx)
     return dx
 
 

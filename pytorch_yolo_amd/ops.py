@@ -18,33 +18,44 @@ The ops (contracts in their docstrings; the kernels in DESIGN.md 3.6c-g):
                                     gradient written as channel views
 models/train.py wires the training-mode forward of the models from them; the models' eval forward stays inference-only.
 
-The structure - every launch has one owner:
-    _forward        pack the weight, yolo_conv2d_fwd: the launch the models use, at either stride; ``into``: a channel view of a wider buffer
+The structure - every launch has one owner.  The pieces:
+    _forward        pack the weight, yolo_conv2d_fwd: the launch the models use, at either stride; ``into``: a channel view of a wider
+                    buffer; ``in_offset``: the operand is a channel view of a wider x
     _conv_grads     the conv's weight / bias and data gradients on g, each only where asked; dispatches on the descriptor's stride and pad
-                    (csrc/conv_bwd.hip, csrc/conv_down_bwd.hip) and is the only caller of those bindings
-    _conv_stats     conv with act none, then the batch statistics: the only caller of bn_train_stats
-    _bn_forward     _conv_stats and the tail: bn_act_fwd, bn_act_pool_fwd (pool stride 2) or bn_act_fwd + the stride-1 pool
+                    (csrc/conv_bwd.hip, csrc/conv_down_bwd.hip) and is the only caller of those bindings; ``dx_into``: a channel view
+    _stats          the batch statistics of a conv's output map: the only caller of bn_train_stats
+    _conv_stats     _forward with act none, then _stats
     _bn_act         the normalise-and-activate launch: bn_act_fwd, or bn_clamp_fwd where the activation is a (lo, hi) clamp
     _bn_grads       the batch-norm + activation backward (g, dgamma, dbeta by need): the only caller of bn_act_bwd / bn_clamp_bwd
-    _pool_forward, _pool_backward   the max-pool launches
-    _ConvFunction(stride)               conv_block, down_block:  _forward / conv2d_bwd_prepare, _conv_grads
-    _ConvBnFunction(stride, pool_stride)  conv_bn_block, down_bn_block, pool_bn_block:  _bn_forward / [_pool_backward,] _bn_grads, _conv_grads
-    _ResBnBlockFunction                 res_bn_block:  _conv_stats, bn_act_add_fwd / _bn_grads, _conv_grads; dy passes through to the residual
-    _SppConcatFunction, _UpsampleConcatFunction, _MaxPoolFunction   the glue ops (csrc/route.hip, csrc/pool_train.hip)
+    _bn_forward     _conv_stats and the tail: _bn_act, bn_act_pool_fwd (pool stride 2) or _bn_act + the stride-1 pool
+    _dw_pack        the depthwise weight rounded once to bf16, laid out [9, c]
+    _dw_stats       the depthwise conv - dwconv3x3, or dwconv3x3_bnin_fwd on an operand that is normalised and clamped as it is loaded -
+                    then _stats: the only caller of the two
+    _dw_grads       the depthwise data and weight gradients on g, each only where asked: the only caller of dwconv3x3_bwd_data,
+                    dwconv3x3_bwd_weight and dwconv3x3_bnin_bwd_weight
+    _POOLS          the four window max-pools (csrc/pool_train.hip): per form the forward and the backward binding; the output maps are
+                    kernels.POOL_OUT
+The Functions, each ``plain`` forward / backward:
+    _ConvFunction(stride, pad)          conv_block, down_block, stem_block:  _forward / conv2d_bwd_prepare, _conv_grads
+    _ConvBnFunction(act, stride, pool_stride)   conv_bn_block, down_bn_block, pool_bn_block, conv_bn_relu6_block, conv_bn_relu_block and
+                                        project_bn_block without a residual:  _bn_forward / [the pool's backward,] _bn_grads, _conv_grads
+    _ResBnFunction(act)                 res_bn_block, project_bn_block with a residual:  _conv_stats, bn_act_add_fwd (leaky) or
+                                        bn_add_rounded_fwd (none) / _bn_grads, _conv_grads; dy passes through to the residual
+    _PoolFunction(form)                 max_pool (both strides), max_pool_ceil, max_pool_321, and - its ``plain`` and ``grad`` - the pool
+                                        tail of _bn_forward and _ConvBnFunction
+    _SppConcatFunction, _UpsampleConcatFunction, _ChannelShuffle2Function   the glue ops (csrc/route.hip, csrc/pointwise.hip,
+                                        csrc/shuffle_train.hip)
     _FireFunction                       fire_block:  three _forward (the expands into one buffer) / fire_bwd_split, _conv_grads twice,
                                         fire_bwd_join, _conv_grads
-    _MaxPoolCeilFunction                max_pool_ceil (csrc/fire_train.hip)
-    _DwBnFunction                       dw_bn_block:  _dw_forward (dwconv3x3, bn_train_stats, _bn_act) / _bn_grads, dwconv3x3_bwd_data,
-                                        dwconv3x3_bwd_weight (csrc/dw_train.hip)
-    _ExpandDwBnFunction                 expand_dw_bn_block:  _conv_stats, dwconv3x3_bnin_fwd, bn_train_stats, _bn_act / _bn_grads,
-                                        dwconv3x3_bwd_data, dwconv3x3_bnin_bwd_weight, _bn_grads, _conv_grads
-    _ProjectBnFunction                  project_bn_block with a residual:  _conv_stats, bn_add_rounded_fwd / _bn_grads, _conv_grads;
-                                        dy passes through to the residual.  Without one it is _ConvBnFunction
-    _MaxPool321Function, _ChannelShuffle2Function   max_pool_321, channel_shuffle2 (csrc/shuffle_train.hip, csrc/pointwise.hip)
+    _DwBnFunction                       dw_bn_block:  _dw_forward (_dw_pack, _dw_stats, _bn_act) / _bn_grads, _dw_grads
+    _ExpandDwBnFunction                 expand_dw_bn_block:  _conv_stats, _dw_pack, _dw_stats (bnin), _bn_act / _bn_grads, _dw_grads (bnin),
+                                        _bn_grads, _conv_grads
     _ShuffleUnitFunction                shuffle_unit_block:  _conv_stats on slot 1 of x (``in_offset``), _bn_act, _dw_forward, _conv_stats,
-                                        _bn_act, channel_shuffle2_fwd / channel_shuffle2_bwd, _bn_grads, _conv_grads, _bn_grads, the
-                                        depthwise gradients, _bn_grads, _conv_grads into slot 1 of the dx buffer (``dx_into``)
-    _check_conv, _check_bn, _need_device    the argument checks: every ValueError, then the RuntimeError, then the first allocation
+                                        _bn_act, channel_shuffle2_fwd / channel_shuffle2_bwd, _bn_grads, _conv_grads, _bn_grads, _dw_grads,
+                                        _bn_grads, _conv_grads into slot 1 of the dx buffer (``dx_into``)
+The argument checks - every ValueError, then the RuntimeError, then the first allocation - and the dispatch:
+    _check_conv, _check_bn, _check_dw, _check_map, _check_pool, _check_stride, _train_only, _need_device
+    _conv_op, _bn_op, _fixed_bn_op, _res_op     the bodies the conv-bearing ops share;  _pool_op: the pool ops' tail
     _apply          Function.apply where a gradient can be asked for, the plain forward on detached inputs otherwise
 tests/test_ops_trace_gpu.py pins every op's launch list (tests/golden/ops_trace.json).
 """
@@ -64,6 +75,14 @@ _ACTS_RELU = {**_ACTS, "relu": ACT_RELU}          # the ops without a batch norm
 _RELU6 = (0.0, 6.0)                               # an activation given as (lo, hi) is a clamp: bn_clamp_fwd / bn_clamp_bwd
 _RELU = (0.0, float("inf"))                       # ReLU after a batch norm: the clamp without an upper bound
 _ACTS_DW = {"relu6": _RELU6, "none": ACT_NONE}    # dw_bn_block
+
+# The window max-pools, by the form that names their output map in kernels.POOL_OUT: (forward launch, backward launch, the arguments
+# after the tensors).  The bindings are looked up when they are called, so a test can wrap them.
+_MAXPOOL = (lambda *a: K.maxpool_train_fwd(*a), lambda *a: K.maxpool_bwd(*a))
+_POOLS = {"2/2": _MAXPOOL + ((2,),),
+          "2/1": _MAXPOOL + ((1,),),
+          "3/2 ceil": (lambda *a: K.maxpool3s2_train_fwd(*a), lambda *a: K.maxpool3s2_bwd(*a), ()),
+          "3/2/1": (lambda *a: K.maxpool3s2p1_train_fwd(*a), lambda *a: K.maxpool3s2p1_bwd(*a), ())}
 
 
 # ---- the launches and their owners -------------------------------------------------------------------------------------------------------
@@ -129,16 +148,23 @@ def _conv_grads(x, weight, g, d, need_x, need_w, need_b, dx_into=None):
     return dx, dw, db
 
 
+def _stats(z, gamma, beta, running, momentum, eps):
+    """The batch statistics over the dense NHWC map z; the running tensors that are given are updated in place.  Returns the saved
+    [4, c] vectors (mean, invstd, scale, shift)."""
+    c = z.shape[3]
+    with torch.cuda.device(z.device):
+        saved = torch.empty((4, c), dtype=torch.float32, device=z.device)
+        ws = torch.empty((K.bn_workspace_bytes(z.numel() // c, c),), dtype=torch.uint8, device=z.device)
+        K.bn_train_stats(z, gamma, beta, eps, momentum, running[0], running[1], saved, ws)
+    return saved
+
+
 def _conv_stats(x, weight, gamma, beta, running, momentum, eps, stride=1, in_offset=None):
-    """conv (act none, zero bias) -> batch statistics over its output map; the running tensors that are given are updated in place.
-    Returns the dense NHWC z the conv wrote, the conv's descriptor and the saved [4, cout] vectors (mean, invstd, scale, shift)."""
+    """conv (act none, zero bias) -> _stats over its output map.  Returns the dense NHWC z the conv wrote, the conv's descriptor and the
+    saved vectors."""
     z, d = _forward(x, weight, None, ACT_NONE, False, stride, in_offset=in_offset)
     z = z.permute(0, 2, 3, 1)
-    with torch.cuda.device(x.device):
-        saved = torch.empty((4, d.cout), dtype=torch.float32, device=x.device)
-        ws = torch.empty((K.bn_workspace_bytes(z.numel() // d.cout, d.cout),), dtype=torch.uint8, device=x.device)
-        K.bn_train_stats(z, gamma, beta, eps, momentum, running[0], running[1], saved, ws)
-    return z, d, saved
+    return z, d, _stats(z, gamma, beta, running, momentum, eps)
 
 
 def _bn_grads(dy, z, saved, act_id, need_x, need_w, need_g, need_b):
@@ -167,23 +193,6 @@ def _bn_act(z, saved, act_id):
     return y
 
 
-def _pool_forward(xn, stride):
-    """The pool launch on the dense bf16 [n, h, w, c] xn: (y, idx), both dense NHWC."""
-    n, h, w, c = xn.shape
-    ho, wo = (h // 2, w // 2) if stride == 2 else (h, w)
-    y = torch.empty((n, ho, wo, c), dtype=torch.bfloat16, device=xn.device)
-    idx = torch.empty((n, ho, wo, c), dtype=torch.uint8, device=xn.device)
-    K.maxpool_train_fwd(xn, y, idx, stride)
-    return y, idx
-
-
-def _pool_backward(dy, idx, shape, stride):
-    """dy (NCHW-shaped, any layout / dtype) -> the dense bf16 [n, h, w, c] gradient of the pool's input."""
-    dx = torch.empty(shape, dtype=torch.bfloat16, device=idx.device)
-    K.maxpool_bwd(_dense_bf16(dy).permute(0, 2, 3, 1), idx, dx, stride)
-    return dx
-
-
 def _bn_forward(x, weight, gamma, beta, running, momentum, eps, act_id, stride=1, pool_stride=0):
     """_conv_stats -> normalise and activate, and pool where ``pool_stride`` is not 0: the fused pass at pool stride 2, the two separate
     launches at pool stride 1.  Returns the NCHW-shaped result, the conv's descriptor, z, saved and the pool's idx (None without a pool)."""
@@ -192,17 +201,18 @@ def _bn_forward(x, weight, gamma, beta, running, momentum, eps, act_id, stride=1
     idx = None
     with torch.cuda.device(x.device):
         if pool_stride == 2:
-            y = torch.empty((n, h // 2, w // 2, c), dtype=torch.bfloat16, device=x.device)
+            y = torch.empty((n,) + K.POOL_OUT["2/2"](h, w) + (c,), dtype=torch.bfloat16, device=x.device)
             idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
             K.bn_act_pool_fwd(z, saved, y, idx, act_id)
+            y = y.permute(0, 3, 1, 2)
         else:
-            y = _bn_act(z, saved, act_id)
+            y = _bn_act(z, saved, act_id).permute(0, 3, 1, 2)
             if pool_stride == 1:
-                y, idx = _pool_forward(y, 1)
-    return y.permute(0, 3, 1, 2), d, z, saved, idx
+                y, idx = _PoolFunction.plain(y, "2/1")
+    return y, d, z, saved, idx
 
 
-# ---- the conv-bearing Functions ----------------------------------------------------------------------------------------------------------
+# ---- the Functions of a conv, a conv + batch norm, a conv + batch norm + residual, and a pool ------------------------------------------------
 class _ConvFunction(torch.autograd.Function):
     """_forward with a backward: prepare (g = dy act'(y)), then _conv_grads.  Once differentiable."""
 
@@ -232,6 +242,43 @@ class _ConvFunction(torch.autograd.Function):
         return dx, dw, db, None, None, None, None
 
 
+class _PoolFunction(torch.autograd.Function):
+    """A window max-pool of _POOLS on the dense bf16 NCHW-shaped x; the backward keeps the windows' tap numbers (uint8), not x."""
+
+    @staticmethod
+    def plain(x, form):
+        """The forward launch: the NCHW-shaped result and idx (dense NHWC)."""
+        launch, _, rest = _POOLS[form]
+        xn = x.permute(0, 2, 3, 1)
+        n, h, w, c = xn.shape
+        with torch.cuda.device(x.device):
+            y = torch.empty((n,) + K.POOL_OUT[form](h, w) + (c,), dtype=torch.bfloat16, device=x.device)
+            idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
+            launch(xn, y, idx, *rest)
+        return y.permute(0, 3, 1, 2), idx
+
+    @staticmethod
+    def grad(dy, idx, shape, form):
+        """The backward launch: dy (NCHW-shaped, any layout / dtype) -> the NCHW-shaped bf16 gradient of the pool's input [n, h, w, c]."""
+        _, launch, rest = _POOLS[form]
+        with torch.cuda.device(idx.device):
+            dx = torch.empty(shape, dtype=torch.bfloat16, device=idx.device)
+            launch(_dense_bf16(dy).permute(0, 2, 3, 1), idx, dx, *rest)
+        return dx.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def forward(ctx, x, form):
+        y, idx = _PoolFunction.plain(x, form)
+        ctx.shape, ctx.form = tuple(x.permute(0, 2, 3, 1).shape), form
+        ctx.save_for_backward(idx)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        return _PoolFunction.grad(dy, ctx.saved_tensors[0], ctx.shape, ctx.form), None
+
+
 class _ConvBnFunction(torch.autograd.Function):
     """_bn_forward (training=True) with a backward: through the pool where there is one (yolo_maxpool_bwd expands dy to the unpooled map),
     then _bn_grads and _conv_grads on its g.  x, weight, z, saved and idx are kept, y is not.  ``running`` is a tuple, so autograd does
@@ -251,28 +298,41 @@ class _ConvBnFunction(torch.autograd.Function):
         need_x, need_w, need_g, need_b = ctx.needs_input_grad[:4]
         with torch.cuda.device(x.device):
             if ctx.pool_stride:
-                dy = _pool_backward(dy, idx, tuple(z.shape), ctx.pool_stride).permute(0, 3, 1, 2)
+                dy = _PoolFunction.grad(dy, idx, tuple(z.shape), f"2/{ctx.pool_stride}")
             g, dgamma, dbeta = _bn_grads(dy, z, saved, ctx.act_id, need_x, need_w, need_g, need_b)
             dx, dw, _ = _conv_grads(x, weight, g, ctx.desc, need_x, need_w, False)
         return dx, dw, dgamma, dbeta, None, None, None, None, None, None
 
 
-class _ResBnBlockFunction(torch.autograd.Function):
-    """_conv_stats -> normalise, activate and add the residual in one pass (yolo_bn_act_add_fwd).  The backward is _ConvBnFunction's on
-    dy (+ the gradient of y_preadd where it was routed, summed in fp32 by torch); dy itself is the residual's."""
+def _res_forward(x, weight, gamma, beta, residual, running, momentum, eps, act_id, want_preadd):
+    """_conv_stats -> normalise, activate and add the residual in one pass: yolo_bn_act_add_fwd (leaky; ``want_preadd``: the value before
+    the add is written too), or without an activation yolo_bn_add_rounded_fwd (the normalised value is rounded to bf16 before the add, as
+    conv_bn_block(act="none") followed by a bf16 add would).  Returns the NCHW-shaped result - (y, y_preadd) with ``want_preadd`` - and
+    what the backward keeps."""
+    z, d, saved = _conv_stats(x, weight, gamma, beta, running, momentum, eps)
+    with torch.cuda.device(x.device):
+        y = torch.empty_like(z)
+        pre = torch.empty_like(z) if want_preadd else None
+        if act_id == ACT_NONE:
+            K.bn_add_rounded_fwd(z, saved, residual.permute(0, 2, 3, 1), y)
+        else:
+            K.bn_act_add_fwd(z, saved, residual.permute(0, 2, 3, 1), y, pre, act_id)
+    y = y.permute(0, 3, 1, 2)
+    return ((y, pre.permute(0, 3, 1, 2)) if want_preadd else y), d, z, saved
+
+
+class _ResBnFunction(torch.autograd.Function):
+    """_res_forward with a backward: _ConvBnFunction's on dy (+ the gradient of y_preadd where it was routed, summed in fp32 by torch); dy
+    itself is the residual's."""
 
     @staticmethod
-    def forward(ctx, x, weight, gamma, beta, residual, running, momentum, eps, want_preadd):
-        z, d, saved = _conv_stats(x, weight, gamma.detach(), beta.detach(), running, momentum, eps)
-        with torch.cuda.device(x.device):
-            y = torch.empty_like(z)
-            pre = torch.empty_like(z) if want_preadd else None
-            K.bn_act_add_fwd(z, saved, residual.detach().permute(0, 2, 3, 1), y, pre, ACT_LEAKY01)
-        ctx.desc = d
+    def forward(ctx, x, weight, gamma, beta, residual, running, momentum, eps, act_id, want_preadd):
+        out, ctx.desc, z, saved = _res_forward(x, weight, gamma.detach(), beta.detach(), residual.detach(), running, momentum, eps, act_id,
+                                               want_preadd)
+        ctx.act_id = act_id
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(x, weight, z, saved)
-        y = y.permute(0, 3, 1, 2)
-        return (y, pre.permute(0, 3, 1, 2)) if want_preadd else y
+        return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -281,7 +341,7 @@ class _ResBnBlockFunction(torch.autograd.Function):
         need_x, need_w, need_g, need_b, need_r = ctx.needs_input_grad[:5]
         dx = dw = dgamma = dbeta = None
         if dy is None and dpre is None:
-            return (None,) * 9
+            return (None,) * 10
         dres = dy if need_r else None
         if dy is not None and dpre is not None:
             dy = dy.float() + dpre.float()                              # one fp32 sum: yolo_bn_act_bwd takes an fp32 dy
@@ -289,9 +349,9 @@ class _ResBnBlockFunction(torch.autograd.Function):
             dy = dpre
         if need_x or need_w or need_g or need_b:
             with torch.cuda.device(x.device):
-                g, dgamma, dbeta = _bn_grads(dy, z, saved, ACT_LEAKY01, need_x, need_w, need_g, need_b)
+                g, dgamma, dbeta = _bn_grads(dy, z, saved, ctx.act_id, need_x, need_w, need_g, need_b)
                 dx, dw, _ = _conv_grads(x, weight, g, ctx.desc, need_x, need_w, False)
-        return dx, dw, dgamma, dbeta, dres, None, None, None, None
+        return dx, dw, dgamma, dbeta, dres, None, None, None, None, None
 
 
 # ---- the argument checks and the dispatch the ops share -----------------------------------------------------------------------------------
@@ -343,6 +403,28 @@ def _check_bn(name, x, weight, stride, gamma, beta, running_mean, running_var, t
     return running
 
 
+def _check_dw(name, w_dw, c, what, arg="w_dw", c8=False):
+    """The ValueErrors of the 3x3 depthwise weight ``arg`` over ``c`` channels, which the op's docstring calls ``what``; ``c8``: the
+    op's own ``c % 8 == 0`` check comes between the shape and the dtype (dw_bn_block, whose c is x's)."""
+    if not isinstance(w_dw, torch.Tensor) or tuple(w_dw.shape) != (c, 1, 3, 3):
+        raise ValueError(f"{name}: {arg} must be [{what}, 1, 3, 3] with {what} = {c} (a 3x3 depthwise conv), not "
+                         f"{list(getattr(w_dw, 'shape', ()))}")
+    if c8 and c % 8:
+        raise ValueError(f"{name}: {what} % 8 == 0 is required ({what} {c})")
+    if w_dw.dtype != torch.float32:
+        raise ValueError(f"{name}: {arg} must be float32 [{what}, 1, 3, 3]")
+
+
+def _check_stride(name, stride):
+    if isinstance(stride, bool) or stride not in (1, 2):
+        raise ValueError(f"{name}: stride {stride!r} unsupported (1 or 2)")
+
+
+def _train_only(name, training):
+    if not training:
+        raise ValueError(f"{name}: training=True only (the frozen layer is the models' inference path)")
+
+
 def _need_device(name, *tensors):
     if not all(t is None or t.is_cuda for t in tensors):
         raise RuntimeError(f"pytorch_yolo_amd.{name} runs on a ROCm device only (no CPU fallback)")
@@ -385,7 +467,8 @@ def _conv_op(name, ksizes, stride, x, weight, bias, act, out_dtype=torch.bfloat1
 
 
 def _bn_op(name, ksizes, stride, pool_stride, x, weight, gamma, beta, running_mean, running_var, training, momentum, eps, act):
-    """The body of conv_bn_block, down_bn_block and pool_bn_block, after _check_conv."""
+    """The body of the conv + batch-norm ops without a residual, after _check_conv.  ``act`` as given: a name of _ACTS, or the activation
+    itself - an ACT_* value or a (lo, hi) clamp."""
     running = _check_bn(name, x, weight, stride, gamma, beta, running_mean, running_var, training, momentum, eps)
     _need_device(name, x, weight, gamma, beta, running_mean, running_var)
     if not training:        # frozen statistics: the folded layer, as the models run it
@@ -393,7 +476,27 @@ def _bn_op(name, ksizes, stride, pool_stride, x, weight, gamma, beta, running_me
         return _conv_op(name, ksizes, stride, x, weight * s.reshape(-1, 1, 1, 1), beta - running[0] * s, act)
     x, weight = _to_kernel_layout(x, weight)
     return _apply(_ConvBnFunction, _bn_forward, (x, weight, gamma.contiguous(), beta.contiguous()), running, float(momentum), float(eps),
-                  _ACTS[act], stride, pool_stride)
+                  _ACTS.get(act, act), int(stride), pool_stride)
+
+
+def _fixed_bn_op(name, act_id, ksizes, x, weight, gamma, beta, running_mean, running_var, stride, training, momentum, eps):
+    """The conv + batch-norm ops whose activation is part of the layer (``act_id``: an ACT_* value or a clamp): ``ksizes`` at stride 1, 3x3
+    at stride 2, training=True only."""
+    _check_stride(name, stride)
+    _check_conv(name, x, weight, None, "none", ksizes if stride == 1 else (3,), True)
+    _train_only(name, training)
+    return _bn_op(name, ksizes, stride, 0, x, weight, gamma, beta, running_mean, running_var, True, momentum, eps, act_id)
+
+
+def _res_op(name, act_id, x, weight, gamma, beta, running_mean, running_var, residual, want_preadd, momentum, eps):
+    """The body of the conv + batch-norm ops with a residual, after _check_conv and _train_only."""
+    if not isinstance(residual, torch.Tensor) or tuple(residual.shape) != (x.shape[0], weight.shape[0], x.shape[2], x.shape[3]):
+        raise ValueError(f"{name}: residual must be [n, cout, h, w]")
+    running = _check_bn(name, x, weight, 1, gamma, beta, running_mean, running_var, True, momentum, eps)
+    _need_device(name, x, weight, residual, gamma, beta, running_mean, running_var)
+    x, weight = _to_kernel_layout(x, weight)
+    return _apply(_ResBnFunction, _res_forward, (x, weight, gamma.contiguous(), beta.contiguous(), _dense_bf16(residual)), running,
+                  float(momentum), float(eps), act_id, bool(want_preadd))
 
 
 # ---- ConvBlock at stride 1 and the downsample, BN folded or on batch statistics --------------------------------------------------------------
@@ -478,15 +581,8 @@ def res_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, re
                 FPN from the last unit of down3 / down4): ``(y, y_preadd)``; both carry gradients.
     Gradients: x bf16, weight, gamma and beta float32, residual the incoming gradient of y unchanged; each computed only where asked."""
     _check_conv("res_bn_block", x, weight, None, "leaky", (1, 3), True)
-    if not training:
-        raise ValueError("res_bn_block: training=True only (the frozen layer is the models' inference path)")
-    if not isinstance(residual, torch.Tensor) or tuple(residual.shape) != (x.shape[0], weight.shape[0], x.shape[2], x.shape[3]):
-        raise ValueError("res_bn_block: residual must be [n, cout, h, w]")
-    running = _check_bn("res_bn_block", x, weight, 1, gamma, beta, running_mean, running_var, True, momentum, eps)
-    _need_device("res_bn_block", x, weight, residual, gamma, beta, running_mean, running_var)
-    x, weight = _to_kernel_layout(x, weight)
-    return _ResBnBlockFunction.apply(x, weight, gamma.contiguous(), beta.contiguous(), _dense_bf16(residual), running, float(momentum),
-                                     float(eps), bool(want_preadd))
+    _train_only("res_bn_block", training)
+    return _res_op("res_bn_block", ACT_LEAKY01, x, weight, gamma, beta, running_mean, running_var, residual, want_preadd, momentum, eps)
 
 
 # ---- the SPP pyramid and the FPN's upsample + concat -------------------------------------------------------------------------------------
@@ -585,31 +681,18 @@ def upsample_concat(a, b, *, up_first=True):
 
 
 # ---- the max-pools of YOLOv3-tiny / LiteYOLOv3: MaxPool and ConvPoolBlock as they train -----------------------------------
-class _MaxPoolFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, stride):
-        xn = x.permute(0, 2, 3, 1)
-        with torch.cuda.device(x.device):
-            y, idx = _pool_forward(xn, stride)
-        ctx.shape, ctx.stride = tuple(xn.shape), stride
-        ctx.save_for_backward(idx)
-        return y.permute(0, 3, 1, 2)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        idx, = ctx.saved_tensors
-        with torch.cuda.device(idx.device):
-            dx = _pool_backward(dy, idx, ctx.shape, ctx.stride)
-        return dx.permute(0, 3, 1, 2), None
-
-
 def _check_pool(name, stride, h, w):
     if isinstance(stride, bool) or stride not in (1, 2):
         raise ValueError(f"{name}: pool stride must be 2 (MaxPool2d(2, 2)) or 1 (MaxPool2d(2, 1, padding=1, dilation=2)), not {stride!r}")
     if h < 2 or w < 2:
         raise ValueError(f"{name}: the pool needs a map of at least 2 x 2, got {h} x {w} (stride 2: empty output; stride 1: a window "
                          "would be all padding)")
+
+
+def _pool_op(name, form, x):
+    """The tail of the pool ops, after their ValueErrors."""
+    _need_device(name, x)
+    return _apply(_PoolFunction, _PoolFunction.plain, (_dense_bf16(x),), form)
 
 
 def max_pool(x, *, stride=2):
@@ -622,8 +705,7 @@ def max_pool(x, *, stride=2):
     is no CPU fallback)."""
     _check_map("max_pool", "x", x)
     _check_pool("max_pool", stride, x.shape[2], x.shape[3])
-    _need_device("max_pool", x)
-    return _MaxPoolFunction.apply(_dense_bf16(x), int(stride))
+    return _pool_op("max_pool", f"2/{int(stride)}", x)
 
 
 def pool_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *, pool_stride=2, training=True, momentum=0.1, eps=1e-5,
@@ -638,8 +720,7 @@ def pool_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *
     The backward expands the incoming gradient to the unpooled map (yolo_maxpool_bwd) and continues as conv_bn_block's.
     Gradients: x bf16, weight, gamma and beta float32, each computed only where asked; two runs give the same bits."""
     _check_conv("pool_bn_block", x, weight, None, act, (1, 3), True)
-    if not training:
-        raise ValueError("pool_bn_block: training=True only (the frozen layer is the models' inference path)")
+    _train_only("pool_bn_block", training)
     _check_pool("pool_bn_block", pool_stride, x.shape[2], x.shape[3])
     return _bn_op("pool_bn_block", (1, 3), 1, int(pool_stride), x, weight, gamma, beta, running_mean, running_var, True, momentum, eps, act)
 
@@ -666,29 +747,6 @@ def stem_block(x, weight, bias=None, *, act="relu"):
     return _apply(_ConvFunction, _forward, (x, weight, bias), _ACTS_RELU[act], False, 2, 0)
 
 
-class _MaxPoolCeilFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        xn = x.permute(0, 2, 3, 1)
-        n, h, w, c = xn.shape
-        with torch.cuda.device(x.device):
-            y = torch.empty((n, h // 2, w // 2, c), dtype=torch.bfloat16, device=x.device)
-            idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
-            K.maxpool3s2_train_fwd(xn, y, idx)
-        ctx.shape = tuple(xn.shape)
-        ctx.save_for_backward(idx)
-        return y.permute(0, 3, 1, 2)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        idx, = ctx.saved_tensors
-        with torch.cuda.device(idx.device):
-            dx = torch.empty(ctx.shape, dtype=torch.bfloat16, device=idx.device)
-            K.maxpool3s2_bwd(_dense_bf16(dy).permute(0, 2, 3, 1), idx, dx)
-        return dx.permute(0, 3, 1, 2)
-
-
 def max_pool_ceil(x):
     """``max_pool2d(x, 3, 2, ceil_mode=True)`` on the device, differentiable once: the pool of SqueezeNet 1.1.  The output map is
     ``(ceil((h - 3) / 2) + 1, ceil((w - 3) / 2) + 1)`` = ``(h // 2, w // 2)``; on an even map the last window is partial (its taps beyond
@@ -699,8 +757,7 @@ def max_pool_ceil(x):
     _check_map("max_pool_ceil", "x", x)
     if x.shape[2] < 2 or x.shape[3] < 2:
         raise ValueError(f"max_pool_ceil: the pool needs a map of at least 2 x 2, got {x.shape[2]} x {x.shape[3]}")
-    _need_device("max_pool_ceil", x)
-    return _MaxPoolCeilFunction.apply(_dense_bf16(x))
+    return _pool_op("max_pool_ceil", "3/2 ceil", x)
 
 
 def _fire_forward(x, sw, sb, w1, b1, w3, b3):
@@ -787,39 +844,61 @@ def conv_bn_relu6_block(x, weight, gamma, beta, running_mean=None, running_var=N
     for the two batch-norm passes, which clamp (yolo_bn_clamp_fwd / yolo_bn_clamp_bwd with lo 0, hi 6).  The gradient is 0 where the
     normalised value is <= 0 or >= 6 (torch's hardtanh rule).
     Gradients: x bf16, weight, gamma and beta float32, each computed only where asked; two runs give the same bits."""
-    if isinstance(stride, bool) or stride not in (1, 2):
-        raise ValueError(f"conv_bn_relu6_block: stride {stride!r} unsupported (1 or 2)")
-    _check_conv("conv_bn_relu6_block", x, weight, None, "none", (1, 3) if stride == 1 else (3,), True)
-    if not training:
-        raise ValueError("conv_bn_relu6_block: training=True only (the frozen layer is the models' inference path)")
-    running = _check_bn("conv_bn_relu6_block", x, weight, stride, gamma, beta, running_mean, running_var, True, momentum, eps)
-    _need_device("conv_bn_relu6_block", x, weight, gamma, beta, running_mean, running_var)
-    x, weight = _to_kernel_layout(x, weight)
-    return _apply(_ConvBnFunction, _bn_forward, (x, weight, gamma.contiguous(), beta.contiguous()), running, float(momentum), float(eps),
-                  _RELU6, int(stride), 0)
+    return _fixed_bn_op("conv_bn_relu6_block", _RELU6, (1, 3), x, weight, gamma, beta, running_mean, running_var, stride, training, momentum,
+                        eps)
+
+
+def _dw_pack(weight):
+    """The depthwise weight [c, 1, 3, 3] rounded once to bf16 and laid out [9, c] (float32, tap-major)."""
+    return weight.detach().to(torch.bfloat16).to(torch.float32).reshape(weight.shape[0], 9).t().contiguous()
+
+
+def _dw_stats(operand, w9c, gamma, beta, running, momentum, eps, stride, bnin=None):
+    """The depthwise conv (act none, zero bias) of the dense NHWC ``operand`` and _stats over its output map: z and saved.  ``bnin`` =
+    (saved, (lo, hi)): the operand is the map before that batch norm and clamp, which the conv applies as it loads it
+    (yolo_dwconv3x3_bnin_fwd; the padding is a zero of the transformed map)."""
+    n, h, w, c = operand.shape
+    with torch.cuda.device(operand.device):
+        z = torch.empty((n, (h - 1) // stride + 1, (w - 1) // stride + 1, c), dtype=torch.bfloat16, device=operand.device)
+        if bnin is None:
+            K.dwconv3x3(operand, w9c, torch.zeros((c,), dtype=torch.float32, device=operand.device), z, n=n, h=h, w=w, c=c, in_view=(c, 0),
+                        out_view=(c, 0), stride=stride, act=ACT_NONE)
+        else:
+            K.dwconv3x3_bnin_fwd(operand, bnin[0], bnin[1][0], bnin[1][1], w9c, z, stride)
+    return z, _stats(z, gamma, beta, running, momentum, eps)
+
+
+def _dw_grads(operand, g, w9c, stride, need_x, need_w, bnin=None):
+    """The gradients of the depthwise conv of ``operand`` (dense NHWC; ``bnin`` as in _dw_stats) on the dense bf16 g, each only where
+    asked: (the dense NHWC data gradient, the [c, 1, 3, 3] weight gradient).  Every buffer is allocated per call and fully written."""
+    n, h, w, c = operand.shape
+    dx = dw = None
+    with torch.cuda.device(operand.device):
+        if need_x:
+            dx = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=operand.device)
+            K.dwconv3x3_bwd_data(g, w9c, dx, stride)
+        if need_w:
+            dw = torch.empty((c, 1, 3, 3), dtype=torch.float32, device=operand.device)
+            ws = torch.empty((K.dwconv3x3_bwd_weight_workspace_bytes(n, h, w, c, stride),), dtype=torch.uint8, device=operand.device)
+            if bnin is None:
+                K.dwconv3x3_bwd_weight(operand, g, dw, ws, stride)
+            else:
+                K.dwconv3x3_bnin_bwd_weight(operand, bnin[0], bnin[1][0], bnin[1][1], g, dw, ws, stride)
+    return dx, dw
 
 
 def _dw_forward(x, weight, gamma, beta, running, momentum, eps, act_id, stride):
-    """The depthwise conv (act none, zero bias) on the weight rounded once to bf16 and laid out [9, c], the batch statistics of its output
-    map and the normalise-and-activate pass.  Returns the NCHW-shaped result and what the backward keeps: z, saved and the [9, c] weight."""
-    xn = x.permute(0, 2, 3, 1)
-    n, h, w, c = xn.shape
-    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    """_dw_pack, _dw_stats and the normalise-and-activate pass.  Returns the NCHW-shaped result and what the backward keeps: z, saved and
+    the [9, c] weight."""
+    w9c = _dw_pack(weight)
+    z, saved = _dw_stats(x.permute(0, 2, 3, 1), w9c, gamma, beta, running, momentum, eps, stride)
     with torch.cuda.device(x.device):
-        w9c = weight.detach().to(torch.bfloat16).to(torch.float32).reshape(c, 9).t().contiguous()
-        z = torch.empty((n, ho, wo, c), dtype=torch.bfloat16, device=x.device)
-        K.dwconv3x3(xn, w9c, torch.zeros((c,), dtype=torch.float32, device=x.device), z, n=n, h=h, w=w, c=c, in_view=(c, 0), out_view=(c, 0),
-                    stride=stride, act=ACT_NONE)
-        saved = torch.empty((4, c), dtype=torch.float32, device=x.device)
-        ws = torch.empty((K.bn_workspace_bytes(n * ho * wo, c),), dtype=torch.uint8, device=x.device)
-        K.bn_train_stats(z, gamma, beta, eps, momentum, running[0], running[1], saved, ws)
         y = _bn_act(z, saved, act_id)
     return y.permute(0, 3, 1, 2), z, saved, w9c
 
 
 class _DwBnFunction(torch.autograd.Function):
-    """_dw_forward with a backward: _bn_grads, then the depthwise data and weight gradients on its g, each only where asked.  x, the
-    [9, c] weight, z and saved are kept, y is not."""
+    """_dw_forward with a backward: _bn_grads, then _dw_grads on its g.  x, the [9, c] weight, z and saved are kept, y is not."""
 
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, running, momentum, eps, act_id, stride):
@@ -833,20 +912,10 @@ class _DwBnFunction(torch.autograd.Function):
     def backward(ctx, dy):
         x, w9c, z, saved = ctx.saved_tensors
         need_x, need_w, need_g, need_b = ctx.needs_input_grad[:4]
-        dx = dw = None
         with torch.cuda.device(x.device):
             g, dgamma, dbeta = _bn_grads(dy, z, saved, ctx.act_id, need_x, need_w, need_g, need_b)
-            xn = x.permute(0, 2, 3, 1)
-            n, h, w, c = xn.shape
-            if need_x:
-                buf = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=x.device)
-                K.dwconv3x3_bwd_data(g, w9c, buf, ctx.stride)
-                dx = buf.permute(0, 3, 1, 2)
-            if need_w:
-                dw = torch.empty((c, 1, 3, 3), dtype=torch.float32, device=x.device)
-                ws = torch.empty((K.dwconv3x3_bwd_weight_workspace_bytes(n, h, w, c, ctx.stride),), dtype=torch.uint8, device=x.device)
-                K.dwconv3x3_bwd_weight(xn, g, dw, ws, ctx.stride)
-        return dx, dw, dgamma, dbeta, None, None, None, None, None
+            dx, dw = _dw_grads(x.permute(0, 2, 3, 1), g, w9c, ctx.stride, need_x, need_w)
+        return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, dgamma, dbeta, None, None, None, None, None
 
 
 def dw_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *, stride=1, act="relu6", momentum=0.1, eps=1e-5, training=True):
@@ -868,55 +937,16 @@ def dw_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, *, 
         raise ValueError(f"{name}: x must be [n, c, h, w] and weight [c, 1, 3, 3]")
     if act not in _ACTS_DW:
         raise ValueError(f"{name}: act must be 'relu6' or 'none', not {act!r}")
-    if isinstance(stride, bool) or stride not in (1, 2):
-        raise ValueError(f"{name}: stride {stride!r} unsupported (1 or 2)")
+    _check_stride(name, stride)
     if min(x.shape) < 1:
         raise ValueError(f"{name}: empty tensor")
     c = x.shape[1]
-    if tuple(weight.shape) != (c, 1, 3, 3):
-        raise ValueError(f"{name}: weight must be [c, 1, 3, 3] with c = {c} (a 3x3 depthwise conv), not {list(weight.shape)}")
-    if c % 8:
-        raise ValueError(f"{name}: c % 8 == 0 is required (c {c})")
-    if weight.dtype != torch.float32:
-        raise ValueError(f"{name}: weight must be float32 [c, 1, 3, 3]")
-    if not training:
-        raise ValueError(f"{name}: training=True only (the frozen layer is the models' inference path)")
+    _check_dw(name, weight, c, "c", arg="weight", c8=True)
+    _train_only(name, training)
     running = _check_bn(name, x, weight, stride, gamma, beta, running_mean, running_var, True, momentum, eps)
     _need_device(name, x, weight, gamma, beta, running_mean, running_var)
     return _apply(_DwBnFunction, _dw_forward, (_dense_bf16(x), weight.contiguous(), gamma.contiguous(), beta.contiguous()), running,
                   float(momentum), float(eps), _ACTS_DW[act], int(stride))
-
-
-def _project_forward(x, weight, gamma, beta, residual, running, momentum, eps):
-    """_conv_stats -> normalise and add the residual in one pass (yolo_bn_add_rounded_fwd: the normalised value is rounded to bf16 before
-    the add, as conv_bn_block(act="none") followed by a bf16 add would)."""
-    z, d, saved = _conv_stats(x, weight, gamma, beta, running, momentum, eps)
-    with torch.cuda.device(x.device):
-        y = torch.empty_like(z)
-        K.bn_add_rounded_fwd(z, saved, residual.permute(0, 2, 3, 1), y)
-    return y.permute(0, 3, 1, 2), d, z, saved
-
-
-class _ProjectBnFunction(torch.autograd.Function):
-    """_project_forward with a backward: _ConvBnFunction's with act none on dy; dy itself is the residual's."""
-
-    @staticmethod
-    def forward(ctx, x, weight, gamma, beta, residual, running, momentum, eps):
-        out, ctx.desc, z, saved = _project_forward(x, weight, gamma.detach(), beta.detach(), residual.detach(), running, momentum, eps)
-        ctx.save_for_backward(x, weight, z, saved)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        x, weight, z, saved = ctx.saved_tensors
-        need_x, need_w, need_g, need_b, need_r = ctx.needs_input_grad[:5]
-        dx = dw = dgamma = dbeta = None
-        if need_x or need_w or need_g or need_b:
-            with torch.cuda.device(x.device):
-                g, dgamma, dbeta = _bn_grads(dy, z, saved, ACT_NONE, need_x, need_w, need_g, need_b)
-                dx, dw, _ = _conv_grads(x, weight, g, ctx.desc, need_x, need_w, False)
-        return dx, dw, dgamma, dbeta, (dy if need_r else None), None, None, None
 
 
 def project_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None, residual=None, *, momentum=0.1, eps=1e-5, training=True):
@@ -931,44 +961,29 @@ def project_bn_block(x, weight, gamma, beta, running_mean=None, running_var=None
                 bfloat16 dense channels-last is taken as it is, anything else is converted by torch.
     Gradients: x bf16, weight, gamma and beta float32, residual the incoming gradient unchanged; each computed only where asked."""
     name = "project_bn_block"
-    _check_conv(name, x, weight, None, "none", (1,), True)
-    if not training:
-        raise ValueError(f"{name}: training=True only (the frozen layer is the models' inference path)")
-    if residual is not None and (not isinstance(residual, torch.Tensor) or
-                                 tuple(residual.shape) != (x.shape[0], weight.shape[0], x.shape[2], x.shape[3])):
-        raise ValueError(f"{name}: residual must be [n, cout, h, w]")
-    running = _check_bn(name, x, weight, 1, gamma, beta, running_mean, running_var, True, momentum, eps)
-    _need_device(name, x, weight, residual, gamma, beta, running_mean, running_var)
-    x, weight = _to_kernel_layout(x, weight)
     if residual is None:
-        return _apply(_ConvBnFunction, _bn_forward, (x, weight, gamma.contiguous(), beta.contiguous()), running, float(momentum), float(eps),
-                      ACT_NONE, 1, 0)
-    return _apply(_ProjectBnFunction, _project_forward, (x, weight, gamma.contiguous(), beta.contiguous(), _dense_bf16(residual)), running,
-                  float(momentum), float(eps))
+        return _fixed_bn_op(name, ACT_NONE, (1,), x, weight, gamma, beta, running_mean, running_var, 1, training, momentum, eps)
+    _check_conv(name, x, weight, None, "none", (1,), True)
+    _train_only(name, training)
+    return _res_op(name, ACT_NONE, x, weight, gamma, beta, running_mean, running_var, residual, False, momentum, eps)
 
 
 # ---- the expand + depthwise pair of an expanding inverted residual as one op: the hidden activation is never written (DESIGN.md 3.6k) ------
 def _expand_dw_forward(x, w_expand, gamma1, beta1, w_dw, gamma2, beta2, running1, running2, momentum1, eps1, momentum2, eps2, stride):
-    """_conv_stats of the expand conv, the depthwise conv on its batch-normed and clamped output (yolo_dwconv3x3_bnin_fwd: the operand is
-    transformed as it is loaded), the statistics of that conv's output and the normalise-and-clamp pass.  Returns the NCHW-shaped result
-    and what the backward keeps: the expand conv's descriptor, z1, saved1, the [9, c] weight, z2 and saved2."""
+    """_conv_stats of the expand conv, the depthwise conv on its batch-normed and clamped output (_dw_stats with ``bnin``: the operand is
+    transformed as it is loaded), and the normalise-and-clamp pass.  Returns the NCHW-shaped result and what the backward keeps: the
+    expand conv's descriptor, z1, saved1, the [9, c] weight, z2 and saved2."""
     z1, d, saved1 = _conv_stats(x, w_expand, gamma1, beta1, running1, momentum1, eps1)
-    n, h, w, c = z1.shape
-    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    w9c = _dw_pack(w_dw)
+    z2, saved2 = _dw_stats(z1, w9c, gamma2, beta2, running2, momentum2, eps2, stride, bnin=(saved1, _RELU6))
     with torch.cuda.device(x.device):
-        w9c = w_dw.detach().to(torch.bfloat16).to(torch.float32).reshape(c, 9).t().contiguous()
-        z2 = torch.empty((n, ho, wo, c), dtype=torch.bfloat16, device=x.device)
-        K.dwconv3x3_bnin_fwd(z1, saved1, _RELU6[0], _RELU6[1], w9c, z2, stride)
-        saved2 = torch.empty((4, c), dtype=torch.float32, device=x.device)
-        ws = torch.empty((K.bn_workspace_bytes(n * ho * wo, c),), dtype=torch.uint8, device=x.device)
-        K.bn_train_stats(z2, gamma2, beta2, eps2, momentum2, running2[0], running2[1], saved2, ws)
         y = _bn_act(z2, saved2, _RELU6)
     return y.permute(0, 3, 1, 2), d, z1, saved1, w9c, z2, saved2
 
 
 class _ExpandDwBnFunction(torch.autograd.Function):
-    """_expand_dw_forward with a backward: _bn_grads on z2, the depthwise data gradient, the depthwise weight gradient on the transformed
-    z1 (yolo_dwconv3x3_bnin_bwd_weight), _bn_grads (clamp) on z1, _conv_grads; each only where asked.  x, the expand weight, z1, saved1,
+    """_expand_dw_forward with a backward: _bn_grads on z2, _dw_grads (the weight gradient on the transformed z1:
+    yolo_dwconv3x3_bnin_bwd_weight), _bn_grads (clamp) on z1, _conv_grads; each only where asked.  x, the expand weight, z1, saved1,
     the [9, c] weight, z2 and saved2 are kept; y1, the activation between the convs, is neither written nor kept."""
 
     @staticmethod
@@ -986,17 +1001,10 @@ class _ExpandDwBnFunction(torch.autograd.Function):
         x, w_expand, z1, saved1, w9c, z2, saved2 = ctx.saved_tensors
         need_x, need_we, need_g1, need_b1, need_wd, need_g2, need_b2 = ctx.needs_input_grad[:7]
         need_y1 = need_x or need_we or need_g1 or need_b1               # what dw_bn_block's x would ask for
-        dx = dwe = dgamma1 = dbeta1 = dwd = None
+        dx = dwe = dgamma1 = dbeta1 = None
         with torch.cuda.device(x.device):
             g2, dgamma2, dbeta2 = _bn_grads(dy, z2, saved2, _RELU6, need_y1, need_wd, need_g2, need_b2)
-            n, h, w, c = z1.shape
-            if need_y1:
-                d1 = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=x.device)
-                K.dwconv3x3_bwd_data(g2, w9c, d1, ctx.stride)
-            if need_wd:
-                dwd = torch.empty((c, 1, 3, 3), dtype=torch.float32, device=x.device)
-                ws = torch.empty((K.dwconv3x3_bwd_weight_workspace_bytes(n, h, w, c, ctx.stride),), dtype=torch.uint8, device=x.device)
-                K.dwconv3x3_bnin_bwd_weight(z1, saved1, _RELU6[0], _RELU6[1], g2, dwd, ws, ctx.stride)
+            d1, dwd = _dw_grads(z1, g2, w9c, ctx.stride, need_y1, need_wd, bnin=(saved1, _RELU6))
             if need_y1:
                 g1, dgamma1, dbeta1 = _bn_grads(d1.permute(0, 3, 1, 2), z1, saved1, _RELU6, need_x, need_we, need_g1, need_b1)
                 dx, dwe, _ = _conv_grads(x, w_expand, g1, ctx.desc, need_x, need_we, False)
@@ -1033,16 +1041,10 @@ def expand_dw_bn_block(x, w_expand, gamma1, beta1, running_mean1, running_var1, 
     bits.  Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no CPU fallback)."""
     name = "expand_dw_bn_block"
     _check_conv(name, x, w_expand, None, "none", (1,), True)
-    if isinstance(stride, bool) or stride not in (1, 2):
-        raise ValueError(f"{name}: stride {stride!r} unsupported (1 or 2)")
-    if not training:
-        raise ValueError(f"{name}: training=True only (the frozen layer is the models' inference path)")
+    _check_stride(name, stride)
+    _train_only(name, training)
     hidden = w_expand.shape[0]
-    if not isinstance(w_dw, torch.Tensor) or tuple(w_dw.shape) != (hidden, 1, 3, 3):
-        raise ValueError(f"{name}: w_dw must be [hidden, 1, 3, 3] with hidden = {hidden} (a 3x3 depthwise conv), not "
-                         f"{list(getattr(w_dw, 'shape', ()))}")
-    if w_dw.dtype != torch.float32:
-        raise ValueError(f"{name}: w_dw must be float32 [hidden, 1, 3, 3]")
+    _check_dw(name, w_dw, hidden, "hidden")
     (momentum1, momentum2), (eps1, eps2) = _pair(name, "momentum", momentum), _pair(name, "eps", eps)
     running1 = _check_bn(name, x, w_expand, 1, gamma1, beta1, running_mean1, running_var1, True, momentum1, eps1)
     hidden_map = torch.empty((x.shape[0], hidden, x.shape[2], x.shape[3]), device="meta")        # (shape only: the depthwise conv's input)
@@ -1063,46 +1065,7 @@ def conv_bn_relu_block(x, weight, gamma, beta, running_mean=None, running_var=No
     conv_bn_relu6_block's contract and launches with the clamp (0, +inf): yolo_bn_clamp_fwd / yolo_bn_clamp_bwd with lo 0 and hi +inf.
     The gradient is 0 where the normalised value is <= 0 (torch's rule for ReLU).
     Gradients: x bf16, weight, gamma and beta float32, each computed only where asked; two runs give the same bits."""
-    name = "conv_bn_relu_block"
-    if isinstance(stride, bool) or stride not in (1, 2):
-        raise ValueError(f"{name}: stride {stride!r} unsupported (1 or 2)")
-    _check_conv(name, x, weight, None, "none", (1, 3) if stride == 1 else (3,), True)
-    if not training:
-        raise ValueError(f"{name}: training=True only (the frozen layer is the models' inference path)")
-    running = _check_bn(name, x, weight, stride, gamma, beta, running_mean, running_var, True, momentum, eps)
-    _need_device(name, x, weight, gamma, beta, running_mean, running_var)
-    x, weight = _to_kernel_layout(x, weight)
-    return _apply(_ConvBnFunction, _bn_forward, (x, weight, gamma.contiguous(), beta.contiguous()), running, float(momentum), float(eps),
-                  _RELU, int(stride), 0)
-
-
-def _pool321_forward(x):
-    """The pool launch on the dense bf16 NCHW-shaped x: the NCHW-shaped result and idx (dense NHWC)."""
-    xn = x.permute(0, 2, 3, 1)
-    n, h, w, c = xn.shape
-    with torch.cuda.device(x.device):
-        y = torch.empty((n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c), dtype=torch.bfloat16, device=x.device)
-        idx = torch.empty(y.shape, dtype=torch.uint8, device=x.device)
-        K.maxpool3s2p1_train_fwd(xn, y, idx)
-    return y.permute(0, 3, 1, 2), idx
-
-
-class _MaxPool321Function(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        y, idx = _pool321_forward(x)
-        ctx.shape = tuple(x.permute(0, 2, 3, 1).shape)
-        ctx.save_for_backward(idx)
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        idx, = ctx.saved_tensors
-        with torch.cuda.device(idx.device):
-            dx = torch.empty(ctx.shape, dtype=torch.bfloat16, device=idx.device)
-            K.maxpool3s2p1_bwd(_dense_bf16(dy).permute(0, 2, 3, 1), idx, dx)
-        return dx.permute(0, 3, 1, 2)
+    return _fixed_bn_op("conv_bn_relu_block", _RELU, (1, 3), x, weight, gamma, beta, running_mean, running_var, stride, training, momentum, eps)
 
 
 def max_pool_321(x):
@@ -1115,8 +1078,7 @@ def max_pool_321(x):
     grad, only the forward runs.  Wrong shapes raise ValueError before any launch; a CPU tensor raises RuntimeError (there is no CPU
     fallback)."""
     _check_map("max_pool_321", "x", x)
-    _need_device("max_pool_321", x)
-    return _apply(_MaxPool321Function, _pool321_forward, (_dense_bf16(x),))
+    return _pool_op("max_pool_321", "3/2/1", x)
 
 
 def _shuffle2_forward(a, b, half):
@@ -1195,7 +1157,7 @@ def _shuffle_unit_forward(x, w1, gamma1, beta1, w_dw, gamma2, beta2, w3, gamma3,
 
 class _ShuffleUnitFunction(torch.autograd.Function):
     """_shuffle_unit_forward with a backward: channel_shuffle2_bwd (da into slot 0 of the dx buffer, db dense), _bn_grads and _conv_grads of
-    the second 1x1 conv, _bn_grads and the depthwise gradients, _bn_grads and _conv_grads of the first 1x1 conv, whose data gradient
+    the second 1x1 conv, _bn_grads and _dw_grads of the depthwise conv, _bn_grads and _conv_grads of the first 1x1 conv, whose data gradient
     writes slot 1 of the dx buffer; each only where asked.  x, the weights, z and saved of the three layers and the two activations
     between them are kept; neither half of x is copied."""
 
@@ -1231,13 +1193,7 @@ class _ShuffleUnitFunction(torch.autograd.Function):
                 dy2, dw3, _ = _conv_grads(y2, w3, g3, d3, need_y2, need_w3, False)
             if need_y2:
                 g2, dgamma2, dbeta2 = _bn_grads(dy2, z2, saved2, ACT_NONE, need_y1, need_wd, need_g2, need_b2)
-                if need_y1:
-                    dy1 = torch.empty((n, h, w, slot), dtype=torch.bfloat16, device=x.device)
-                    K.dwconv3x3_bwd_data(g2, w9c, dy1, 1)
-                if need_wd:
-                    dwd = torch.empty((slot, 1, 3, 3), dtype=torch.float32, device=x.device)
-                    ws = torch.empty((K.dwconv3x3_bwd_weight_workspace_bytes(n, h, w, slot, 1),), dtype=torch.uint8, device=x.device)
-                    K.dwconv3x3_bwd_weight(y1, g2, dwd, ws, 1)
+                dy1, dwd = _dw_grads(y1, g2, w9c, 1, need_y1, need_wd)
             if need_y1:
                 g1, dgamma1, dbeta1 = _bn_grads(dy1.permute(0, 3, 1, 2), z1, saved1, _RELU, need_x, need_w1, need_g1, need_b1)
                 _, dw1, _ = _conv_grads(x, w1, g1, d1, need_x, need_w1, False, dx_into=dxb)
@@ -1287,11 +1243,7 @@ def shuffle_unit_block(x, half, w1, gamma1, beta1, running_mean1, running_var1, 
         if not isinstance(w_, torch.Tensor) or tuple(w_.shape) != (slot, slot, k, k):
             raise ValueError(f"{name}: {what} must be [slot, slot, 1, 1] with slot = {slot}, not {list(getattr(w_, 'shape', ()))}")
         _check_conv(name, slot_map, w_, None, "none", (1,), True)
-    if not isinstance(w_dw, torch.Tensor) or tuple(w_dw.shape) != (slot, 1, 3, 3):
-        raise ValueError(f"{name}: w_dw must be [slot, 1, 3, 3] with slot = {slot} (a 3x3 depthwise conv), not "
-                         f"{list(getattr(w_dw, 'shape', ()))}")
-    if w_dw.dtype != torch.float32:
-        raise ValueError(f"{name}: w_dw must be float32 [slot, 1, 3, 3]")
+    _check_dw(name, w_dw, slot, "slot")
     momentum, eps = _triple(name, "momentum", momentum), _triple(name, "eps", eps)
     bns = ((w1, gamma1, beta1, running_mean1, running_var1), (w_dw, gamma2, beta2, running_mean2, running_var2),
            (w3, gamma3, beta3, running_mean3, running_var3))

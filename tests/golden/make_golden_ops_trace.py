@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Record tests/golden/ops_trace.json on the GPU: the launch list of every case of tests/test_ops_trace_gpu.py - case name -> list of
-records (binding name; per argument a tensor's dtype, shape and contiguity, a YoloConvDesc's fields, or the number itself), the forward's
-records followed by the backward's.  Sorted keys, one record per line; a rerun on the same code reproduces the file byte for byte.
+records (binding name; per argument a tensor's dtype, shape and contiguity, a YoloConvDesc's fields, the number itself, or a tuple of
+numbers as a list), the forward's records followed by the backward's.  Sorted keys, one record per line; a rerun on the same code reproduces the file byte for byte.
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden_ops_trace.py [output path]
 

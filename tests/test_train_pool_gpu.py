@@ -63,6 +63,30 @@ def test_pool_kernels_equal_the_restatement(case):
         assert not f32np(got["dx"])[:, h - 1].any() and not f32np(got["dx"])[:, :, w - 1].any()
 
 
+def test_stride2_backward_copies_the_gradient_bits():
+    """The 2/2 windows do not overlap, so the backward is a copy, not a sum: dx takes dy's bits - a -0.0 stays -0.0, which ``0.f + d`` would
+    turn into +0.0 - at the pixel idx names and is +0 everywhere else, the dropped odd row and column included."""
+    shape, out = (1, 3, 5, 8), (1, 1, 2, 8)
+    gen = torch.Generator().manual_seed(54)
+    x = torch.randn(shape, generator=gen).to(BF16).to(DEV)
+    dy = -(1.0 + torch.rand(out, generator=gen)).to(BF16)                      # negative normal values ...
+    dy[..., ::2] = -0.0                                                        # ... and -0.0 in every other channel
+    dy = dy.to(DEV)
+    y, idx = torch.empty(out, dtype=BF16, device=DEV), torch.empty(out, dtype=U8, device=DEV)
+    dx = torch.full(shape, NAN, dtype=BF16, device=DEV)
+    K.maxpool_train_fwd(x, y, idx, 2)
+    K.maxpool_bwd(dy, idx, dx, 2)
+    torch.cuda.synchronize()
+    dy_bits, tap = dy.view(torch.int16).cpu().numpy(), idx.cpu().numpy()
+    want = np.zeros(shape, dtype=np.int16)
+    for ox in range(out[2]):
+        for ch in range(out[3]):
+            want[0, tap[0, 0, ox, ch] // 2, 2 * ox + tap[0, 0, ox, ch] % 2, ch] = dy_bits[0, 0, ox, ch]
+    assert np.array_equal(dx.view(torch.int16).cpu().numpy(), want)
+    assert (want == np.int16(-0x8000)).sum() == 8 and (want != 0).sum() == 16    # the eight -0.0 arrived as -0.0
+    assert not want[:, 2].any() and not want[:, :, 4].any()
+
+
 @pytest.mark.parametrize("c", [8, 72])
 @pytest.mark.parametrize("hw", [(6, 4), (7, 5)], ids=["6x4", "7x5"])
 def test_bn_act_pool_equals_the_two_launches(hw, c):
